@@ -8,8 +8,15 @@ and shadows (adaptive-threshold statistics), ending with every per-image result 
 host.  Per-GPU batch is fixed (weak scaling): BASELINE.json config 4 is 4096 images over
 8 GPUs = 512 per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the headline (`value`,
+`ms_per_step`); --dump-outputs DIR also writes what the last timed step returned as
+DIR/<name>.npy (same arguments, same inputs and seeds: two builds compare output for
+output).  --full adds every secondary leg (the steps one batch at a time with the kernel
+timings and rooflines, the isolated-kernel step, served_batcher, per_class, cpu_baseline,
+the e2e lines); without it those fields are null.
 
 --gpus is authoritative: without a launcher (no WORLD_SIZE) and N > 1 the script starts N
 ranks itself under torch.distributed.run (child processes, before any GPU call); under a
@@ -362,6 +369,57 @@ def e2e_png(be, B, H, W, feats, steps, distinct, seed, fmt="PNG", decode_steps=2
                       f"{decode_steps} warm batches on the same threads"}
 
 
+def _hex_rgb(s):
+    """'#rrggbb' -> [r, g, b]; anything else (no colour in that slot) -> [-1, -1, -1]."""
+    if isinstance(s, str) and len(s) == 7 and s[0] == "#":
+        try:
+            return [int(s[1:3], 16), int(s[3:5], 16), int(s[5:7], 16)]
+        except ValueError:
+            pass
+    return [-1, -1, -1]
+
+
+def dump_outputs(path, recs, feats):
+    """--dump-outputs: the records the last timed step returned (backend.ImageFeatures, one
+    per image of the batch, in input order) as DIR/<name>.npy.  Every field of every image
+    is written (a 512-image batch is ~0.3 MB); integers that may pass 2^24 are float64.
+    Unused slots (fewer than 5 centres, no accent colour) hold -1."""
+    from low_level_feature_extraction_amd._lib import SHAPE_TYPES
+    from low_level_feature_extraction_amd.backend import SHADOW_LEVELS
+
+    os.makedirs(path, exist_ok=True)
+    n = len(recs)
+    out = {}
+    if "colors" in feats:
+        k = max([len(r.counts) for r in recs] + [1])
+        cen = np.full((n, k, 3), -1, np.float32)
+        cnt = np.full((n, k), -1, np.float64)
+        for i, r in enumerate(recs):
+            cen[i, :len(r.counts)] = r.centers_rgb
+            cnt[i, :len(r.counts)] = r.counts
+        out["centers_rgb"], out["counts"] = cen, cnt
+        out["n_unique"] = np.array([r.n_unique for r in recs], np.float64)
+        out["compactness"] = np.array([r.compactness for r in recs], np.float64)
+        # primary, background, three accents
+        out["palette_rgb"] = np.array([[_hex_rgb(c) for c in (r.palette[0], r.palette[1], *r.palette[2])]
+                                       for r in recs], np.float32).reshape(n, 5, 3)
+    if "shadows" in feats:
+        out["shadow_sum"] = np.array([r.shadow_sum for r in recs], np.float64)
+        out["shadow_count"] = np.array([r.shadow_count for r in recs], np.float64)
+        levels = list(SHADOW_LEVELS)
+        out["shadow_level"] = np.array([levels.index(r.shadow_level) for r in recs], np.float32)
+    if "shapes" in feats:
+        types = {v: k for k, v in SHAPE_TYPES.items()}
+        out["n_contours"] = np.array([r.n_contours for r in recs], np.float64)
+        out["n_shapes"] = np.array([len(r.shapes) for r in recs], np.float64)
+        # one row per shape, images in order: image, type code, x, y, width, height, border_radius, area
+        rows = [[i, types[s["type"]], s["x"], s["y"], s["width"], s["height"], s["border_radius"], s["area"]]
+                for i, r in enumerate(recs) for s in r.shapes]
+        out["shapes"] = np.array(rows, np.float64).reshape(len(rows), 8)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def _config_name(B, H, W, feats, pre):
     full = set(feats) == {"colors", "shapes", "shadows"}
     if (H, W) == (1080, 1920) and full and pre == "auto":
@@ -483,10 +541,28 @@ def main():
                          "41.6k vs 32.5k), else 2 (the 256-thread k-means packs beside the next batch's "
                          "kernels and a third batch only contends: 256 x 1080p colours+shapes 26.8k vs 22.1k, "
                          "512 x 1080p 27.3k vs 25.4k; profiles/r6/kmeans_wg/depth_small.txt)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, every secondary leg: the same steps one batch at a time and the "
+                         "kernel timings / rooflines from them, the isolated-kernel step, served_batcher, "
+                         "per_class, cpu_baseline and the e2e lines (each still governed by its own option). "
+                         "Without it the run sets up, warms up, times --steps steps and prints the headline "
+                         "fields; the secondary fields are null, and a leg option given anyway is named on stderr")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0's batch: one "
+                         "row per image, see dump_outputs) as DIR/<name>.npy, float32 / float64")
     ap.add_argument("--dry-run", action="store_true",
                     help="launch the ranks, initialise the process group and run the control-plane collectives "
                          "(barrier, MAX over ranks), print the line's identity fields with value null; no workload")
     args = ap.parse_args()
+    ignored = []
+    if not args.full:  # a plain run: the headline's steps only
+        legs = ("--cpu-baseline", "--cpu-images", "--cpu-workers", "--cpu-input", "--e2e-host-steps",
+                "--e2e-png-steps", "--e2e-jpeg-steps", "--e2e-alt-contours", "--e2e-at-scale", "--per-class-steps",
+                "--batcher-inflight", "--batcher-steps")
+        ignored = [o for o in legs if any(a == o or a.startswith(o + "=") for a in sys.argv[1:])]
+        args.cpu_baseline = "off"
+        args.e2e_host_steps = args.e2e_png_steps = args.e2e_jpeg_steps = 0
+        args.per_class_steps = args.batcher_steps = 0
 
     if check_world(args.gpus) == "launch":
         # no GPU call has happened in this process: the ranks are children, and this
@@ -508,6 +584,9 @@ def main():
     if world > 1 and args.e2e_at_scale == "off":
         args.e2e_host_steps = args.e2e_png_steps = args.e2e_jpeg_steps = 0
     rank = int(os.environ.get("RANK", "0"))
+    if ignored and rank == 0 and not args.dry_run:
+        print(f"bench.py: {', '.join(ignored)} only take effect with --full; this run times the headline alone "
+              f"and leaves those legs' fields null", file=sys.stderr)
     local = int(os.environ.get("LOCAL_RANK", "0"))
     # rehearsal of the N-rank path on a one-GPU box: every rank on cuda:0, gloo for the
     # control-plane collectives (RCCL refuses two ranks on one device)
@@ -607,9 +686,11 @@ def main():
         k-means."""
         batch = imgs if batch is None else batch
         futs = []
+        recs = None
         if not pipelined:
             for k in range(k_steps):
-                futs.append(asm_pool.submit(assemble_step, be.process(batch, feats, seed=seed0 + k, index_base=base)))
+                recs = be.process(batch, feats, seed=seed0 + k, index_base=base)
+                futs.append(asm_pool.submit(assemble_step, recs))
         else:
             pending = []
             ts = tc = 0.0  # serving thread: wall time in submit / collect
@@ -632,6 +713,7 @@ def main():
         t_last = time.perf_counter()
         shapes = sum(f.result() for f in futs)
         run_steps.tail_ms = (time.perf_counter() - t_last) * 1e3  # assembly left after the last collect
+        run_steps.last_recs = recs  # the last step's records (--dump-outputs)
         return shapes
 
     pipelined = args.pipeline == "on"
@@ -660,13 +742,17 @@ def main():
     host_ct = be.host_contour_stats(reset=True)
     asm_ms, asm_tail = list(asm_log), run_steps.tail_ms
     serving = getattr(run_steps, "serving", None) if pipelined else None
+    last_recs = run_steps.last_recs
     barrier()
     dt = shard.max_over_ranks(t1 - t0, device=coll_dev)
-    stats = be.kernel_stats()
+    # (pipelined steps are not event-timed: without --full a pipelined run has no kernel timings)
+    stats = be.kernel_stats() if not pipelined else {}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_recs, feats)
     # the same steps one batch at a time (llfe_process_batch): the reference rate and,
     # when pipelined, the kernel timings
     dt_sync = None
-    if pipelined:
+    if pipelined and args.full:
         be.set_profiling(True)
         barrier()
         ts0 = time.perf_counter()
@@ -681,12 +767,14 @@ def main():
     # one extra, untimed step with every kernel in order on one stream: isolated kernel
     # durations for the secondary rooflines (in the timed steps the shapes kernels share
     # the GPU with the colour front, which stretches their event-timed spans)
-    be.set_concurrency(False)
-    be.set_profiling(True)
-    be.process(imgs, feats, seed=args.seed, index_base=base)
-    torch.cuda.synchronize()
-    iso = be.kernel_stats()
-    be.set_concurrency(True)
+    iso = {}
+    if args.full:
+        be.set_concurrency(False)
+        be.set_profiling(True)
+        be.process(imgs, feats, seed=args.seed, index_base=base)
+        torch.cuda.synchronize()
+        iso = be.kernel_stats()
+        be.set_concurrency(True)
     be.set_profiling(False)
 
     # the product request path at the same load: single-image requests through the
@@ -851,6 +939,7 @@ def main():
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": round(dt / args.steps * 1e3, 3),
+        "full": args.full,
         "pipelined": pipelined,
         "inflight": be.inflight if pipelined else 1,
         "value_one_batch_at_a_time": round(total_images / dt_sync, 2) if dt_sync else None,

@@ -3,7 +3,7 @@
 # beside the headline of the same run, interleaved, twice each
 set -u -o pipefail
 mkdir -p gpurun_out
-ARGS="--cpu-baseline off --e2e-host-steps 0 --e2e-png-steps 0 --e2e-jpeg-steps 0 --per-class-steps 0 ${BD_ARGS:-}"
+ARGS="--full --cpu-baseline off --e2e-host-steps 0 --e2e-png-steps 0 --e2e-jpeg-steps 0 --per-class-steps 0 ${BD_ARGS:-}"
 for rep in 1 2; do
 for d in 2 3; do
     timeout -k 10 300 python bench.py $ARGS --batcher-inflight $d > gpurun_out/bd_$d.json 2> gpurun_out/bd_$d.err || { tail -20 gpurun_out/bd_$d.err; exit 1; }

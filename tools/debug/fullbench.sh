@@ -1,8 +1,10 @@
 set -u -o pipefail
-timeout -k 10 600 python bench.py > gpurun_out/full.json 2> gpurun_out/full.err || { tail -5 gpurun_out/full.err; exit 1; }
-python3 - <<'PY'
-import json
-d = json.loads(open("gpurun_out/full.json").read().strip().splitlines()[-1])
+OUT=${LLFE_OUT:-bench_out}
+mkdir -p $OUT
+timeout -k 10 600 python bench.py --full > $OUT/full.json 2> $OUT/full.err || { tail -5 $OUT/full.err; exit 1; }
+python3 - $OUT/full.json <<'PY'
+import json, sys
+d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 print(d["value"], d["ms_per_step"])
 print("png", d["e2e_png"])
 print("jpeg", d["e2e_jpeg"])

@@ -1,7 +1,7 @@
 #!/bin/bash
 # GPU box (round 6): the headline with 2 vs 3 batches in flight, interleaved, twice each
 set -u -o pipefail
-ARGS="--cpu-baseline off --e2e-host-steps 0 --e2e-png-steps 0 --e2e-jpeg-steps 0 --per-class-steps 0 --batcher-steps 0"
+ARGS="--full --cpu-baseline off --e2e-host-steps 0 --e2e-png-steps 0 --e2e-jpeg-steps 0 --per-class-steps 0 --batcher-steps 0"
 for rep in 1 2; do
 for d in 2 3; do
     timeout -k 10 300 python bench.py $ARGS --inflight $d > gpurun_out/if_$d.json 2> gpurun_out/if_$d.err || { tail -20 gpurun_out/if_$d.err; exit 1; }

@@ -8,7 +8,7 @@ cp $L /tmp/libllfe_keep_p.so
 for r in 1 2; do
   for v in tools/debug/variants/libllfe_*.so; do
     cp "$v" $L
-    timeout -k 10 300 python bench.py --cpu-baseline off --e2e-png-steps 0 --e2e-jpeg-steps 0 --e2e-host-steps 0 --per-class-steps 0 "$@" \
+    timeout -k 10 300 python bench.py --full --cpu-baseline off --e2e-png-steps 0 --e2e-jpeg-steps 0 --e2e-host-steps 0 --per-class-steps 0 "$@" \
         > gpurun_out/pv.json 2> gpurun_out/pv.err || { echo "$v failed"; tail -3 gpurun_out/pv.err; cp /tmp/libllfe_keep_p.so $L; exit 1; }
     python3 -c "
 import json,sys

@@ -1,5 +1,5 @@
 set -u -o pipefail
-ARGS="--cpu-baseline off --e2e-host-steps 0 --e2e-png-steps 0 --e2e-jpeg-steps 0 --per-class-steps 0"
+ARGS="--full --cpu-baseline off --e2e-host-steps 0 --e2e-png-steps 0 --e2e-jpeg-steps 0 --per-class-steps 0"
 for d in 2 3; do
 timeout -k 10 300 python bench.py $ARGS --batcher-inflight $d > gpurun_out/sv_$d.json 2> gpurun_out/sv_$d.err || { tail -20 gpurun_out/sv_$d.err; exit 1; }
 python3 -c "

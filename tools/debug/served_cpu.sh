@@ -3,7 +3,7 @@
 # (cpu.stat nr_throttled / throttled_usec deltas over the bench) for each host-thread budget
 # given as an argument (LLFE_HOST_THREADS; "default" = the placement's budget).
 set -u -o pipefail
-ARGS="--cpu-baseline off --e2e-host-steps 0 --e2e-png-steps 0 --e2e-jpeg-steps 0 --per-class-steps 0"
+ARGS="--full --cpu-baseline off --e2e-host-steps 0 --e2e-png-steps 0 --e2e-jpeg-steps 0 --per-class-steps 0"
 st() { cat /sys/fs/cgroup/cpu.stat 2>/dev/null | tr '\n' ' '; }
 for t in "$@"; do
     if [ "$t" = default ]; then unset LLFE_HOST_THREADS; else export LLFE_HOST_THREADS=$t; fi

@@ -5,7 +5,7 @@
 set -u -o pipefail
 mkdir -p gpurun_out
 export TMPDIR=/tmp
-ARGS="--cpu-baseline off --e2e-host-steps 0 --e2e-png-steps 0 --e2e-jpeg-steps 0 --per-class-steps 0 --batcher-steps 0 ${VT_ARGS:-}"
+ARGS="--full --cpu-baseline off --e2e-host-steps 0 --e2e-png-steps 0 --e2e-jpeg-steps 0 --per-class-steps 0 --batcher-steps 0 ${VT_ARGS:-}"
 for rep in 1 2; do
 for v in "$@"; do
     LLFE_LIB_PATH=tools/debug/variants/libllfe_$v.so timeout -k 10 300 python bench.py $ARGS > gpurun_out/vt_$v.json 2> gpurun_out/vt_$v.err || { tail -20 gpurun_out/vt_$v.err; exit 1; }

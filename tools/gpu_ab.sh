@@ -8,7 +8,7 @@ mkdir -p gpurun_out
 export TMPDIR=/tmp
 timeout -k 10 600 bash tools/debug/identity.sh > gpurun_out/${TAG}_identity.log 2>&1; rc=$?; cat gpurun_out/${TAG}_identity.log; [ $rc -eq 0 ] || exit 1
 grep -q DIFFERENT gpurun_out/${TAG}_identity.log && exit 1
-ARGS="--cpu-baseline off --e2e-host-steps 0 --e2e-png-steps 0 --e2e-jpeg-steps 0 --per-class-steps 0 --batcher-steps 0 $*"
+ARGS="--full --cpu-baseline off --e2e-host-steps 0 --e2e-png-steps 0 --e2e-jpeg-steps 0 --per-class-steps 0 --batcher-steps 0 $*"
 for v in A B A B; do
     if [ $v = A ]; then E="$SW"; else E=""; fi
     env $E timeout -k 10 300 python bench.py $ARGS > gpurun_out/${TAG}_$v.json 2> gpurun_out/${TAG}_$v.err || { tail -20 gpurun_out/${TAG}_$v.err; exit 1; }
