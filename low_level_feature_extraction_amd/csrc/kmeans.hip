@@ -21,6 +21,19 @@
 //  * compactness = sum of double(normL2Sqr) to the final centres with the labels of
 //    the last assignment.  Cluster sums are exact int64 (OpenCV accumulates float32
 //    sequentially; the difference is far below the uint8 truncation of the output).
+//
+// k-means++ trial sums as gains (pp_cubes).  A round needs T_j = sum_p min(D(p), d(p, t_j))
+// per trial, in total and per red-quarter partition; the round before left sum(D) exactly
+// (sum0, sm.pD[P]), so the sweep accumulates g_j = sum_p max(0, D(p) - d(p, t_j)) and the
+// round end takes T_j = sum(D) - g_j, pD[P] -= g_best[P].  g_j is non-zero only where t_j
+// is strictly closer than every chosen centre: on a box (cube, cell, super-cell) where t_j
+// is never strictly closer than the chosen centre c_k nearest to the box centre,
+// d(., t_j) >= d(., c_k) >= D and the box adds 0 -- also where a bisector between two chosen
+// centres cuts it, which the sums themselves could not decide.  Where c_k owns the box and
+// t_j is at least as close everywhere the box adds sum d(., c_k) - sum d(., t_j), in which the
+// sum |p|^2 terms cancel; an undecided cube's colours add max(0, H_t - max_m H_m) (H_c(p) =
+// 2 p.c - |c|^2), again without |p|^2.  All integers: every T_j, every prefix and every
+// choice is bit-identical to the plain sums.
 #include "kmeans_common.h"
 
 #include <mutex>
@@ -45,10 +58,15 @@ constexpr int kCellMinCubes = LLFE_KM_CELL_MIN;  // cube count from which the sw
 #define LLFE_KM_SUPS 1  // Lloyd tests 4 x 16 x 16 super-cells before cells
 #endif
 #ifndef LLFE_KM_PP_SUPS
-#define LLFE_KM_PP_SUPS 0  // k-means++ sweeps test 4 x 16 x 16 super-cells before cells (measured slower)
+#define LLFE_KM_PP_SUPS 0  // k-means++ sweeps test 4 x 16 x 16 super-cells before cells (measured slower, also
+                           // with the gain form)
 #endif
 #ifndef LLFE_KM_PP_SUPS_KK
 #define LLFE_KM_PP_SUPS_KK 0  // ... in the rounds with at most this many chosen centres (0: the first round)
+#endif
+#ifndef LLFE_KM_PP_ZSKIP
+#define LLFE_KM_PP_ZSKIP 1  // a partition change whose three gain accumulators are all zero skips its wave
+                            // sums and atomics (a partition far from the trials adds nothing)
 #endif
 #ifndef LLFE_KM_WIDE
 #define LLFE_KM_WIDE 0  // 1: the second build of this file (_build.py: 512 threads, unroll 4) as
@@ -209,7 +227,8 @@ struct KmSmem {
     int next_chunk;                      // next 64-cube chunk to hand out (cube sweeps)
     unsigned long long fail_pts;  // keys read point by point in this Lloyd sweep
     // cube-based k-means++ (pp_cubes)
-    unsigned long long psum[3][kParts];  // per trial and red-quarter partition: sum of T_j
+    unsigned long long psum[3][kParts];  // per trial and red-quarter partition: the trial's gain sum(D) - T_j
+                                         // (the first round: sum of d(., c0))
     unsigned long long pD[kParts];       // per partition: sum of D (the winning trial)
     unsigned long long pex[3];
     unsigned long long S[3];
@@ -694,7 +713,8 @@ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, int K, uint64
                 tz[j] = __builtin_amdgcn_readfirstlane(unpack_b(k));
             }
         }
-        // ---- trial sums T_j = sum min(D, d(., t_j)) per partition (kk == 0: sum d(., c0))
+        // ---- trial gains g_j = sum max(0, D - d(., t_j)) per partition, T_j = sum(D) - g_j
+        // (kk == 0: sum d(., c0))
         // the round's sweep, instantiated per number of chosen centres (KK = kk <= kMaxK - 1):
         // the centre loops become straight-line code without per-centre guards
         auto sweep = [&](auto KKc) __attribute__((always_inline)) {
@@ -739,14 +759,15 @@ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, int K, uint64
                 fails += (unsigned long long)count;
                 if (lane < count) {
                     // d(p, c) = |p|^2 - H_c(p), H_c(p) = 2 p.c - |c|^2 (exact integers): the
-                    // |p|^2 term is common to D and every trial, so min(D, d(p, t)) =
-                    // |p|^2 - max(max_m H_m, H_t).  2 p.c - |c|^2 = dot2((B, R), 2 (c_B, c_R))
-                    // over the 24-bit multiply-add G 2 c_G - |c|^2 (u32 arithmetic wraps to the
-                    // exact int): two VALU ops per centre
+                    // |p|^2 term is common to D and every trial, so the colour's gain
+                    // max(0, D - d(p, t)) = max(0, H_t - max_m H_m) and |p|^2 is never formed
+                    // (right whichever chosen centre is nearest: no owner is assumed here).
+                    // 2 p.c - |c|^2 = dot2((B, R), 2 (c_B, c_R)) over the 24-bit multiply-add
+                    // G 2 c_G - |c|^2 (u32 arithmetic wraps to the exact int): two VALU ops per
+                    // centre
                     const uint32_t kq = stg[(tail + lane) & (kStage - 1)];
                     const u16x2 rb = __builtin_bit_cast(u16x2, kq & 0x00FF00FFu);  // (B, R)
                     const uint32_t g = (kq >> 8) & 255u;
-                    const uint32_t p2 = __builtin_amdgcn_udot2(rb, rb, __umul24(g, g), false);
                     auto H = [&](u16x2 crb2, int cg2, int c2) {
                         return (int)__builtin_amdgcn_udot2(rb, crb2, __umul24(g, (uint32_t)cg2) + (0u - (uint32_t)c2), false);
                     };
@@ -754,9 +775,9 @@ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, int K, uint64
     #pragma unroll
                     for (int m = 1; m < kMaxK; m++)
                         if (m < KK) Hm = max(Hm, H(chrb[m], chg2[m], C2[m]));
-                    acc0 += p2 - (uint32_t)max(Hm, H(trb[0], tg2[0], T2[0]));
-                    acc1 += p2 - (uint32_t)max(Hm, H(trb[1], tg2[1], T2[1]));
-                    acc2 += p2 - (uint32_t)max(Hm, H(trb[2], tg2[2], T2[2]));
+                    acc0 += (uint32_t)max(H(trb[0], tg2[0], T2[0]) - Hm, 0);
+                    acc1 += (uint32_t)max(H(trb[1], tg2[1], T2[1]) - Hm, 0);
+                    acc2 += (uint32_t)max(H(trb[2], tg2[2], T2[2]) - Hm, 0);
                 }
                 tail += count;
             };
@@ -821,11 +842,12 @@ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, int K, uint64
                 if (lane == 0) b = atomicAdd(&sm.next_chunk, kRun);
                 return b;
             };
-            // Closed forms of a box (a cube, or a cell of up to four cubes) with origin o,
-            // count n, colour-offset sums S_u and S_u2: v_j = sum over its colours of
-            // min(D, d(., t_j)) (kk == 0: d(., t_0)), `fail` when some chosen centre or trial
-            // is not decided on the whole box.  ext: the box's offsets to its centre
-            // doubled, (3, 3, 3) for a cube, (3, 7, 7) for a cell; MK / NAx / NBx: its corner
+            // Closed forms of a box (a cube, a cell of up to four cubes, a super-cell of up to
+            // four cells) with origin o, count n, colour-offset sums S_u and S_u2: v_j = the
+            // gain of trial j on the box, sum over its colours of max(0, D - d(., t_j))
+            // (kk == 0: the sum of d(., t_0)), `fail` when some trial is not decided on the
+            // whole box.  ext: the box's offsets to its centre doubled, (3, 3, 3) for a cube,
+            // (3, 7, 7) for a cell, (3, 15, 15) for a super-cell; MK / NAx / NBx: its corner
             // margins.
             auto box_vals = [&](int ox, int oy, int oz, int n, int sx, int sy, int sz, int s2, const int *MK,
                                 const int *NAx, const int *NBx, int ex, int ey, int ez, uint32_t &v0, uint32_t &v1,
@@ -889,19 +911,23 @@ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, int K, uint64
                     if (m >= KK) break;
                     if (m != k) owned = owned & (Dc[m] - Dk - MK[m * kMaxK + k] >= 0);
                 }
-                // box sums: P + n D_c(o) - 2 c.S_u, P = n |o|^2 + 2 o.S_u + S_u2
-                const int Pc = __mul24(n, odot(orb, oy)) + 2 * sdot(orb, oy) + s2;
-                const uint32_t ds = (uint32_t)(Pc + __mul24(n, Dk) - sdot(krb, ky));
+                // Gains.  Box sums are P + n D_c(o) - 2 c.S_u with P = n |o|^2 + 2 o.S_u + S_u2
+                // common to every centre, so P cancels out of sum d(., c_k) - sum d(., t_j) =
+                // n (D_k(o) - D_t(o)) - (2 c_k.S_u - 2 t_j.S_u).  A: t_j is never strictly
+                // closer than c_k, hence never closer than D <= d(., c_k): gain 0 whether or not
+                // c_k owns the box.  B on an owned box: D = d(., c_k) and t_j is at least as
+                // close everywhere, the gain is the difference of the two sums (>= 0, and
+                // < 2^32: n <= 1024 colours of at most 195 075 each).
+                const int sk = sdot(krb, ky);
+                bool dec = true;
                 uint32_t vv[3];
-                bool dec = owned;
     #pragma unroll
                 for (int j = 0; j < 3; j++) {
-                    const int Dt = T2[j] - odot(trb[j], tg2[j]);
-                    const int f = Dt - Dk;
+                    const int f = T2[j] - odot(trb[j], tg2[j]) - Dk;
                     const bool A = f - NAx[j * kMaxK + k] >= 0;  // t_j never strictly closer than c_k
                     const bool B = f + NBx[j * kMaxK + k] <= 0;  // t_j always at least as close
-                    dec = dec & (A | B);
-                    vv[j] = A ? ds : (uint32_t)(Pc + __mul24(n, Dt) - sdot(trb[j], tg2[j]));
+                    dec = dec & (A | (owned & B));
+                    vv[j] = A ? 0u : (uint32_t)(sdot(trb[j], tg2[j]) - sk - __mul24(n, f));
                 }
                 v0 = vv[0];
                 v1 = vv[1];
@@ -940,11 +966,14 @@ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, int K, uint64
                 if (Pseg != Pcur) {
                     if (Pcur >= 0) {
                         flush_pk();
-                        const unsigned long long a0 = wave_sum(acc0), a1 = wave_sum(acc1), a2 = wave_sum(acc2);
-                        if (lane == 0) {
-                            atomicAdd(&sm.psum[0][Pcur], a0);
-                            atomicAdd(&sm.psum[1][Pcur], a1);
-                            atomicAdd(&sm.psum[2][Pcur], a2);
+                        // (gains: a partition far from the three trials adds nothing)
+                        if (!LLFE_KM_PP_ZSKIP || __ballot((acc0 | acc1 | acc2) != 0)) {
+                            const unsigned long long a0 = wave_sum(acc0), a1 = wave_sum(acc1), a2 = wave_sum(acc2);
+                            if (lane == 0) {
+                                atomicAdd(&sm.psum[0][Pcur], a0);
+                                atomicAdd(&sm.psum[1][Pcur], a1);
+                                atomicAdd(&sm.psum[2][Pcur], a2);
+                            }
                         }
                     }
                     acc0 = acc1 = acc2 = 0;
@@ -1005,7 +1034,8 @@ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, int K, uint64
                     }
                 };
                 // (round 6) the first round (KK = 0: the sums of d(., c0), every box decided) walks
-                // the super-cells; the later rounds only with LLFE_KM_PP_SUPS (measured slower)
+                // the super-cells; the later rounds only with LLFE_KM_PP_SUPS (measured slower, with the
+                // sums and again with the gains, which decide more super-cells: DESIGN.md §3)
                 if (stab && (LLFE_KM_PP_SUPS || KK <= LLFE_KM_PP_SUPS_KK)) {
                     // super-cells first, the same closed forms with extents (3, 15, 15); the
                     // cells of the undecided ones (one partition at a time) are listed in the wave's
@@ -1184,8 +1214,9 @@ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, int K, uint64
         if (wid == 0) {
 #pragma unroll
             for (int j = 0; j < 3; j++) {
+                // rounds >= 1 hold the trials' gains: T_j = sum(D) - g_j (g_j <= sum(D))
                 const unsigned long long s = wave_sum(sm.psum[j][lane]);
-                if (lane == 0) sm.S[j] = s;
+                if (lane == 0) sm.S[j] = kk > 0 ? sum0 - s : s;
             }
         }
         __syncthreads();
@@ -1199,7 +1230,7 @@ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, int K, uint64
                 }
         }
         sum0 = sm.S[best];
-        if (tid < kParts) sm.pD[tid] = sm.psum[best][tid];
+        if (tid < kParts) sm.pD[tid] = kk > 0 ? sm.pD[tid] - sm.psum[best][tid] : sm.psum[0][tid];
         if (tid == 0 && kk > 0) {
             sm.icc[kk][0] = best == 0 ? tx[0] : (best == 1 ? tx[1] : tx[2]);
             sm.icc[kk][1] = best == 0 ? ty[0] : (best == 1 ? ty[1] : ty[2]);
