@@ -62,7 +62,7 @@ constexpr int kCellMinCubes = LLFE_KM_CELL_MIN;  // cube count from which the sw
                            // with the gain form)
 #endif
 #ifndef LLFE_KM_PP_SUPS_KK
-#define LLFE_KM_PP_SUPS_KK 0  // ... in the rounds with at most this many chosen centres (0: the first round)
+#define LLFE_KM_PP_SUPS_KK 0  // ... in the rounds with at most this many chosen centres (0: none -- the first round takes no sweep)
 #endif
 #ifndef LLFE_KM_PP_ZSKIP
 #define LLFE_KM_PP_ZSKIP 1  // a partition change whose three gain accumulators are all zero skips its wave
@@ -228,7 +228,6 @@ struct KmSmem {
     unsigned long long fail_pts;  // keys read point by point in this Lloyd sweep
     // cube-based k-means++ (pp_cubes)
     unsigned long long psum[3][kParts];  // per trial and red-quarter partition: the trial's gain sum(D) - T_j
-                                         // (the first round: sum of d(., c0))
     unsigned long long pD[kParts];       // per partition: sum of D (the winning trial)
     unsigned long long pex[3];
     unsigned long long S[3];
@@ -481,7 +480,7 @@ __device__ __forceinline__
 void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, int K, uint64_t &rng,
                          const CubeEnt *__restrict__ ctab, int C, const CellEnt *__restrict__ ltab, int L,
                          const SupEnt *__restrict__ stab, int S, const uint32_t *__restrict__ part_uq, const uint32_t *__restrict__ hist,
-                         unsigned long long &bytes, uint32_t &pp_pts, uint32_t &pp_sel, uint64_t &t_sel) {
+                         const uint64_t *__restrict__ mom, unsigned long long &bytes, uint32_t &pp_pts, uint32_t &pp_sel, uint64_t &t_sel) {
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const uint32_t c0 = cvrng_next(rng) % (uint32_t)N;  // (every thread advances its rng copy)
     if (wid == 0) {
@@ -496,12 +495,34 @@ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, int K, uint64
     if (tid == 0) {
         sm.fail_pts = 0;
         sm.sel_pts = 0;
-        sm.qtot = 0;
     }
     if (tid >= 64 && tid < 64 + (kMaxK - 1) * 3) (&sm.icc[1][0])[tid - 64] = 0;
-    unsigned long long sum0 = 0, qacc = 0;  // qacc: sum |p|^2 over the lane's cubes
-    for (int kk = 0; kk < K; kk++) {
+    // ---- the first round in closed form.  With no chosen centre D = d(., c0), and per
+    // partition P sum_P |p - c0|^2 = Q_P - 2 c0 . S_P + n_P |c0|^2 from the partition's moments
+    // n_P, S_P = sum p, Q_P = sum |p|^2 (k_uq_gather; exact 64-bit integers, the same for all
+    // ten attempts of the image): one wave, no walk over the tables.  sum |p|^2 over the image
+    // (the closed-form compactness) is the sum of Q_P.
+    unsigned long long mq[kPartMoments];
+    if (wid == 1) {
+#pragma unroll
+        for (int q = 0; q < kPartMoments; q++) mq[q] = mom[q * kParts + lane];
+    }
+    __syncthreads();
+    if (wid == 1) {
+        const unsigned long long cx = (unsigned long long)sm.icc[0][0], cy = (unsigned long long)sm.icc[0][1],
+                                 cz = (unsigned long long)sm.icc[0][2];
+        const unsigned long long d = mq[4] + mq[0] * (cx * cx + cy * cy + cz * cz) - 2ull * (cx * mq[1] + cy * mq[2] + cz * mq[3]);
+        sm.pD[lane] = d;
+        const unsigned long long s = wave_sum(d), qt = wave_sum(mq[4]);
+        if (lane == 0) {
+            sm.S[0] = s;
+            sm.qtot = qt;
+        }
+    }
+    unsigned long long sum0 = 0;
+    for (int kk = 1; kk < K; kk++) {
         __syncthreads();
+        if (kk == 1) sum0 = sm.S[0];  // (the first round's total)
         ICent ch;  // chosen centres 0 .. kk-1 (uniform)
 #pragma unroll
         for (int m = 0; m < kMaxK; m++) {
@@ -510,14 +531,7 @@ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, int K, uint64
             ch.z[m] = __builtin_amdgcn_readfirstlane(sm.icc[m][2]);
         }
         int tx[3], ty[3], tz[3];
-        if (kk == 0) {
-#pragma unroll
-            for (int j = 0; j < 3; j++) {
-                tx[j] = ch.x[0];
-                ty[j] = ch.y[0];
-                tz[j] = ch.z[0];
-            }
-        } else {
+        {
             const uint64_t tsel0 = wall_clock64();
             double p[3];
 #pragma unroll
@@ -714,8 +728,7 @@ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, int K, uint64
             }
         }
         // ---- trial gains g_j = sum max(0, D - d(., t_j)) per partition, T_j = sum(D) - g_j
-        // (kk == 0: sum d(., c0))
-        // the round's sweep, instantiated per number of chosen centres (KK = kk <= kMaxK - 1):
+        // the round's sweep, instantiated per number of chosen centres (1 <= KK = kk <= kMaxK - 1):
         // the centre loops become straight-line code without per-centre guards
         auto sweep = [&](auto KKc) __attribute__((always_inline)) {
             constexpr int KK = decltype(KKc)::value;
@@ -844,8 +857,7 @@ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, int K, uint64
             };
             // Closed forms of a box (a cube, a cell of up to four cubes, a super-cell of up to
             // four cells) with origin o, count n, colour-offset sums S_u and S_u2: v_j = the
-            // gain of trial j on the box, sum over its colours of max(0, D - d(., t_j))
-            // (kk == 0: the sum of d(., t_0)), `fail` when some trial is not decided on the
+            // gain of trial j on the box, sum over its colours of max(0, D - d(., t_j)), `fail` when some trial is not decided on the
             // whole box.  ext: the box's offsets to its centre doubled, (3, 3, 3) for a cube,
             // (3, 7, 7) for a cell, (3, 15, 15) for a super-cell; MK / NAx / NBx: its corner
             // margins.
@@ -853,18 +865,6 @@ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, int K, uint64
                                 const int *NAx, const int *NBx, int ex, int ey, int ez, uint32_t &v0, uint32_t &v1,
                                 uint32_t &v2, bool &fail) __attribute__((always_inline)) {
                 fail = false;
-                if (KK == 0) {
-                    auto bsum = [&](int cx, int cy, int cz) {
-                        const int ax = ox - cx, ay = oy - cy, az = oz - cz;
-                        const uint32_t q = (uint32_t)(__mul24(ax, ax) + __mul24(ay, ay) + __mul24(az, az));
-                        return __umul24((uint32_t)n, q) + 2u * (uint32_t)(__mul24(ax, sx) + __mul24(ay, sy) + __mul24(az, sz)) +
-                               (uint32_t)s2;
-                    };
-                    v0 = bsum(tx[0], ty[0], tz[0]);
-                    qacc += bsum(0, 0, 0);
-                    v1 = v2 = 0;
-                    return;
-                }
                 // owner candidate: nearest chosen centre to the box centre q = o + ext / 2:
                 // argmin_m |q - c_m|^2 = argmin_m (D_m(o) - ext . c_m), first minimum.
                 // Dot products of (R, B) pairs by v_dot2_u32_u16 plus the G term by a
@@ -1033,9 +1033,9 @@ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, int K, uint64
                         __builtin_amdgcn_wave_barrier();  // (the list is rewritten next)
                     }
                 };
-                // (round 6) the first round (KK = 0: the sums of d(., c0), every box decided) walks
-                // the super-cells; the later rounds only with LLFE_KM_PP_SUPS (measured slower, with the
-                // sums and again with the gains, which decide more super-cells: DESIGN.md §3)
+                // super-cells only with LLFE_KM_PP_SUPS, or in the rounds up to LLFE_KM_PP_SUPS_KK chosen
+                // centres (measured slower, with the sums and again with the gains, which decide more
+                // super-cells: DESIGN.md §3; the first round takes no sweep)
                 if (stab && (LLFE_KM_PP_SUPS || KK <= LLFE_KM_PP_SUPS_KK)) {
                     // super-cells first, the same closed forms with extents (3, 15, 15); the
                     // cells of the undecided ones (one partition at a time) are listed in the wave's
@@ -1204,7 +1204,6 @@ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, int K, uint64
             if (lane == 0 && fails) atomicAdd(&sm.fail_pts, fails);
         };
         switch (kk) {
-            case 0: sweep(std::integral_constant<int, 0>{}); break;
             case 1: sweep(std::integral_constant<int, 1>{}); break;
             case 2: sweep(std::integral_constant<int, 2>{}); break;
             case 3: sweep(std::integral_constant<int, 3>{}); break;
@@ -1214,31 +1213,27 @@ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, int K, uint64
         if (wid == 0) {
 #pragma unroll
             for (int j = 0; j < 3; j++) {
-                // rounds >= 1 hold the trials' gains: T_j = sum(D) - g_j (g_j <= sum(D))
+                // the trials' gains: T_j = sum(D) - g_j (g_j <= sum(D))
                 const unsigned long long s = wave_sum(sm.psum[j][lane]);
-                if (lane == 0) sm.S[j] = kk > 0 ? sum0 - s : s;
+                if (lane == 0) sm.S[j] = sum0 - s;
             }
         }
         __syncthreads();
         int best = 0;
-        if (kk > 0) {
-            double bs = 1.7976931348623157e308;
-            for (int j = 0; j < 3; j++)
-                if ((double)sm.S[j] < bs) {
-                    bs = (double)sm.S[j];
-                    best = j;
-                }
-        }
+        double bs = 1.7976931348623157e308;
+        for (int j = 0; j < 3; j++)
+            if ((double)sm.S[j] < bs) {
+                bs = (double)sm.S[j];
+                best = j;
+            }
         sum0 = sm.S[best];
-        if (tid < kParts) sm.pD[tid] = kk > 0 ? sm.pD[tid] - sm.psum[best][tid] : sm.psum[0][tid];
-        if (tid == 0 && kk > 0) {
+        if (tid < kParts) sm.pD[tid] -= sm.psum[best][tid];
+        if (tid == 0) {
             sm.icc[kk][0] = best == 0 ? tx[0] : (best == 1 ? tx[1] : tx[2]);
             sm.icc[kk][1] = best == 0 ? ty[0] : (best == 1 ? ty[1] : ty[2]);
             sm.icc[kk][2] = best == 0 ? tz[0] : (best == 1 ? tz[1] : tz[2]);
         }
     }
-    qacc = wave_sum(qacc);
-    if (lane == 0) atomicAdd(&sm.qtot, qacc);
     __syncthreads();
     if (tid < kMaxK * 3) {
         const int k = tid / 3, j = tid % 3;
@@ -1383,7 +1378,7 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
         pp_cubes(sm, pts, N, K, rng, ctab, C, cubes.cells + (size_t)img * cubes.cell_stride, cubes.n_cells[img],
                  cubes.sups ? cubes.sups + (size_t)img * cubes.sup_stride : nullptr, cubes.sups ? cubes.n_sups[img] : 0,
                  cubes.part_uq + (size_t)img * kParts, cubes.part_hist ? cubes.part_hist + (size_t)img * kParts : nullptr,
-                 bytes, pp_pts, pp_sel, t_sel);
+                 cubes.moments + (size_t)img * kPartMoments * kParts, bytes, pp_pts, pp_sel, t_sel);
     } else {
     int cur = 0;
     {
@@ -1630,7 +1625,30 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
     }
     __syncthreads();
 
+    // Pair thresholds T[k][j] of the sweeps' margin tests (below), from the centres in sm.c: lane
+    // q < kMaxK^2 writes pair (k, j) = (q / kMaxK, q % kMaxK) of the three tables.  Cube:
+    // 3 L1(c_j - c_k) + 1; 4 x 8 x 8 cell: 3 |dx| + 7 (|dy| + |dz|) + 1; 4 x 16 x 16 super-cell:
+    // 3 |dx| + 15 (|dy| + |dz|) + 1 (twice the half extents); -inf where the pair needs no test
+    // (j == k, or an unused centre).
+    auto thr_tables = [&](int q) {
+        const int k = q / kMaxK, j = q % kMaxK;
+        const float dx = fabsf(sm.c[j][0] - sm.c[k][0]), dy = fabsf(sm.c[j][1] - sm.c[k][1]),
+                    dz = fabsf(sm.c[j][2] - sm.c[k][2]);
+        const bool none = j == k || j >= K || k >= K;
+        sm.thrL[0][q] = none ? -__builtin_inff() : 3.f * (dx + dy + dz) + 1.f;
+        sm.thrL[1][q] = none ? -__builtin_inff() : 3.f * dx + 7.f * (dy + dz) + 1.f;
+        sm.thrL[2][q] = none ? -__builtin_inff() : 3.f * dx + 15.f * (dy + dz) + 1.f;
+    };
+    // An iteration is three barrier phases: the sweep; the partial sums of the accumulators; then
+    // wave 0 finishes the sums, forms the new centres and the next sweep's thresholds while every
+    // thread clears its accumulator slots.  The first sweep's tables and zeros are set up here.
     if (tid == 0) sm.next_chunk = 0;
+    if (use_cubes && tid < kMaxK * kMaxK) thr_tables(tid);
+#pragma unroll
+    for (int k = 0; k < kMaxK; k++) {
+        sm.accA[k][tid] = 0;
+        sm.accB[k][tid] = 0;
+    }
     __syncthreads();
     int iter = 1;
     const double eps2 = 0.2 * 0.2;
@@ -1639,12 +1657,7 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
     for (;;) {
         const uint64_t tsw0 = wall_clock64();
         const CentP c = pack_centres(load_centres(sm.c));
-#pragma unroll
-        for (int k = 0; k < kMaxK; k++) {
-            sm.accA[k][tid] = 0;
-            sm.accB[k][tid] = 0;
-        }
-        // (lane-private slots: no barrier needed between zeroing and accumulation)
+        // (the accumulator slots are lane-private and were cleared after the last partial sums)
         if (use_cubes) {
             // Margin test per 4x4x4 cube, q = its centre, k = argmin d(q, c_k):
             //   d_j(p) - d_k(p) is linear in p, so over the cube it is >= (d_j(q) - d_k(q))
@@ -1678,22 +1691,10 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
                     }
                 }
             }
-            // Pair thresholds T[k][j] in LDS, read per lane for the lane's owner k: a box
-            // passes when d_j(q) - d_k(q) > T[k][j] for every j (T[k][k] = -inf), five
-            // compares against the owner's row instead of the ten centre pairs' compares
-            // combined by the owner masks.  Cube: 3 L1(c_j - c_k) + 1; 4 x 8 x 8 cell:
-            // 3 |dx| + 7 (|dy| + |dz|) + 1; 4 x 16 x 16 super-cell: 3 |dx| + 15 (|dy| + |dz|) + 1
-            // (twice the half extents).
-            if (tid < 3 * kMaxK * kMaxK) {
-                const int kind = tid / (kMaxK * kMaxK), k = (tid / kMaxK) % kMaxK, j = tid % kMaxK;
-                const float dx = fabsf(sm.c[j][0] - sm.c[k][0]), dy = fabsf(sm.c[j][1] - sm.c[k][1]),
-                            dz = fabsf(sm.c[j][2] - sm.c[k][2]);
-                sm.thrL[kind][k * kMaxK + j] = (j == k || j >= K || k >= K) ? -__builtin_inff()
-                                               : kind == 0 ? 3.f * (dx + dy + dz) + 1.f
-                                               : kind == 1 ? 3.f * dx + 7.f * (dy + dz) + 1.f
-                                                           : 3.f * dx + 15.f * (dy + dz) + 1.f;
-            }
-            __syncthreads();
+            // Pair thresholds T[k][j] in LDS (thr_tables, written with the centres), read per lane
+            // for the lane's owner k: a box passes when d_j(q) - d_k(q) > T[k][j] for every j
+            // (T[k][k] = -inf), five compares against the owner's row instead of the ten centre
+            // pairs' compares combined by the owner masks.
             unsigned long long fails = 0;
             // boundary colours: each undecided cube's lanes (lane = mask bit) store their
             // colour into this wave's LDS ring at head + rank (a dummy slot per lane when
@@ -2049,19 +2050,78 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
             sm.red[part][v] = acc;
         }
         __syncthreads();
-        if (tid < 20) {
-            unsigned long long acc = 0;
-            for (int part = 0; part < 32; part++) acc += sm.red[part][tid];
-            const int k = tid >> 2, comp = tid & 3;
-            if (comp < 3) sm.sums[k][comp] = (long long)acc;
-            else sm.counts[k] = (int)acc;
-        } else if (tid < 20 + kMaxK * 3) {
-            const int q = tid - 20, k = q / 3, j = q % 3;
-            sm.cprev[k][j] = sm.c[k][j];
-        } else if (tid == 64) {
-            sm.n_moved = 0;
+#pragma unroll
+        for (int k = 0; k < kMaxK; k++) {  // (the next sweep's; nothing reads the slots after the partial sums)
+            sm.accA[k][tid] = 0;
+            sm.accB[k][tid] = 0;
         }
-        __syncthreads();
+        // Wave 0 ends the iteration: lane v = 4 k + comp < 20 finishes value v (cluster k's sums
+        // x, y, z and its count), and the 15 (cluster, component) lanes form their own new centre
+        // component, OpenCV's expressions in its order: (float)sum * (1.f / (float)count), the
+        // move against the previous centre in float, squared in double and summed over j = 0, 1, 2,
+        // the largest over the clusters.  With an empty cluster (rare) the update waits: the
+        // workgroup runs the empty-cluster path, then wave 0 the update from the adjusted sums
+        // (pass 1).
+        for (int pass = 0;; pass++) {
+            if (wid == 0) {
+                const int v = lane < 20 ? lane : 0, k = v >> 2, comp = v & 3;
+                unsigned long long val = 0;
+                bool go = true;
+                if (pass == 0) {
+                    if (lane < 20) {
+                        for (int part = 0; part < 32; part++) val += sm.red[part][v];
+                        if (comp < 3) {
+                            sm.sums[k][comp] = (long long)val;
+                            sm.cprev[k][comp] = sm.c[k][comp];
+                        } else {
+                            sm.counts[k] = (int)val;
+                        }
+                    }
+                    go = !__ballot(lane < 20 && comp == 3 && k < K && val == 0);
+                    if (lane == 0) {
+                        sm.n_moved = 0;
+                        sm.flag = go ? 0 : 2;  // 2: an empty cluster
+                    }
+                } else {
+                    val = comp < 3 ? (unsigned long long)sm.sums[k][comp] : (unsigned long long)sm.counts[k];
+                }
+                if (go) {  // (uniform)
+                    const int count = (int)__shfl(val, v | 3);
+                    const float scale = 1.f / (float)count;
+                    const float nv = (float)(long long)val * scale;
+                    const double t = (double)(nv - (comp < 3 ? sm.cprev[k][comp] : 0.f));
+                    const double t2 = t * t;
+                    double dist = 0.0;
+                    dist += __shfl(t2, 4 * k);
+                    dist += __shfl(t2, 4 * k + 1);
+                    dist += __shfl(t2, 4 * k + 2);
+                    if (lane < 20 && comp < 3 && k < K) sm.c[k][comp] = nv;
+                    double max_shift = 0.0;
+#pragma unroll
+                    for (int k1 = 0; k1 < kMaxK; k1++) {
+                        const double dk = __shfl(dist, 4 * k1);
+                        if (k1 < K) max_shift = fmax(max_shift, dk);
+                    }
+                    if (use_cubes) {  // the next sweep's thresholds from the new centres (this wave's own writes)
+                        __builtin_amdgcn_wave_barrier();
+                        if (lane < kMaxK * kMaxK) thr_tables(lane);
+                    }
+                    if (lane == 0) {
+                        sm.flag = (iter + 1 == 100 || max_shift <= eps2) ? 1 : 0;
+                        sm.next_chunk = 0;
+                        // (trace) iterations by their largest centre move, 8 u8 bins
+                        // [0,.25) [.25,.5) [.5,1) [1,2) [2,4) [4,8) [8,16) [16,inf): max_shift is the
+                        // move squared, compared with the squared edges
+                        const int bin = (max_shift >= 0.0625) + (max_shift >= 0.25) + (max_shift >= 1.0) +
+                                        (max_shift >= 4.0) + (max_shift >= 16.0) + (max_shift >= 64.0) +
+                                        (max_shift >= 256.0);
+                        const unsigned long long sh = 8ull * (unsigned)bin;
+                        if (((drift_hist >> sh) & 255ull) < 255ull) drift_hist += 1ull << sh;
+                    }
+                }
+            }
+            __syncthreads();
+            if (sm.flag != 2) break;
 
         // ---- empty clusters: move the farthest point of the biggest cluster (rare)
         for (int ek = 0; ek < K; ek++) {
@@ -2144,31 +2204,8 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
             }
             __syncthreads();
         }
-        if (tid == 0) {
-            double max_shift = 0.0;
-            for (int k = 0; k < K; k++) {
-                const float scale = 1.f / (float)sm.counts[k];
-                double dist = 0.0;
-                for (int j = 0; j < 3; j++) {
-                    float v = (float)sm.sums[k][j] * scale;
-                    sm.c[k][j] = v;
-                    double t = (double)(v - sm.cprev[k][j]);
-                    dist += t * t;
-                }
-                max_shift = fmax(max_shift, dist);
-            }
-            sm.flag = (iter + 1 == 100 || max_shift <= eps2) ? 1 : 0;
-            sm.next_chunk = 0;
-            // (trace) iterations by their largest centre move, 8 u8 bins
-            // [0,.25) [.25,.5) [.5,1) [1,2) [2,4) [4,8) [8,16) [16,inf)
-            const double mv = sqrt(max_shift);
-            int bin = 0;
-            for (double t = 0.25; bin < 7 && mv >= t; t *= 2.0) bin++;
-            const unsigned long long sh = 8ull * (unsigned)bin;
-            if (((drift_hist >> sh) & 255ull) < 255ull) drift_hist += 1ull << sh;
-        }
+        }  // (pass)
         iter++;
-        __syncthreads();
         if (sm.flag) break;
     }
 

@@ -210,7 +210,7 @@ struct Work {
     DevBuf<uint8_t> d_in, d_cls, d_sroot, d_tflag;  // d_tflag: the stencil's hysteresis tile flags
     bool tflag_valid = false;  // d_tflag belongs to the class map in d_cls (stencil_params)
     DevBuf<int8_t> d_noise, d_nfield;  // d_nfield: the launch's noise field (unique.hip)
-    DevBuf<uint64_t> d_bits, d_ebits;
+    DevBuf<uint64_t> d_bits, d_ebits, d_pmom;  // d_pmom: the partitions' moments (KmeansCubes::moments)
     DevBuf<unsigned long long> d_shadow;
     DevBuf<int> d_order, d_parent, d_nroots, d_ftlist, d_ptlist;
     DevBuf<uint16_t> d_lab, d_roots;
@@ -674,6 +674,7 @@ int color_stage(llfe_ctx *ctx, Work &W, const uint8_t *img, const uint64_t *img_
     HIPCHK(ctx, W.d_pmeta.ensure((size_t)n * kParts * 5));
     HIPCHK(ctx, W.d_nuniq.ensure(n));
     HIPCHK(ctx, W.d_ncubes.ensure(n));
+    HIPCHK(ctx, W.d_pmom.ensure((size_t)n * kPartMoments * kParts));
     // (d_pmeta: hist, cl, uq, cc, cs; k-means reads uq)
     uint32_t *hist = W.d_pmeta.p, *cl = hist + (size_t)n * kParts, *uq = hist + (size_t)2 * n * kParts,
              *cc = uq + (size_t)n * kParts, *cs = cc + (size_t)n * kParts;
@@ -699,7 +700,8 @@ int color_stage(llfe_ctx *ctx, Work &W, const uint8_t *img, const uint64_t *img_
     TIMED(ctx, s, "k_uq_gather", 0,
           launch_uq_gather(W.d_raw.p, n, key_stride, hist, uq, cc, cl, cs, W.d_segcubes.p, W.d_segcells.p,
                            W.d_keys.p, W.d_cubes.p, W.d_cells.p, W.d_sups.p, cube_stride, cell_stride,
-                           cell_stride, W.d_nuniq.p, W.d_ncubes.p, W.d_ncells.p, W.d_nsups.p, contiguous_keys, s));
+                           cell_stride, W.d_nuniq.p, W.d_ncubes.p, W.d_ncells.p, W.d_nsups.p, W.d_pmom.p,
+                           contiguous_keys, s));
     return LLFE_OK;
 }
 
@@ -913,7 +915,8 @@ int enqueue_chunk(llfe_ctx *ctx, const llfe_batch *b, uint32_t features, uint64_
                                 W.d_pmeta.p + (size_t)2 * n * kParts, W.d_cells.p, W.d_ncells.p,
                                 std::min<int64_t>(std::min<int64_t>(key_stride, kMaxCubes), (int64_t)kParts * kCellsPerPart),
                                 seg ? W.d_pmeta.p : nullptr, W.d_sups.p, W.d_nsups.p,
-                                std::min<int64_t>(std::min<int64_t>(key_stride, kMaxCubes), (int64_t)kParts * kCellsPerPart)};
+                                std::min<int64_t>(std::min<int64_t>(key_stride, kMaxCubes), (int64_t)kParts * kCellsPerPart),
+                                W.d_pmom.p};
         rc = kmeans_stage(ctx, W, seg ? W.d_raw.p : W.d_keys.p, key_stride, W.d_nuniq.p, n, n_colors, seed, index,
                           cubes, col_s);
         if (rc) return rc;
@@ -1795,7 +1798,7 @@ int llfe_kmeans(llfe_ctx *ctx, const uint32_t *keys, int64_t key_stride, const i
     Work &W = ctx->ws[0];
     HIPCHK(ctx, W.d_nuniq.ensure(n));
     HIPCHK(ctx, hipMemcpyAsync(W.d_nuniq.p, n_points, sizeof(int64_t) * n, hipMemcpyHostToDevice, s));
-    const KmeansCubes none{nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0};  // plain sweeps over caller-supplied keys
+    const KmeansCubes none{nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr};  // plain sweeps over caller-supplied keys
     int rc = kmeans_stage(ctx, W, keys, key_stride, W.d_nuniq.p, n, n_colors, seed, ImgIndex{index_base, nullptr}, none, s);
     if (rc) return rc;
     HIPCHK(ctx, ctx->h_kout.ensure(n));

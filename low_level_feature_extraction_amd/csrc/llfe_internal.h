@@ -153,6 +153,7 @@ constexpr int kMaxColors = LLFE_MAX_COLORS;  // the generic k-means (k_kmeans_bi
 constexpr int kAttempts = 10;
 constexpr int kParts = 64;         // key partitions by red quarter r >> 2
 constexpr int kCubesPerPart = 4096;  // 64 x 64 cubes of 4x4x4 per partition
+constexpr int kPartMoments = 5;      // per partition: n, sum r, sum g, sum b, sum |p|^2 (KmeansCubes::moments)
 
 struct KmeansAttemptOut {
     double compactness;
@@ -240,6 +241,10 @@ struct KmeansCubes {
     const SupEnt *sups;       // per image (sup_stride) super-cells in partition order (nullptr: none)
     const int32_t *n_sups;
     int64_t sup_stride;
+    // per image: the partitions' moments over their colours p, [kPartMoments][kParts] exact 64-bit
+    // sums (k_uq_gather): count, sum r, sum g, sum b, sum |p|^2.  k-means++ takes its first round
+    // (sum of d(., c0) per partition) and sum |p|^2 from them.
+    const uint64_t *moments;
 };
 // Unique colours (unique.hip), all per image with stride key_stride (u32 keys):
 //   keys:    pixels -> noised keys into `raw`, partition histogram `hist` (n x 64, zeroed)
@@ -249,7 +254,7 @@ struct KmeansCubes {
 //            counts -> uq, cc, cl (n x 64)
 //   gather:  contiguous sorted keys -> `keys` (may alias part), cube table -> `cubes`,
 //            cell table -> `cells` (first cube indices made image-global), n_unique, n_cubes,
-//            n_cells
+//            n_cells, the partitions' moments -> `moments` (n x kPartMoments x 64)
 // noise: the caller's parity noise (n x P x 3 int8) or null -> the launch's noise field
 // (noise_field_pixels(P) bytes at `field`, written by launch_uq_noise; unique.hip)
 int64_t noise_field_pixels(int64_t P);
@@ -269,8 +274,8 @@ hipError_t launch_uq_gather(const uint32_t *skeys, int n, int64_t key_stride, co
                             const uint32_t *cc, const uint32_t *cl, const uint32_t *cs, const CubeEnt *seg_cubes,
                             const CellEnt *seg_cells, uint32_t *keys, CubeEnt *cubes,
                             CellEnt *cells, SupEnt *sups, int64_t cube_stride, int64_t cell_stride, int64_t sup_stride,
-                            int64_t *n_unique, int32_t *n_cubes, int32_t *n_cells, int32_t *n_sups, bool copy_keys,
-                            hipStream_t s);
+                            int64_t *n_unique, int32_t *n_cubes, int32_t *n_cells, int32_t *n_sups,
+                            uint64_t *moments, bool copy_keys, hipStream_t s);
 
 // per image: K = min(n_colors, U); attempts run as separate workgroups
 // (ordered largest U first), then a finalize kernel picks the best attempt.

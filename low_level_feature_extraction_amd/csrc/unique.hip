@@ -16,7 +16,7 @@
 //                 (at the partition's place in key order) and its 4x4x4 cubes (occupancy
 //                 mask + exact sums, CubeEnt)
 //   k_uq_gather   per image: prefix over the partitions, contiguous sorted keys + cube
-//                 table
+//                 table, and each partition's moments (count, colour sums, sum |p|^2)
 #include <algorithm>
 
 #include "llfe_internal.h"
@@ -641,7 +641,8 @@ __global__ __launch_bounds__(GT) void k_uq_gather(const uint32_t *__restrict__ s
                                                   long long cube_stride, long long cell_stride, long long sup_stride,
                                                   long long *__restrict__ n_unique,
                                                   int *__restrict__ n_cubes, int *__restrict__ n_cells,
-                                                  int *__restrict__ n_sups, int copy_keys) {
+                                                  int *__restrict__ n_sups,
+                                                  unsigned long long *__restrict__ moments, int copy_keys) {
     __shared__ uint32_t sp, su, sc, sl, ss, nu, nc, nl, ns;
     const int R = blockIdx.x, img = blockIdx.y, t = threadIdx.x;
     if (t < 64) {
@@ -680,10 +681,32 @@ __global__ __launch_bounds__(GT) void k_uq_gather(const uint32_t *__restrict__ s
     for (uint32_t i = t; i < C; i += GT) oc[i] = scp[i];
     const CellEnt *slp = seg_cells + ((size_t)img * NPART + R) * kCellsPerPart;
     CellEnt *ol = cells + (size_t)img * cell_stride + sl;
+    // ... and the partition's moments over its colours p (exact, 64-bit): n, sum r, sum g, sum b,
+    // sum |p|^2, from the cells: with cell origin o and u = p - o, sum p = n o + sum u and
+    // sum |p|^2 = n |o|^2 + 2 o . sum u + sum |u|^2.  k-means++ forms its first round from them.
+    // A partition has <= 2^18 colours, so n and the three colour sums (<= 255 x 2^18) fit 32 bits
+    // and are reduced two to a 64-bit word: n | sum r << 32, sum g | sum b << 32, sum |p|^2.
+    static_assert(kPartMoments == 5, "n, sum r, sum g, sum b, sum |p|^2");
+    unsigned long long mom[3] = {0ull, 0ull, 0ull};
     for (uint32_t i = t; i < L; i += GT) {
         CellEnt e = slp[i];
+        const uint32_t ox = ((e.id >> 10) & 63u) * 4u, oy = ((e.id >> 5) & 31u) * 8u, oz = (e.id & 31u) * 8u;
+        const uint32_t ln = (e.id >> 18) & 511u, lr = e.sums & 1023u, lg = (e.sums >> 10) & 2047u, lb = e.sums >> 21;
+        mom[0] += (unsigned long long)ln | ((unsigned long long)(ln * ox + lr) << 32);  // (<= 256 x 255 a cell)
+        mom[1] += (unsigned long long)(ln * oy + lg) | ((unsigned long long)(ln * oz + lb) << 32);
+        mom[2] += ln * (ox * ox + oy * oy + oz * oz) + 2u * (ox * lr + oy * lg + oz * lb) + e.s2;  // <= 256 x 195 075
         e.first += cbase;
         ol[i] = e;
+    }
+    __shared__ unsigned long long wmom[GT / 64][3];
+    if (L) {  // (uniform; most partitions of a flat "ui" image are empty)
+#pragma unroll
+        for (int q = 0; q < 3; q++) {
+            unsigned long long v = mom[q];
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+            if ((t & 63) == 0) wmom[t >> 6][q] = v;
+        }
     }
     // the partition's super-cells (round 6), thread t = super-cell (G4, B4) = (t >> 4, t & 15):
     // its cells (2 G4 + j, 2 B4 + c) from a map of the partition's cells by (G2, B2), its count
@@ -694,6 +717,15 @@ __global__ __launch_bounds__(GT) void k_uq_gather(const uint32_t *__restrict__ s
     __shared__ uint32_t wsum[GT / 64];
     for (int i = t; i < kCellsPerPart; i += GT) cmap[i] = -1;
     __syncthreads();
+    if (t < kPartMoments) {  // (an empty partition: zeros)
+        unsigned long long v = 0;
+        if (L) {
+#pragma unroll
+            for (int w = 0; w < GT / 64; w++) v += wmom[w][t < 4 ? t >> 1 : 2];
+            if (t < 4) v = (t & 1) ? v >> 32 : v & 0xFFFFFFFFull;
+        }
+        moments[((size_t)img * kPartMoments + t) * NPART + R] = v;
+    }
     for (uint32_t i = t; i < L; i += GT) cmap[slp[i].id & (kCellsPerPart - 1)] = (short)i;
     __syncthreads();
     const int G4 = t >> 4, B4 = t & 15;
@@ -783,12 +815,12 @@ hipError_t launch_uq_gather(const uint32_t *skeys, int n, int64_t key_stride, co
                             const uint32_t *cc, const uint32_t *cl, const uint32_t *cs, const CubeEnt *seg_cubes,
                             const CellEnt *seg_cells, uint32_t *keys, CubeEnt *cubes,
                             CellEnt *cells, SupEnt *sups, int64_t cube_stride, int64_t cell_stride, int64_t sup_stride,
-                            int64_t *n_unique, int32_t *n_cubes, int32_t *n_cells, int32_t *n_sups, bool copy_keys,
-                            hipStream_t s) {
+                            int64_t *n_unique, int32_t *n_cubes, int32_t *n_cells, int32_t *n_sups,
+                            uint64_t *moments, bool copy_keys, hipStream_t s) {
     hipLaunchKernelGGL(k_uq_gather, dim3(NPART, n), dim3(GT), 0, s, skeys, (long long)key_stride, hist, uq, cc, cl, cs,
                        seg_cubes, seg_cells, keys, cubes, cells, sups, (long long)cube_stride,
                        (long long)cell_stride, (long long)sup_stride, (long long *)n_unique, (int *)n_cubes,
-                       (int *)n_cells, (int *)n_sups, copy_keys ? 1 : 0);
+                       (int *)n_cells, (int *)n_sups, (unsigned long long *)moments, copy_keys ? 1 : 0);
     return hipGetLastError();
 }
 
