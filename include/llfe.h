@@ -252,7 +252,7 @@ int llfe_batch_capacity(int32_t h, int32_t w);
 /* ---- stage entry points (parity tests; device in/out unless noted) ------
  * The ones that use the context's workspace (llfe_shape_mask, llfe_canny,
  * llfe_shadow_stats, llfe_color_unique, llfe_kmeans, llfe_find_contours_gpu,
- * llfe_shapes_from_masks_gpu) and llfe_process_images return LLFE_ERR_INVALID while a
+ * llfe_shapes_from_masks_gpu, llfe_font_detect) and llfe_process_images return LLFE_ERR_INVALID while a
  * batch submitted with llfe_submit_batch is not yet collected. */
 /* gray = cvtColor(BGR2GRAY); out = GaussianBlur(gray, (5,5), 0)
  * (shape pyc @L18-21, shadow pyc @L8-9) */
@@ -276,6 +276,30 @@ int llfe_edge_classes(llfe_ctx *ctx, const uint8_t *bgr, uint8_t *classes, int32
  * 0/255 u8; bgr and mask are device pointers (n x h x w x 3 / n x h x w). */
 int llfe_font_binary(llfe_ctx *ctx, const uint8_t *bgr, uint8_t *mask, int32_t n, int32_t h, int32_t w,
                      llfe_stream stream);
+/* FontDetector.detect_font on the device (app/services/analyze/font_detector.py:39-67
+ * detect_text_regions, :109-155 detect_font): per image the external contours of the
+ * binary in cv2's list order, the text regions among their bounding rectangles
+ * (0.1 < w / float(h) < 15 and h > 8), the largest one (max by w * h, the first in list
+ * order on ties) and the exact sum of cvtColor(BGR2GRAY) over its rectangle, from which
+ * the caller makes np.mean as (double)gray_sum / (width * height).
+ * bgr (n x h x w x 3) and binary (n x h x w, nonzero = foreground) are device pointers;
+ * binary may be NULL: it is then llfe_font_binary(bgr); with a binary, bgr may be NULL
+ * (regions only: every gray_sum is 0).  results (n records) and regions
+ * (4 x int32 x, y, w, h per region, the images' lists one after another; may be NULL when
+ * only the records are wanted) are host pointers.  *regions_needed (may be NULL) receives
+ * the total number of regions; when regions is given and region_capacity is short the
+ * call returns LLFE_ERR_CAPACITY with results still valid.  LLFE_ERR_UNSUPPORTED: width
+ * above 4096, height above 65535, or a mask the border follower gives up on. */
+typedef struct {
+    int32_t n_contours;      /* external contours of the binary */
+    int32_t n_regions;       /* those passing the aspect / height filter */
+    int32_t x, y, width, height; /* largest region (first in cv2 order on equal w*h); zeros when n_regions == 0 */
+    int64_t region_offset;   /* this image's regions are regions[4*region_offset ...], n_regions of them, cv2 order */
+    uint64_t gray_sum;       /* sum of BGR2GRAY over the largest region's rectangle; 0 when none */
+} llfe_font_result;          /* 40 bytes */
+int llfe_font_detect(llfe_ctx *ctx, const uint8_t *bgr, const uint8_t *binary, int32_t n, int32_t h, int32_t w,
+                     llfe_font_result *results, int32_t *regions, int64_t region_capacity,
+                     int64_t *regions_needed, llfe_stream stream);
 /* TextExtractor.preprocess_image (app/services/analyze/text_extractor.py:15-46): gray
  * (cvtColor BGR2GRAY for 3 / 4 channels, the image itself for 1), INTER_CUBIC upscale by
  * max(2, 300 / w, 100 / h) when h < 30 or w < 100, Otsu THRESH_BINARY, bitwise_not when

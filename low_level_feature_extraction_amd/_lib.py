@@ -117,6 +117,19 @@ class LlfeKmeansAttempt(C.Structure):
     ]
 
 
+class LlfeFontResult(C.Structure):
+    _fields_ = [
+        ("n_contours", C.c_int32),
+        ("n_regions", C.c_int32),
+        ("x", C.c_int32),
+        ("y", C.c_int32),
+        ("width", C.c_int32),
+        ("height", C.c_int32),
+        ("region_offset", C.c_int64),
+        ("gray_sum", C.c_uint64),
+    ]
+
+
 # every symbol declared in include/llfe.h, with its ctypes signature
 _vp, _i32, _i64, _u32, _u64 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_uint64
 SIGNATURES = {
@@ -147,6 +160,7 @@ SIGNATURES = {
     "llfe_canny": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "llfe_dilate3": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "llfe_font_binary": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "llfe_font_detect": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _i64, C.POINTER(C.c_int64), _vp]),
     "llfe_text_binary": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, C.POINTER(_i32), _vp]),
     "llfe_text_size": (C.c_int, [_i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),
     "llfe_shadow_stats": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),

@@ -482,6 +482,55 @@ class Backend:
         self._call("llfe_font_binary", x.data_ptr(), out.data_ptr(), n, h, w, self._stream(x))
         return out
 
+    def font_detect(self, images, binary=None, regions=False) -> list:
+        """FontDetector.detect_font's pixel work on the GPU (llfe_font_detect): per image
+        the external contours of the font binary (or of ``binary``, n x h x w, nonzero =
+        foreground), the text regions among their bounding boxes, the largest one and the
+        exact gray sum over it.  ``images``: N x H x W x 3 BGR, numpy or device tensor (None
+        with a ``binary``: no gray sums).  -> list of dicts n_contours, n_regions, x, y,
+        width, height, gray_sum and, with ``regions=True``, regions: [(x, y, w, h)] in
+        findContours order.  No mask or image comes back to the host."""
+        torch = _torch()
+        if images is None and binary is None:
+            raise ValueError("font_detect needs images or a binary")
+        x = self._dev_batch(images) if images is not None else None
+        b = None
+        if binary is not None:
+            b = binary if _is_torch(binary) else torch.from_numpy(np.ascontiguousarray(binary, np.uint8))
+            if b.dtype != torch.uint8:
+                raise ValueError(f"expected a uint8 binary, got {b.dtype}")
+            if b.dim() == 2:
+                b = b[None]
+            b = b.to(f"cuda:{self.device}").contiguous()
+            if b.dim() != 3 or (x is not None and tuple(b.shape) != tuple(x.shape[:3])):
+                raise ValueError(f"binary {tuple(b.shape)} does not match the images")
+        n, h, w = (x if x is not None else b).shape[:3]
+        res = (L.LlfeFontResult * max(n, 1))()
+        need = C.c_int64(0)
+        cap = max(4096, 256 * n) if regions else 0
+        while True:
+            reg = np.empty((cap, 4), np.int32) if regions else None
+            with self._lock:
+                rc = self._lib.llfe_font_detect(self.ctx, x.data_ptr() if x is not None else None,
+                                                b.data_ptr() if b is not None else None, n, h, w, res,
+                                                reg.ctypes.data if regions else None, cap, C.byref(need),
+                                                self._stream(x if x is not None else b))
+            if rc == L.LLFE_ERR_CAPACITY and regions and need.value > cap:  # grown once: need is exact
+                cap = int(need.value)
+                continue
+            self._chk(rc)
+            break
+        out = []
+        for i in range(n):
+            r = res[i]
+            d = {"n_contours": int(r.n_contours), "n_regions": int(r.n_regions), "x": int(r.x), "y": int(r.y),
+                 "width": int(r.width), "height": int(r.height), "gray_sum": int(r.gray_sum)}
+            if regions:
+                o = int(r.region_offset)
+                d["regions"] = [tuple(v) for v in reg[o:o + d["n_regions"]].tolist()]
+            out.append(d)
+        return out
+
     def text_binary(self, image):
         """TextExtractor.preprocess_image on the GPU (text_extractor.py:15-46): one
         H x W [x C] uint8 image (C = 1, 3 BGR or 4 BGRA) -> (out_h x out_w 0/255 device

@@ -26,6 +26,10 @@
 //   k_ct_bases / k_ct_shapes   reversed start order, area >= 100 filter, one wave per
 //                  kept contour: perimeter, Douglas-Peucker counts, hull area
 //
+// The boxes-only mode (launch_contours(..., boxes_only), the font path of font.hip) keeps
+// the contour set, order, areas and bounding boxes but stores no vertices and ends after
+// k_ct_scan: its memory grows with the number of components, not with border length.
+//
 // Every floating-point quantity is exact or computed in OpenCV's order: areas are
 // integer shoelace sums, segment lengths are float sqrt of integers (double sqrt then
 // float rounding is the correctly rounded float sqrt for integers < 2^26), their sum in
@@ -328,6 +332,7 @@ struct TraceCount {
     __device__ void mark(int, int, bool) {}
 };
 
+template <bool PTS>  // PTS = false: marks, area and box only (boxes-only mode)
 struct TraceWrite {
     int2 *pts;          // vertex destination (capacity cap)
     uint64_t *mv, *mn;  // mark planes of the image (row stride wpr), null: no marks
@@ -341,7 +346,7 @@ struct TraceWrite {
     int my = -1, mq = -1;  // marks of one 64-pixel word are OR-ed once per visit of the word
     unsigned long long bv = 0, bn = 0;
     __device__ void vertex(int x, int y) {
-        if (on && nv < cap) pts[nv] = make_int2(x, y);
+        if (PTS && on && nv < cap) pts[nv] = make_int2(x, y);
         if (nv == 0) {
             fx = x;
             fy = y;
@@ -486,7 +491,9 @@ __device__ bool trace_outer(NB &nbh, const Geo &g, int x0, int y0, F &f) {
 // one wave per component, one pass: vertices go to the block's staging area (exact
 // length known afterwards -> allocate -> copy), marks to the planes; a border longer
 // than the staging area is followed a second time straight into its allocation
+// (BOXES: no vertices, hence no staging and no second pass)
 constexpr uint32_t kStage = kCtStage;
+template <bool BOXES>
 __global__ __launch_bounds__(64) void k_ct_trace(const uint64_t *__restrict__ bits, Geo g, CtComp *__restrict__ comps,
                                                   int64_t comp_cap, int2 *__restrict__ pts, int64_t pts_cap,
                                                   int2 *__restrict__ stage, uint64_t *__restrict__ mv,
@@ -495,7 +502,7 @@ __global__ __launch_bounds__(64) void k_ct_trace(const uint64_t *__restrict__ bi
     __shared__ unsigned long long s_off;
     const int lane = threadIdx.x;
     const int64_t ncomp = min((int64_t)ctr->comps, comp_cap);
-    int2 *st = stage + (size_t)blockIdx.x * kStage;
+    int2 *st = BOXES ? nullptr : stage + (size_t)blockIdx.x * kStage;
     for (int64_t slot = blockIdx.x; slot < ncomp; slot += gridDim.x) {
         CtComp c = comps[slot];
         c.key = (uint32_t)__builtin_amdgcn_readfirstlane((int)c.key);
@@ -503,9 +510,24 @@ __global__ __launch_bounds__(64) void k_ct_trace(const uint64_t *__restrict__ bi
         const int y = c.key / g.W, x = c.key - y * g.W;
         const size_t pb = (size_t)c.img * g.H * g.wpr;
         NbWindow nbh{bits, g, c.img, lane, win};
-        TraceWrite f{st, mv + pb, mn + pb, g.wpr, lane == 0, kStage};
+        TraceWrite<!BOXES> f{st, mv + pb, mn + pb, g.wpr, lane == 0, kStage};
         const bool ok = trace_outer(nbh, g, x, y, f);
         f.close();
+        if (BOXES) {
+            if (lane == 0) {
+                if (!ok) atomicOr(&ctr->flags, kCtBadTrace);
+                c.nv = 0;
+                c.off = 0;
+                c.area2 = f.a2;
+                c.x0 = (uint16_t)f.x0;
+                c.y0 = (uint16_t)f.y0;
+                c.x1 = (uint16_t)f.x1;
+                c.y1 = (uint16_t)f.y1;
+                comps[slot] = c;
+            }
+            __syncthreads();
+            continue;
+        }
         if (lane == 0) {
             if (!ok) atomicOr(&ctr->flags, kCtBadTrace);
             s_off = atomicAdd(&ctr->pts, (unsigned long long)f.nv);
@@ -523,7 +545,7 @@ __global__ __launch_bounds__(64) void k_ct_trace(const uint64_t *__restrict__ bi
                 }
             } else {
                 NbWindow nb2{bits, g, c.img, lane, win};
-                TraceWrite f2{pts + off, nullptr, nullptr, g.wpr, lane == 0, f.nv};
+                TraceWrite<true> f2{pts + off, nullptr, nullptr, g.wpr, lane == 0, f.nv};
                 trace_outer(nb2, g, x, y, f2);
             }
         }
@@ -564,6 +586,7 @@ __device__ bool pix_is_right_mark(const ScanPlanes &sp, const Geo &g, const uint
     return __hip_atomic_load(acc + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != kRejected;
 }
 
+template <bool PTS>
 struct QuirkWrite {  // a border followed from a non-first pixel: marks go to the Q planes
     int2 *pts;
     uint64_t *qv, *qn;
@@ -573,7 +596,7 @@ struct QuirkWrite {  // a border followed from a non-first pixel: marks go to th
     int64_t a2 = 0;
     int x0 = 1 << 30, y0 = 1 << 30, x1 = -1, y1 = -1;
     __device__ void vertex(int x, int y) {
-        pts[nv] = make_int2(x, y);
+        if (PTS) pts[nv] = make_int2(x, y);
         if (nv == 0) {
             fx = x;
             fy = y;
@@ -625,6 +648,9 @@ __device__ __forceinline__ int wave_excl_sum(int v, int lane) {
 
 // one 64-lane workgroup per image: replays OpenCV's RETR_EXTERNAL raster scan
 // (contours.cpp scan_external) and writes the image's contours in start order
+// (BOXES: the borders it follows itself leave marks, area and box but no vertices, and
+// the shape indices of the refs stay -1)
+template <bool BOXES>
 __global__ __launch_bounds__(64) void k_ct_scan(const uint64_t *__restrict__ bits, Geo g,
                                                  const uint16_t *__restrict__ lab, const int *__restrict__ P,
                                                  uint64_t *__restrict__ planes, size_t plane_stride,
@@ -813,22 +839,22 @@ __global__ __launch_bounds__(64) void k_ct_scan(const uint64_t *__restrict__ bit
                         // a border started away from a component's first pixel
                         TraceCount fc;
                         NbGlobal nbg{bits, g, img};
-                        bool ok = trace_outer(nbg, g, bpos, y, fc);
+                        const bool ok = BOXES ? true : trace_outer(nbg, g, bpos, y, fc);
                         const unsigned slot = atomicAdd(&ctr->comps, 1u);
-                        const unsigned long long off = atomicAdd(&ctr->pts, (unsigned long long)fc.nv);
+                        const unsigned long long off = BOXES ? 0ull : atomicAdd(&ctr->pts, (unsigned long long)fc.nv);
                         if (!ok) atomicOr(&ctr->flags, kCtBadTrace);
                         if (slot >= comp_cap || off + fc.nv > (unsigned long long)pts_cap || nref >= cap_img) {
                             atomicOr(&ctr->flags, slot >= comp_cap ? kCtOverflowComps
                                                                    : (nref >= cap_img ? kCtOverflowRefs : kCtOverflowPts));
                             s_bcast[1] = -1;
                         } else {
-                            QuirkWrite fw{pts + off, sp.qv, sp.qn, g.wpr};
-                            trace_outer(nbg, g, bpos, y, fw);
+                            QuirkWrite<!BOXES> fw{pts + off, sp.qv, sp.qn, g.wpr};
+                            if (!trace_outer(nbg, g, bpos, y, fw)) atomicOr(&ctr->flags, kCtBadTrace);
                             fw.close();
                             CtComp c;
                             c.key = y * g.W + bpos;
                             c.img = img;
-                            c.nv = fw.nv;
+                            c.nv = BOXES ? 0u : fw.nv;
                             c.off = (uint32_t)off;
                             c.area2 = fw.a2;
                             c.x0 = (uint16_t)fw.x0;
@@ -860,7 +886,7 @@ __global__ __launch_bounds__(64) void k_ct_scan(const uint64_t *__restrict__ bit
     __threadfence();
     __syncthreads();
     int kept = 0;
-    for (int c0 = 0; c0 < nref; c0 += 64) {
+    for (int c0 = 0; !BOXES && c0 < nref; c0 += 64) {
         const int idx = nref - 1 - (c0 + lane);
         bool keep = false;
         int2 r = make_int2(0, -1);
@@ -1247,7 +1273,8 @@ CtCaps contours_default_caps(int n, int h, int w) {
 
 size_t contours_plane_words(int n, int h, int w) { return (size_t)n * h * words_per_row(w); }
 
-hipError_t launch_contours(const uint64_t *bits, int n, int h, int w, const CtWork &wk, hipStream_t s) {
+hipError_t launch_contours(const uint64_t *bits, int n, int h, int w, const CtWork &wk, hipStream_t s,
+                           bool boxes_only) {
     if (n <= 0) return hipSuccess;
     Geo g{h, w, words_per_row(w), tiles_x(w), tiles_x(w) * tiles_y(h), n};
     const size_t pw = contours_plane_words(n, h, w);
@@ -1262,9 +1289,17 @@ hipError_t launch_contours(const uint64_t *bits, int n, int h, int w, const CtWo
     hipLaunchKernelGGL(k_ct_collect, grid, dim3(NT), 0, s, g, wk.roots, wk.nroots, wk.parent, wk.comps, wk.acc,
                        wk.planes + 4 * pw, wk.ctr, wk.img_info, wk.caps.comps);
     hipLaunchKernelGGL(k_ct_finalize, grid, dim3(NT), 0, s, g, wk.roots, wk.nroots, wk.parent);
-    hipLaunchKernelGGL(k_ct_trace, dim3(kCtTraceBlocks), dim3(64), 0, s, bits, g, wk.comps, wk.caps.comps, wk.pts,
-                       wk.caps.pts, wk.stage, wk.planes, wk.planes + pw, wk.ctr);
-    hipLaunchKernelGGL(k_ct_scan, dim3(n), dim3(64), 0, s, bits, g, wk.lab, wk.parent, wk.planes, pw, wk.comps,
+    if (boxes_only) {  // wk.pts, wk.stage and wk.shapes are not touched
+        hipLaunchKernelGGL(k_ct_trace<true>, dim3(kCtTraceBlocks), dim3(64), 0, s, bits, g, wk.comps, wk.caps.comps,
+                           wk.pts, wk.caps.pts, wk.stage, wk.planes, wk.planes + pw, wk.ctr);
+        hipLaunchKernelGGL(k_ct_scan<true>, dim3(n), dim3(64), 0, s, bits, g, wk.lab, wk.parent, wk.planes, pw,
+                           wk.comps, wk.caps.comps, wk.acc, wk.pts, wk.caps.pts, wk.refs, wk.caps.refs, wk.ctr,
+                           wk.img_info);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL(k_ct_trace<false>, dim3(kCtTraceBlocks), dim3(64), 0, s, bits, g, wk.comps, wk.caps.comps,
+                       wk.pts, wk.caps.pts, wk.stage, wk.planes, wk.planes + pw, wk.ctr);
+    hipLaunchKernelGGL(k_ct_scan<false>, dim3(n), dim3(64), 0, s, bits, g, wk.lab, wk.parent, wk.planes, pw, wk.comps,
                        wk.caps.comps, wk.acc, wk.pts, wk.caps.pts, wk.refs, wk.caps.refs, wk.ctr, wk.img_info);
     hipLaunchKernelGGL(k_ct_bases, dim3(1), dim3(1024), 0, s, n, wk.img_info, wk.ctr, wk.caps.shapes);
     hipLaunchKernelGGL(k_ct_shapes, dim3(8, n), dim3(64), 0, s, wk.comps, wk.pts, wk.refs, wk.img_info, wk.ctr,

@@ -233,6 +233,9 @@ struct Work {
     DevBuf<int> d_ct_info;
     DevBuf<llfe_shape> d_ct_shapes;
     CtCaps ct_min{0, 0, 0, 0};  // grown minimum capacities (0 = defaults)
+    // llfe_font_detect (font.hip): per-image records, the region lists of a pass
+    DevBuf<llfe_font_result> d_font_rec;
+    DevBuf<int4> d_font_reg;
 };
 
 // hipEvent pairs around launches (enabled by llfe_set_profiling)
@@ -597,8 +600,10 @@ int run_hysteresis_dilate(llfe_ctx *ctx, Work &W, int n, int h, int w, uint64_t 
     return LLFE_OK;
 }
 
-// External contours + shape records of W.d_bits on the GPU (hysteresis workspace reused)
-int run_contours(llfe_ctx *ctx, Work &W, int n, int h, int w, const uint64_t *bits, hipStream_t s) {
+// External contours + shape records of W.d_bits on the GPU (hysteresis workspace reused);
+// boxes: the boxes-only mode (no vertex, staging or shape storage)
+int run_contours(llfe_ctx *ctx, Work &W, int n, int h, int w, const uint64_t *bits, hipStream_t s,
+                 bool boxes = false) {
     CtCaps c = contours_default_caps(n, h, w);
     c.comps = std::max(c.comps, W.ct_min.comps);
     c.pts = std::max(c.pts, W.ct_min.pts);
@@ -612,16 +617,19 @@ int run_contours(llfe_ctx *ctx, Work &W, int n, int h, int w, const uint64_t *bi
     HIPCHK(ctx, W.d_ct_planes.ensure(5 * contours_plane_words(n, h, w)));
     HIPCHK(ctx, W.d_ct_comps.ensure(c.comps));
     HIPCHK(ctx, W.d_ct_acc.ensure(c.comps));
-    HIPCHK(ctx, W.d_ct_pts.ensure(c.pts));
+    if (!boxes) HIPCHK(ctx, W.d_ct_pts.ensure(c.pts));
     HIPCHK(ctx, W.d_ct_refs.ensure(c.refs));
-    HIPCHK(ctx, W.d_ct_stage.ensure((size_t)kCtTraceBlocks * kCtStage));
+    if (!boxes) HIPCHK(ctx, W.d_ct_stage.ensure((size_t)kCtTraceBlocks * kCtStage));
     HIPCHK(ctx, W.d_ct_ctr.ensure(1));
     HIPCHK(ctx, W.d_ct_info.ensure((size_t)n * kCtInfo));
-    HIPCHK(ctx, W.d_ct_shapes.ensure(c.shapes));
+    if (!boxes) HIPCHK(ctx, W.d_ct_shapes.ensure(c.shapes));
     CtWork wk{W.d_lab.p, W.d_parent.p, W.d_roots.p, W.d_nroots.p, W.d_ct_planes.p, W.d_ct_comps.p, W.d_ct_acc.p,
               W.d_ct_pts.p, W.d_ct_refs.p, W.d_ct_stage.p, W.d_ct_ctr.p, W.d_ct_info.p, W.d_ct_shapes.p, c};
     // algorithmic bytes: mask bits read by components + scan, labels written and read
-    TIMED(ctx, s, "k_contours", (double)n * h * w * (0.25 + 4.0), launch_contours(bits, n, h, w, wk, s));
+    if (boxes)
+        TIMED(ctx, s, "k_contours_boxes", (double)n * h * w * (0.25 + 4.0), launch_contours(bits, n, h, w, wk, s, true));
+    else
+        TIMED(ctx, s, "k_contours", (double)n * h * w * (0.25 + 4.0), launch_contours(bits, n, h, w, wk, s));
     return LLFE_OK;
 }
 
@@ -2149,6 +2157,80 @@ int llfe_shapes_from_masks_gpu(llfe_ctx *ctx, const uint8_t *masks, int32_t n, i
     }
     if (needed) *needed = total;
     return total > capacity ? LLFE_ERR_CAPACITY : LLFE_OK;
+}
+
+// FontDetector.detect_font after its binary (font_detector.py:39-67, :109-155) on workspace
+// 0 and the caller's stream: binary -> bit rows -> boxes-only contour pass -> region filter,
+// largest region, its gray sum (font.hip).  One D2H of the records per device pass, and
+// of the region list when it is asked for.
+int llfe_font_detect(llfe_ctx *ctx, const uint8_t *bgr, const uint8_t *binary, int32_t n, int32_t h, int32_t w,
+                     llfe_font_result *results, int32_t *regions, int64_t region_capacity, int64_t *regions_needed,
+                     llfe_stream stream) {
+    if (!ctx || !valid_dims(n, h, w) || (!bgr && !binary) || !results || (regions && region_capacity < 0))
+        return LLFE_ERR_INVALID;
+    if (int rc_ = stage_enter(ctx, __func__)) return rc_;
+    if (w > kCtMaxWidth || h > kCtMaxHeight)
+        return ctx->fail(LLFE_ERR_UNSUPPORTED, "llfe_font_detect needs width <= %d and height <= %d", kCtMaxWidth,
+                         kCtMaxHeight);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    Work &W = ctx->ws[0];
+    const int chunk = chunk_for(h, w);
+    const size_t P = (size_t)h * w;
+    int64_t total = 0;
+    HIPCHK(ctx, ctx->h_ct_ctr_s[0].ensure(1));
+    for (int i0 = 0; i0 < n; i0 += chunk) {
+        const int m = std::min(chunk, n - i0);
+        const uint8_t *img = bgr ? bgr + (size_t)i0 * P * 3 : nullptr;
+        const uint8_t *bin = binary ? binary + (size_t)i0 * P : nullptr;
+        if (!bin) {
+            HIPCHK(ctx, W.d_cls.ensure((size_t)m * P));
+            W.tflag_valid = false;  // d_cls no longer holds a class map
+            TIMED(ctx, s, "k_font_binary", (double)m * P * 4, launch_font_binary(img, m, h, w, W.d_cls.p, ctx->sp, s));
+            bin = W.d_cls.p;
+        }
+        HIPCHK(ctx, W.d_bits.ensure((size_t)m * h * words_per_row(w)));
+        TIMED(ctx, s, "k_font_pack", (double)m * P * (1 + 0.125), launch_font_pack(bin, m, h, w, W.d_bits.p, s));
+        HIPCHK(ctx, W.d_font_rec.ensure((size_t)m));
+        for (int attempt = 0;; attempt++) {
+            const int rc = run_contours(ctx, W, m, h, w, W.d_bits.p, s, true);
+            if (rc) return rc;
+            TIMED(ctx, s, "k_font_select", 0.0,
+                  launch_font_select(W.d_ct_comps.p, W.d_ct_refs.p, W.d_ct_info.p, m, W.d_font_rec.p, s));
+            if (img) TIMED(ctx, s, "k_font_gray_sum", 0.0, launch_font_gray_sum(img, m, h, w, W.d_font_rec.p, s));
+            HIPCHK(ctx, hipMemcpyAsync(ctx->h_ct_ctr_s[0].p, W.d_ct_ctr.p, sizeof(CtCounters), hipMemcpyDeviceToHost, s));
+            HIPCHK(ctx, hipMemcpyAsync(results + i0, W.d_font_rec.p, sizeof(llfe_font_result) * m,
+                                       hipMemcpyDeviceToHost, s));
+            HIPCHK(ctx, hipStreamSynchronize(s));
+            const CtCounters ct = *ctx->h_ct_ctr_s[0].p;
+            if (ct.flags & ~kCtOverflowMask)
+                return ctx->fail(LLFE_ERR_UNSUPPORTED, "llfe_font_detect: unsupported mask (flags 0x%x)", ct.flags);
+            if (!(ct.flags & kCtOverflowMask)) break;
+            if (attempt >= 8) return ctx->fail(LLFE_ERR_CAPACITY, "llfe_font_detect: capacities still overflow");
+            grow_contour_caps(W, m, h, w, ct);
+        }
+        int64_t chunk_total = 0;
+        for (int i = 0; i < m; i++) {
+            results[i0 + i].region_offset = total + chunk_total;
+            chunk_total += results[i0 + i].n_regions;
+        }
+        const int64_t room = std::max<int64_t>(0, std::min(chunk_total, region_capacity - total));
+        if (regions && room > 0) {
+            HIPCHK(ctx, W.d_font_reg.ensure((size_t)room));
+            TIMED(ctx, s, "k_font_regions", 0.0,
+                  launch_font_regions(W.d_ct_comps.p, W.d_ct_refs.p, W.d_ct_info.p, m, W.d_font_rec.p, W.d_font_reg.p,
+                                      room, s));
+            HIPCHK(ctx, hipMemcpyAsync(regions + 4 * total, W.d_font_reg.p, sizeof(int4) * (size_t)room,
+                                       hipMemcpyDeviceToHost, s));
+            HIPCHK(ctx, hipStreamSynchronize(s));
+        }
+        total += chunk_total;
+    }
+    ctx->prof.collect(-2);
+    if (regions_needed) *regions_needed = total;
+    if (regions && total > region_capacity)
+        return ctx->fail(LLFE_ERR_CAPACITY, "region capacity %lld < %lld", (long long)region_capacity, (long long)total);
+    return LLFE_OK;
 }
 
 double llfe_border_radius(const int32_t *points, int32_t n, double epsilon_factor) {

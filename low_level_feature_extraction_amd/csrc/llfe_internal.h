@@ -127,7 +127,26 @@ struct CtWork {
 };
 CtCaps contours_default_caps(int n, int h, int w);
 size_t contours_plane_words(int n, int h, int w);
-hipError_t launch_contours(const uint64_t *bits, int n, int h, int w, const CtWork &wk, hipStream_t s);
+// boxes_only: contour set, order (refs, img_info), areas and bounding boxes only -- no
+// vertices (wk.pts, wk.stage, wk.shapes may be null, caps.pts / caps.shapes are unused),
+// and the pass ends after k_ct_scan; kCtOverflowPts / kCtTooWide / kCtDpOverflow cannot arise
+hipError_t launch_contours(const uint64_t *bits, int n, int h, int w, const CtWork &wk, hipStream_t s,
+                           bool boxes_only = false);
+
+// FontDetector.detect_font after its binary (font.hip), on the boxes-only contour pass:
+//   pack:    n x h x w u8 binary (nonzero = foreground) -> n x h x words_per_row u64 bit rows
+//   select:  per image, the contours in cv2 order (newest start first) filtered by
+//            0.1 < w / h < 15 and h > 8 (as 10 w > h, w < 15 h): count, largest w * h
+//            (first on ties) -> rec[i] (gray_sum zeroed)
+//   regions: (optional) the kept boxes (x, y, w, h) in order, image after image, into
+//            regions[0, cap) (entries past cap are dropped; the counts in rec say so)
+//   gray:    rec[i].gray_sum = sum of BGR2GRAY over the winning rectangle of image i
+hipError_t launch_font_pack(const uint8_t *mask, int n, int h, int w, uint64_t *bits, hipStream_t s);
+hipError_t launch_font_select(const CtComp *comps, const int2 *refs, const int *img_info, int n,
+                              llfe_font_result *rec, hipStream_t s);
+hipError_t launch_font_regions(const CtComp *comps, const int2 *refs, const int *img_info, int n,
+                               const llfe_font_result *rec, int4 *regions, int64_t cap, hipStream_t s);
+hipError_t launch_font_gray_sum(const uint8_t *bgr, int n, int h, int w, llfe_font_result *rec, hipStream_t s);
 
 inline int words_per_row(int w) { return (w + 63) / 64; }
 inline int tiles_x(int w) { return (w + kTileW - 1) / kTileW; }
