@@ -42,10 +42,15 @@ extern "C" {
 #define LLFE_ERR_OOM (-4)
 #define LLFE_ERR_UNSUPPORTED (-5)
 
-/* feature mask bits (FeatureType colors / shapes / shadows) */
+/* feature mask bits (FeatureType colors / shapes / shadows / fonts) */
 #define LLFE_FEATURE_COLORS 1u
 #define LLFE_FEATURE_SHAPES 2u
 #define LLFE_FEATURE_SHADOWS 4u
+/* FontDetector.detect_font's pixel work (font_detector.py:17-67, :109-155): one
+ * llfe_font_result per image, fetched with llfe_font_records after the call (the
+ * 328-byte llfe_image_result does not change).  The pass runs on the shapes / shadows
+ * stream, beside the colour stream's k-means, in either contour mode. */
+#define LLFE_FEATURE_FONTS 8u
 
 /* shape type codes (ShapeAnalyzer.analyze_shapes @L159-172 type strings) */
 #define LLFE_SHAPE_UNKNOWN 0
@@ -190,6 +195,7 @@ int llfe_host_contour_stats(llfe_ctx *ctx, double *busy_ms, int64_t *images, int
  *   ColorExtractor.extract_colors native work  (color_extractor.py:217-236)
  *   ShapeAnalyzer.analyze_shapes               (shape pyc @L125-189)
  *   ShadowAnalyzer.analyze_shadow_level stats  (shadow pyc @L12-24)
+ *   FontDetector.detect_font's pixel work      (LLFE_FEATURE_FONTS; records: llfe_font_records)
  * results[n] host; shapes[shape_capacity] host; *shapes_needed = total shapes
  * (LLFE_ERR_CAPACITY when it exceeds shape_capacity; results are still valid). */
 int llfe_process_batch(llfe_ctx *ctx, const llfe_batch *batch, uint32_t features, uint64_t seed,
@@ -252,7 +258,7 @@ int llfe_batch_capacity(int32_t h, int32_t w);
 /* ---- stage entry points (parity tests; device in/out unless noted) ------
  * The ones that use the context's workspace (llfe_shape_mask, llfe_canny,
  * llfe_shadow_stats, llfe_color_unique, llfe_kmeans, llfe_find_contours_gpu,
- * llfe_shapes_from_masks_gpu, llfe_font_detect) and llfe_process_images return LLFE_ERR_INVALID while a
+ * llfe_shapes_from_masks_gpu, llfe_font_detect, llfe_font_bits) and llfe_process_images return LLFE_ERR_INVALID while a
  * batch submitted with llfe_submit_batch is not yet collected. */
 /* gray = cvtColor(BGR2GRAY); out = GaussianBlur(gray, (5,5), 0)
  * (shape pyc @L18-21, shadow pyc @L8-9) */
@@ -300,6 +306,29 @@ typedef struct {
 int llfe_font_detect(llfe_ctx *ctx, const uint8_t *bgr, const uint8_t *binary, int32_t n, int32_t h, int32_t w,
                      llfe_font_result *results, int32_t *regions, int64_t region_capacity,
                      int64_t *regions_needed, llfe_stream stream);
+/* The font binary of llfe_font_binary as bit rows, in one kernel (k_font_bits; the front end
+ * of LLFE_FEATURE_FONTS): bits is device n x h x ceil(w / 64) u64, bit x & 63 of word
+ * x >> 6 is pixel x (set = 255 in llfe_font_binary's mask), every bit at x >= w is 0.
+ * bgr is a device pointer (n x h x w x 3). */
+int llfe_font_bits(llfe_ctx *ctx, const uint8_t *bgr, uint64_t *bits, int32_t n, int32_t h, int32_t w,
+                   llfe_stream stream);
+/* the same for n separately allocated device images of one size: images is a HOST array of
+ * n device pointers, each a packed h x w x 3 image (what llfe_submit_images reads in place) */
+int llfe_font_bits_images(llfe_ctx *ctx, const uint8_t *const *images, uint64_t *bits, int32_t n, int32_t h,
+                          int32_t w, llfe_stream stream);
+/* host only: the column-strip width and row-segment height k_font_bits uses for an h x w
+ * image (one wave per strip and segment), so that tests can stand on its seams */
+int llfe_font_bits_tiling(int32_t h, int32_t w, int32_t *strip_w, int32_t *seg_h);
+/* font records of a call that ran with LLFE_FEATURE_FONTS.
+ * ticket = a collected llfe_submit_* ticket, or LLFE_LAST_CALL for the last
+ * llfe_process_batch / llfe_process_images.  n must equal that call's image count; out
+ * receives n records in the call's image order (region_offset is 0: no region lists on this
+ * path; for llfe_process_images the rectangle is in the preprocessed image's coordinates).
+ * Valid from the call's return (the ticket's collect) until the next process / collect on
+ * this context.  LLFE_ERR_INVALID for an uncollected, unknown or expired ticket, a call that
+ * ran without the bit, or a wrong n. */
+#define LLFE_LAST_CALL (-1)
+int llfe_font_records(llfe_ctx *ctx, int64_t ticket, llfe_font_result *out, int32_t n);
 /* TextExtractor.preprocess_image (app/services/analyze/text_extractor.py:15-46): gray
  * (cvtColor BGR2GRAY for 3 / 4 channels, the image itself for 1), INTER_CUBIC upscale by
  * max(2, 300 / w, 100 / h) when h < 30 or w < 100, Otsu THRESH_BINARY, bitwise_not when

@@ -30,6 +30,8 @@ LLFE_ERR_UNSUPPORTED = -5
 FEATURE_COLORS = 1
 FEATURE_SHAPES = 2
 FEATURE_SHADOWS = 4
+FEATURE_FONTS = 8
+LAST_CALL = -1  # LLFE_LAST_CALL (llfe_font_records)
 
 SHAPE_TYPES = {0: "unknown", 1: "triangle", 2: "rectangle", 3: "circle", 4: "polygon"}
 
@@ -161,6 +163,10 @@ SIGNATURES = {
     "llfe_dilate3": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "llfe_font_binary": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "llfe_font_detect": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _i64, C.POINTER(C.c_int64), _vp]),
+    "llfe_font_bits": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "llfe_font_bits_images": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "llfe_font_bits_tiling": (C.c_int, [_i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),
+    "llfe_font_records": (C.c_int, [_vp, _i64, _vp, _i32]),
     "llfe_text_binary": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, C.POINTER(_i32), _vp]),
     "llfe_text_size": (C.c_int, [_i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),
     "llfe_shadow_stats": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),

@@ -19,7 +19,8 @@ import numpy as np
 
 from . import _lib as L
 
-FEATURE_BITS = {"colors": L.FEATURE_COLORS, "shapes": L.FEATURE_SHAPES, "shadows": L.FEATURE_SHADOWS}
+FEATURE_BITS = {"colors": L.FEATURE_COLORS, "shapes": L.FEATURE_SHAPES, "shadows": L.FEATURE_SHADOWS,
+                "fonts": L.FEATURE_FONTS}
 
 
 SHADOW_LEVELS = ("Low", "Moderate", "High")  # llfe_image_result.shadow_level 0 / 1 / 2
@@ -53,6 +54,9 @@ class ImageFeatures:
     # palette (primary, background, [3 accents]) and analyze_shadow_level's level
     palette: tuple | None = None
     shadow_level: str | None = None
+    # "fonts": the image's llfe_font_result as font_detect's dict (n_contours, n_regions, x, y,
+    # width, height, gray_sum)
+    font: dict | None = None
 
 
 def _torch():
@@ -67,6 +71,14 @@ def _is_torch(x) -> bool:
     except ImportError:  # pragma: no cover
         return False
     return isinstance(x, torch.Tensor)
+
+
+def font_bits_tiling(h: int, w: int):
+    """(strip width, segment height) of k_font_bits for an h x w image (llfe_font_bits_tiling)."""
+    sw, sh = C.c_int32(0), C.c_int32(0)
+    if L.lib().llfe_font_bits_tiling(int(h), int(w), C.byref(sw), C.byref(sh)) < 0:
+        raise ValueError(f"font_bits_tiling: invalid {h}x{w}")
+    return sw.value, sh.value
 
 
 def text_size(h: int, w: int):
@@ -248,7 +260,8 @@ class Backend:
                     continue
                 self._chk(rc)
                 break
-        out = self._convert(results, shapes, n, mask, w, h)
+            fonts = self._font_records(L.LAST_CALL, n, mask)
+        out = self._convert(results, shapes, n, mask, w, h, fonts)
         del keep, nkeep
         return out
 
@@ -306,12 +319,25 @@ class Backend:
                     continue
                 self._chk(rc)
                 break
-        out = self._convert(results, shapes, n, mask, [sz[0] for sz in sizes], [sz[1] for sz in sizes])
+            fonts = self._font_records(L.LAST_CALL, n, mask)
+        out = self._convert(results, shapes, n, mask, [sz[0] for sz in sizes], [sz[1] for sz in sizes], fonts)
         del keep
         return out
 
+    def _font_records(self, ticket: int, n: int, mask: int):
+        """The font records of the call just made (llfe_font_records; the caller holds the
+        context lock, so no other call comes between) as font_detect's dicts, or None
+        without the fonts bit."""
+        if not mask & L.FEATURE_FONTS:
+            return None
+        res = (L.LlfeFontResult * max(n, 1))()
+        self._chk(self._lib.llfe_font_records(self.ctx, C.c_int64(ticket), res, n))
+        F = np.ctypeslib.as_array(res)[:n]
+        cols = [F[k].tolist() for k in _FONT_FIELDS]
+        return [dict(zip(_FONT_FIELDS, v)) for v in zip(*cols)]
+
     @staticmethod
-    def _convert(results, shapes, n, mask, w, h) -> list:
+    def _convert(results, shapes, n, mask, w, h, fonts=None) -> list:
         # bulk conversion through numpy views of the ctypes arrays (per-field ctypes
         # access would cost ~20 us per image while the GPU waits for the next batch)
         R = np.ctypeslib.as_array(results)[:n]
@@ -344,7 +370,8 @@ class Backend:
         ws = w if isinstance(w, list) else [w] * n
         hs = h if isinstance(h, list) else [h] * n
         out = [ImageFeatures(cen[i, :ncol[i]], cnt[i, :ncol[i]], nu[i], comp[i], ssum[i], scnt[i],
-                             recs[off[i]:off[i] + nsh[i]] if recs else [], ncont[i], ws[i], hs[i], pal[i], lv[i])
+                             recs[off[i]:off[i] + nsh[i]] if recs else [], ncont[i], ws[i], hs[i], pal[i], lv[i],
+                             fonts[i] if fonts else None)
                for i in range(n)]
         return out
 
@@ -445,8 +472,9 @@ class Backend:
                     continue
                 self._chk(rc)
                 break
+            fonts = self._font_records(ticket, n, mask)
         del self._inflight[ticket]
-        return self._convert(results, shapes, n, mask, w, h)
+        return self._convert(results, shapes, n, mask, w, h, fonts)
 
     # ------------------------------------------------------------------ stages (device tensors)
     def _dev_batch(self, images):
@@ -480,6 +508,27 @@ class Backend:
         n, h, w, _ = x.shape
         out = torch.empty((n, h, w), dtype=torch.uint8, device=x.device)
         self._call("llfe_font_binary", x.data_ptr(), out.data_ptr(), n, h, w, self._stream(x))
+        return out
+
+    def font_bits(self, images):
+        """The font binary as bit rows in one kernel (llfe_font_bits): n x h x ceil(w / 64)
+        int64 device tensor (the u64 words; bit x & 63 of word x >> 6 is pixel x).  ``images``:
+        an N x H x W x 3 batch, or a list of separately allocated H x W x 3 device tensors of
+        one size, read in place through an address table (llfe_font_bits_images)."""
+        torch = _torch()
+        if isinstance(images, (list, tuple)):
+            ts = [t.to(f"cuda:{self.device}").contiguous() for t in images]
+            n, (h, w, _) = len(ts), ts[0].shape
+            if any(tuple(t.shape) != (h, w, 3) or t.dtype != torch.uint8 for t in ts):
+                raise ValueError("font_bits: a list must hold H x W x 3 uint8 tensors of one size")
+            out = torch.empty((n, h, (w + 63) // 64), dtype=torch.int64, device=ts[0].device)
+            tab = (C.c_void_p * n)(*[t.data_ptr() for t in ts])
+            self._call("llfe_font_bits_images", tab, out.data_ptr(), n, h, w, self._stream(ts[0]))
+            return out
+        x = self._dev_batch(images)
+        n, h, w, _ = x.shape
+        out = torch.empty((n, h, (w + 63) // 64), dtype=torch.int64, device=x.device)
+        self._call("llfe_font_bits", x.data_ptr(), out.data_ptr(), n, h, w, self._stream(x))
         return out
 
     def font_detect(self, images, binary=None, regions=False) -> list:
@@ -760,6 +809,7 @@ class Backend:
         return out
 
 
+_FONT_FIELDS = ("n_contours", "n_regions", "x", "y", "width", "height", "gray_sum")
 # "gpu_force_fallback": diagnostic GPU mode whose chunks all take the host fallback
 CONTOUR_MODES = {"host": 0, "gpu": 1, "gpu_force_fallback": 2}
 CV_INTER = {"linear": 1, "cubic": 2, "area": 3, "lanczos4": 4}

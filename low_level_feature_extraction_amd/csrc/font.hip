@@ -153,7 +153,9 @@ __global__ __launch_bounds__(NT) void k_font_regions(const CtComp *__restrict__ 
 
 // grid (G, n): the rows of image blockIdx.y's winning rectangle go round the waves of
 // its G workgroups; exact u64 sum, one atomic per workgroup
-__global__ __launch_bounds__(NT) void k_font_gray_sum(const uint8_t *__restrict__ bgr, int H, int W,
+// (img_tab, may be null: image i at img_tab[i] instead of bgr + i * H * W * 3)
+__global__ __launch_bounds__(NT) void k_font_gray_sum(const uint8_t *__restrict__ bgr,
+                                                      const uint64_t *__restrict__ img_tab, int H, int W,
                                                       llfe_font_result *rec) {
     __shared__ unsigned long long s_sum[NW];
     const int img = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -162,7 +164,7 @@ __global__ __launch_bounds__(NT) void k_font_gray_sum(const uint8_t *__restrict_
     } r = {rec[img].n_regions, rec[img].x, rec[img].y, rec[img].width, rec[img].height};  // (not gray_sum: others add)
     if (r.n_regions <= 0|| r.width <= 0 || r.height <= 0) return;
     if (r.x < 0 || r.y < 0 || r.x + r.width > W || r.y + r.height > H) return;  // (never: boxes lie in the image)
-    const uint8_t *im = bgr + (size_t)img * H * W * 3;
+    const uint8_t *im = img_tab ? (const uint8_t *)img_tab[img] : bgr + (size_t)img * H * W * 3;
     unsigned long long sum = 0;
     for (int row = blockIdx.x * NW + wv; row < r.height; row += gridDim.x * NW) {
         const uint8_t *p = im + ((size_t)(r.y + row) * W + r.x) * 3;
@@ -207,10 +209,11 @@ hipError_t launch_font_regions(const CtComp *comps, const int2 *refs, const int 
     return hipGetLastError();
 }
 
-hipError_t launch_font_gray_sum(const uint8_t *bgr, int n, int h, int w, llfe_font_result *rec, hipStream_t s) {
+hipError_t launch_font_gray_sum(const uint8_t *bgr, int n, int h, int w, llfe_font_result *rec, hipStream_t s,
+                                const uint64_t *img_tab) {
     if (n <= 0) return hipSuccess;
     const int g = std::max(1, std::min(32, (h + NW - 1) / NW));
-    hipLaunchKernelGGL(k_font_gray_sum, dim3(g, n), dim3(NT), 0, s, bgr, h, w, rec);
+    hipLaunchKernelGGL(k_font_gray_sum, dim3(g, n), dim3(NT), 0, s, bgr, img_tab, h, w, rec);
     return hipGetLastError();
 }
 

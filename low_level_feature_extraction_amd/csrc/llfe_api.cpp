@@ -236,6 +236,7 @@ struct Work {
     // llfe_font_detect (font.hip): per-image records, the region lists of a pass
     DevBuf<llfe_font_result> d_font_rec;
     DevBuf<int4> d_font_reg;
+    DevBuf<uint64_t> d_fbits;  // LLFE_FEATURE_FONTS: the chunk's font bit rows (k_font_bits)
 };
 
 // hipEvent pairs around launches (enabled by llfe_set_profiling)
@@ -420,6 +421,7 @@ struct llfe_ctx {
         std::vector<llfe_image_result> res;
         std::vector<llfe_shape> shp;
         std::vector<int64_t> idx;  // llfe_submit_images: the images' global indices (b.indices)
+        std::vector<llfe_font_result> fnt;  // LLFE_FEATURE_FONTS: the records (llfe_font_records)
     };
     Pending inflight[kMaxSlots];
     bool any_inflight() const {
@@ -470,6 +472,20 @@ struct llfe_ctx {
     HostBuf<uint64_t> h_gather_s[kMaxSlots];
     DevBuf<uint64_t> d_gather_s[kMaxSlots];
     Work *km_last = nullptr;  // workspace of the last k-means launch (llfe_kmeans_attempts)
+    // LLFE_FEATURE_FONTS: per slot the records and counters of the chunk's font pass, whether
+    // that pass ran its contours on the GPU (else finish_chunk takes the host path) and the
+    // image table the chunk was read through (llfe_submit_images in place; null: packed)
+    HostBuf<llfe_font_result> h_font_rec_s[kMaxSlots];
+    HostBuf<CtCounters> h_font_ctr_s[kMaxSlots];
+    bool slot_font_gpu[kMaxSlots] = {};
+    const uint64_t *slot_tab[kMaxSlots] = {};
+    HostBuf<uint64_t> h_fbits;  // font bit rows of a chunk on the host path
+    int64_t font_fallbacks = 0;  // font chunks whose contours ran on the host pool
+    // llfe_font_records: the records of the last process call (font_owner = LLFE_LAST_CALL) or
+    // the last collected ticket, valid until the next process / collect
+    std::vector<llfe_font_result> font_recs;
+    int64_t font_owner = LLFE_LAST_CALL;
+    bool font_has = false;
     // per-thread host scratch
     std::vector<std::vector<int8_t>> work;
     std::vector<Contours> cont;
@@ -824,6 +840,26 @@ int chunk_index(llfe_ctx *ctx, Work &W, const llfe_batch *b, int i0, int n, hipS
     return LLFE_OK;
 }
 
+// LLFE_FEATURE_FONTS after k_font_bits, on stream s: the boxes-only contour pass over
+// W.d_fbits, the region filter and largest region, its gray sum, then the D2H of the n
+// records and of the pass's counters into host slot `slot` (on s itself, so whatever
+// follows on s may reuse the contour workspace).
+int font_pass(llfe_ctx *ctx, Work &W, const uint8_t *img, const uint64_t *img_tab, int n, int h, int w, int slot,
+              hipStream_t s) {
+    HIPCHK(ctx, W.d_font_rec.ensure((size_t)n));
+    HIPCHK(ctx, ctx->h_font_rec_s[slot].ensure((size_t)n));
+    HIPCHK(ctx, ctx->h_font_ctr_s[slot].ensure(1));
+    const int rc = run_contours(ctx, W, n, h, w, W.d_fbits.p, s, true);
+    if (rc) return rc;
+    TIMED(ctx, s, "k_font_select", 0.0,
+          launch_font_select(W.d_ct_comps.p, W.d_ct_refs.p, W.d_ct_info.p, n, W.d_font_rec.p, s));
+    TIMED(ctx, s, "k_font_gray_sum", 0.0, launch_font_gray_sum(img, n, h, w, W.d_font_rec.p, s, img_tab));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_font_ctr_s[slot].p, W.d_ct_ctr.p, sizeof(CtCounters), hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_font_rec_s[slot].p, W.d_font_rec.p, sizeof(llfe_font_result) * n,
+                               hipMemcpyDeviceToHost, s));
+    return LLFE_OK;
+}
+
 // Device half of one chunk, on slot `slot`'s stream and workspace: every kernel, then
 // the D2H of the per-image results into host slot `slot`, with events the host half
 // waits on.
@@ -836,7 +872,7 @@ int enqueue_chunk(llfe_ctx *ctx, const llfe_batch *b, uint32_t features, uint64_
     hipStream_t s = ctx->streams[q];
     const int h = b->height, w = b->width, wpr = words_per_row(w);
     const bool want_col = features & LLFE_FEATURE_COLORS, want_shp = features & LLFE_FEATURE_SHAPES,
-               want_shd = features & LLFE_FEATURE_SHADOWS;
+               want_shd = features & LLFE_FEATURE_SHADOWS, want_fnt = features & LLFE_FEATURE_FONTS;
     const int64_t P = (int64_t)h * w;
     const int64_t key_stride = (std::max<int64_t>(P, 1) + 3) & ~int64_t(3);
     const int n_colors = b->n_colors ? b->n_colors : kMaxK;
@@ -853,7 +889,7 @@ int enqueue_chunk(llfe_ctx *ctx, const llfe_batch *b, uint32_t features, uint64_
     // k-means 12.8k -- the stencil waves slow the k-means attempts more than they fill
     // its tail.
     hipStream_t col_s = s;
-    if (want_col && ctx->concurrent && (want_shp || want_shd)) {
+    if (want_col && ctx->concurrent && (want_shp || want_shd || want_fnt)) {
         col_s = ctx->col_streams[q];
         HIPCHK(ctx, hipEventRecord(ctx->input_ready, s));
         HIPCHK(ctx, hipStreamWaitEvent(col_s, ctx->input_ready, 0));
@@ -866,6 +902,20 @@ int enqueue_chunk(llfe_ctx *ctx, const llfe_batch *b, uint32_t features, uint64_
     }
     // d_shadow / d_bits of this workspace may still be in the previous chunk's D2H
     if (ctx->w_mask_slot[q] >= 0) HIPCHK(ctx, hipStreamWaitEvent(s, ctx->mask_done[ctx->w_mask_slot[q]], 0));
+    // fonts first on this stream: the pass shares the hysteresis / contour workspace with the
+    // shapes pass below, and its records and counters have left it (d_font_rec, the host
+    // slot) before the shapes pass overwrites it
+    ctx->slot_tab[slot] = img_tab;
+    if (want_fnt) {
+        HIPCHK(ctx, W.d_fbits.ensure((size_t)n * h * wpr));
+        TIMED(ctx, s, "k_font_bits", (double)n * P * (3 + 0.125), launch_font_bits(img, img_tab, n, h, w, W.d_fbits.p, s));
+        // (wider / taller than the GPU contour pass takes: finish_chunk runs the host path)
+        ctx->slot_font_gpu[slot] = w <= kCtMaxWidth && h <= kCtMaxHeight;
+        if (ctx->slot_font_gpu[slot]) {
+            rc = font_pass(ctx, W, img, img_tab, n, h, w, slot, s);
+            if (rc) return rc;
+        }
+    }
     if (want_shp || want_shd) {
         HIPCHK(ctx, W.d_shadow.ensure(2 * (size_t)n + shadow_tiles(n, h, w)));
         StencilParams sp = ctx->sp;
@@ -987,6 +1037,102 @@ int redo_masks(llfe_ctx *ctx, const llfe_batch *b, int i0, int n, hipStream_t s)
     return run_hysteresis_dilate(ctx, W, n, h, w, W.d_bits.p, nullptr, s);
 }
 
+// Recompute the font bit rows of a chunk synchronously into workspace 0's d_fbits (the
+// device is idle after the hipDeviceSynchronize; the input is still the caller's, read
+// through the slot's image table when the chunk was submitted in place).
+int redo_font_bits(llfe_ctx *ctx, const llfe_batch *b, int i0, int n, int slot, hipStream_t s, const uint8_t **img) {
+    HIPCHK(ctx, hipDeviceSynchronize());
+    Work &W = ctx->ws[0];
+    const int h = b->height, w = b->width;
+    const int8_t *noise;
+    llfe_batch nb = *b;
+    nb.noise = nullptr;
+    const int rc = stage_input(ctx, W, &nb, i0, n, img, &noise, s);
+    if (rc) return rc;
+    HIPCHK(ctx, W.d_fbits.ensure((size_t)n * h * words_per_row(w)));
+    HIPCHK(ctx, launch_font_bits(*img, ctx->slot_tab[slot], n, h, w, W.d_fbits.p, s));
+    return LLFE_OK;
+}
+
+// Font records of a chunk (LLFE_FEATURE_FONTS) from the slot's host copies.  The rare cases
+// go the way gpu_shapes_of_chunk's do, so one unusual image never fails its batch: a pass
+// that overflowed a contour capacity is redone for this chunk alone, synchronously on
+// workspace 0, with the capacities grown from what its counters asked for; an image wider
+// than 4096 / taller than 65535, or a mask the border follower flags, has its bit rows
+// copied back and traced on the host pool (external_contours_bits), boxes, filter and first
+// maximum of w * h on the host, and only the gray sums on the device.
+int fonts_of_chunk(llfe_ctx *ctx, const llfe_batch *b, int i0, int n, int slot, llfe_font_result *out) {
+    const int h = b->height, w = b->width, wpr = words_per_row(w);
+    hipStream_t s = ctx->streams[0];
+    Work &W = ctx->ws[0];
+    bool host = !ctx->slot_font_gpu[slot];
+    for (int attempt = 0; !host; attempt++) {
+        const CtCounters ct = *ctx->h_font_ctr_s[slot].p;
+        if (ct.flags & ~kCtOverflowMask) {
+            host = true;
+            break;
+        }
+        if (!(ct.flags & kCtOverflowMask)) break;
+        if (attempt >= 8) return ctx->fail(LLFE_ERR_CAPACITY, "font contours: capacities still overflow (0x%x)", ct.flags);
+        const uint8_t *img;
+        int rc = redo_font_bits(ctx, b, i0, n, slot, s, &img);
+        if (rc) return rc;
+        grow_contour_caps(W, n, h, w, ct);
+        rc = font_pass(ctx, W, img, ctx->slot_tab[slot], n, h, w, slot, s);
+        if (rc) return rc;
+        HIPCHK(ctx, hipStreamSynchronize(s));
+    }
+    if (!host) {
+        std::memcpy(out, ctx->h_font_rec_s[slot].p, sizeof(llfe_font_result) * (size_t)n);
+        return LLFE_OK;
+    }
+    const uint8_t *img;
+    int rc = redo_font_bits(ctx, b, i0, n, slot, s, &img);
+    if (rc) return rc;
+    const size_t words = (size_t)n * h * wpr;
+    HIPCHK(ctx, ctx->h_fbits.ensure(words));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_fbits.p, W.d_fbits.p, sizeof(uint64_t) * words, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    const uint64_t *hb = ctx->h_fbits.p;
+    ctx->pool->parallel_for(n, [&](int i, int wid) {
+        Contours &c = ctx->cont[wid];
+        external_contours_bits(hb + (size_t)i * h * wpr, h, w, wpr, ctx->work[wid], c);
+        const int nc = (int)c.start.size() - 1;
+        llfe_font_result r{};
+        r.n_contours = std::max(nc, 0);
+        int64_t best = -1;
+        for (int k = 0; k < nc; k++) {  // cv2's list order: newest start first
+            const int j = nc - 1 - k;
+            int x0 = INT32_MAX, y0 = INT32_MAX, x1 = INT32_MIN, y1 = INT32_MIN;
+            for (int64_t p = c.start[j]; p < c.start[j + 1]; p++) {
+                x0 = std::min(x0, c.xy[2 * p]);
+                x1 = std::max(x1, c.xy[2 * p]);
+                y0 = std::min(y0, c.xy[2 * p + 1]);
+                y1 = std::max(y1, c.xy[2 * p + 1]);
+            }
+            if (x1 < x0) continue;
+            const int64_t bw = (int64_t)x1 - x0 + 1, bh = (int64_t)y1 - y0 + 1;
+            if (!(10 * bw > bh && bw < 15 * bh && bh > 8)) continue;  // 0.1 < w / float(h) < 15 and h > 8
+            r.n_regions++;
+            if (bw * bh > best) {  // max(key = w * h): the first maximum wins
+                best = bw * bh;
+                r.x = x0;
+                r.y = y0;
+                r.width = (int32_t)bw;
+                r.height = (int32_t)bh;
+            }
+        }
+        out[i] = r;
+    });
+    HIPCHK(ctx, W.d_font_rec.ensure((size_t)n));
+    HIPCHK(ctx, hipMemcpyAsync(W.d_font_rec.p, out, sizeof(llfe_font_result) * n, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, launch_font_gray_sum(img, n, h, w, W.d_font_rec.p, s, ctx->slot_tab[slot]));
+    HIPCHK(ctx, hipMemcpyAsync(out, W.d_font_rec.p, sizeof(llfe_font_result) * n, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    ctx->font_fallbacks++;
+    return LLFE_OK;
+}
+
 // Shape records of a chunk whose contours ran on the GPU (slot's host copies).  A pass
 // that overflowed a capacity is redone for this chunk alone, synchronously, with the
 // capacities grown from what its counters asked for.  A mask the GPU tracer does not
@@ -1049,8 +1195,10 @@ int gpu_shapes_of_chunk(llfe_ctx *ctx, const llfe_batch *b, int i0, int n, int s
 }
 
 // Host half of one chunk: wait for its slot, fill the result records, trace contours.
+// fonts (LLFE_FEATURE_FONTS): the batch's font records; the chunk's go to fonts[i0 ...]
 int finish_chunk(llfe_ctx *ctx, const llfe_batch *b, uint32_t features, int i0, int n, int slot,
-                 llfe_image_result *results, llfe_shape *shapes, int64_t shape_capacity, int64_t &total_shapes) {
+                 llfe_image_result *results, llfe_shape *shapes, int64_t shape_capacity, int64_t &total_shapes,
+                 llfe_font_result *fonts) {
     const int h = b->height, w = b->width, wpr = words_per_row(w);
     const bool want_col = features & LLFE_FEATURE_COLORS, want_shp = features & LLFE_FEATURE_SHAPES,
                want_shd = features & LLFE_FEATURE_SHADOWS;
@@ -1066,6 +1214,10 @@ int finish_chunk(llfe_ctx *ctx, const llfe_batch *b, uint32_t features, int i0, 
             r.shadow_count = sh[n + i];
             r.shadow_level = shadow_level(r.shadow_sum, r.shadow_count);
         }
+    }
+    if ((features & LLFE_FEATURE_FONTS) && fonts) {
+        int rc = fonts_of_chunk(ctx, b, i0, n, slot, fonts + i0);
+        if (rc) return rc;
     }
     if (want_shp && ctx->slot_gpu_ct[slot]) {
         int rc = gpu_shapes_of_chunk(ctx, b, i0, n, slot, results, shapes, shape_capacity, total_shapes);
@@ -1288,6 +1440,9 @@ int llfe_process_batch(llfe_ctx *ctx, const llfe_batch *b, uint32_t features, ui
     hipStream_t s = (hipStream_t)stream;
     const bool want_shp = features & LLFE_FEATURE_SHAPES;
     int64_t total_shapes = 0;
+    ctx->font_has = false;  // (llfe_font_records: the previous call's records end here)
+    ctx->font_recs.assign((features & LLFE_FEATURE_FONTS) ? (size_t)b->n : 0, llfe_font_result{});
+    llfe_font_result *const fonts = ctx->font_recs.data();
     // two-slot software pipeline: enqueue chunk c on stream c & 1 (kernels + D2H into
     // slot c & 1), then finish chunk c - 1 on the host (contours, result records) while
     // the GPU runs c -- and the tail of c - 1's k-means shares the GPU with c.  Both
@@ -1301,7 +1456,8 @@ int llfe_process_batch(llfe_ctx *ctx, const llfe_batch *b, uint32_t features, ui
         int rc = enqueue_chunk(ctx, b, features, seed, i0, n, slot, 0);
         if (rc) return rc;
         if (prev_i0 >= 0) {
-            rc = finish_chunk(ctx, b, features, prev_i0, prev_n, slot ^ 1, results, shapes, shape_capacity, total_shapes);
+            rc = finish_chunk(ctx, b, features, prev_i0, prev_n, slot ^ 1, results, shapes, shape_capacity, total_shapes,
+                              fonts);
             if (rc) return rc;
         }
         prev_i0 = i0;
@@ -1309,7 +1465,8 @@ int llfe_process_batch(llfe_ctx *ctx, const llfe_batch *b, uint32_t features, ui
         slot ^= 1;
     }
     if (prev_i0 >= 0) {
-        int rc = finish_chunk(ctx, b, features, prev_i0, prev_n, slot ^ 1, results, shapes, shape_capacity, total_shapes);
+        int rc = finish_chunk(ctx, b, features, prev_i0, prev_n, slot ^ 1, results, shapes, shape_capacity, total_shapes,
+                              fonts);
         if (rc) return rc;
     }
     // (every chunk has been waited for; the caller's stream gets the same order)
@@ -1318,6 +1475,8 @@ int llfe_process_batch(llfe_ctx *ctx, const llfe_batch *b, uint32_t features, ui
         HIPCHK(ctx, hipStreamWaitEvent(s, ctx->stream_done[q], 0));
     }
     ctx->prof.collect();
+    ctx->font_owner = LLFE_LAST_CALL;
+    ctx->font_has = (features & LLFE_FEATURE_FONTS) != 0;
     if (shapes_needed) *shapes_needed = total_shapes;
     if (want_shp && total_shapes > shape_capacity)
         return ctx->fail(LLFE_ERR_CAPACITY, "shape capacity %lld < %lld", (long long)shape_capacity,
@@ -1377,9 +1536,11 @@ int llfe_process_images(llfe_ctx *ctx, const llfe_image_desc *images, int32_t n,
             }
         }
     }
-    const bool want_shp = features & LLFE_FEATURE_SHAPES;
+    const bool want_shp = features & LLFE_FEATURE_SHAPES, want_fnt = features & LLFE_FEATURE_FONTS;
     int64_t total_shapes = 0;
     bool short_cap = false;
+    ctx->font_has = false;
+    std::vector<llfe_font_result> fonts(want_fnt ? (size_t)n : 0);  // in input order (each group's call leaves its own)
     std::vector<llfe_image_result> res;
     std::vector<int64_t> gidx;
     for (const auto &g : groups) {
@@ -1440,10 +1601,14 @@ int llfe_process_images(llfe_ctx *ctx, const llfe_image_desc *images, int32_t n,
                 llfe_image_result r = res[j];
                 r.shape_offset += total_shapes;
                 results[g.second[a + j]] = r;
+                if (want_fnt) fonts[g.second[a + j]] = ctx->font_recs[j];
             }
             total_shapes += need;
         }
     }
+    ctx->font_recs.swap(fonts);
+    ctx->font_owner = LLFE_LAST_CALL;
+    ctx->font_has = want_fnt;
     if (shapes_needed) *shapes_needed = total_shapes;
     if (want_shp && (short_cap || total_shapes > shape_capacity))
         return ctx->fail(LLFE_ERR_CAPACITY, "shape capacity %lld < %lld", (long long)shape_capacity,
@@ -1589,8 +1754,11 @@ int llfe_collect_batch(llfe_ctx *ctx, int64_t ticket, llfe_image_result *results
         pd.res.assign((size_t)n, llfe_image_result{});
         int64_t total = 0;
         if (n > 0) {
-            int rc = finish_chunk(ctx, &pd.b, pd.features, 0, n, slot, pd.res.data(), nullptr, 0, total);
+            pd.fnt.assign((pd.features & LLFE_FEATURE_FONTS) ? (size_t)n : 0, llfe_font_result{});
+            int rc = finish_chunk(ctx, &pd.b, pd.features, 0, n, slot, pd.res.data(), nullptr, 0, total, pd.fnt.data());
             if (rc) return rc;
+        } else {
+            pd.fnt.clear();
         }
         pd.shp.clear();
         if (pd.features & LLFE_FEATURE_SHAPES) {
@@ -1610,6 +1778,20 @@ int llfe_collect_batch(llfe_ctx *ctx, int64_t ticket, llfe_image_result *results
         return ctx->fail(LLFE_ERR_CAPACITY, "shape capacity %lld < %lld", (long long)shape_capacity, (long long)total);
     pd.busy = false;
     ctx->next_collect++;
+    ctx->font_recs.swap(pd.fnt);
+    ctx->font_owner = ticket;
+    ctx->font_has = (pd.features & LLFE_FEATURE_FONTS) != 0;
+    return LLFE_OK;
+}
+
+int llfe_font_records(llfe_ctx *ctx, int64_t ticket, llfe_font_result *out, int32_t n) {
+    if (!ctx || !out || n < 0) return LLFE_ERR_INVALID;
+    if (!ctx->font_has || ticket != ctx->font_owner)
+        return ctx->fail(LLFE_ERR_INVALID, "llfe_font_records: no font records of ticket %lld (not collected, expired, "
+                                           "or run without LLFE_FEATURE_FONTS)", (long long)ticket);
+    if ((size_t)n != ctx->font_recs.size())
+        return ctx->fail(LLFE_ERR_INVALID, "llfe_font_records: n=%d, the call had %zu images", n, ctx->font_recs.size());
+    if (n) std::memcpy(out, ctx->font_recs.data(), sizeof(llfe_font_result) * (size_t)n);
     return LLFE_OK;
 }
 
@@ -1637,6 +1819,49 @@ int llfe_font_binary(llfe_ctx *ctx, const uint8_t *bgr, uint8_t *mask, int32_t n
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, launch_font_binary(bgr, n, h, w, mask, ctx->sp, (hipStream_t)stream));
     HIPCHK(ctx, hipStreamSynchronize((hipStream_t)stream));
+    return LLFE_OK;
+}
+
+namespace {
+int font_bits_stage(llfe_ctx *ctx, const uint8_t *bgr, const uint64_t *img_tab, uint64_t *bits, int n, int h, int w,
+                    hipStream_t s) {
+    TIMED(ctx, s, "k_font_bits", (double)n * h * w * (3 + 0.125), launch_font_bits(bgr, img_tab, n, h, w, bits, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    ctx->prof.collect(-2);
+    return LLFE_OK;
+}
+}  // namespace
+
+int llfe_font_bits(llfe_ctx *ctx, const uint8_t *bgr, uint64_t *bits, int32_t n, int32_t h, int32_t w,
+                   llfe_stream stream) {
+    if (!ctx || !valid_dims(n, h, w) || !bgr || !bits) return LLFE_ERR_INVALID;
+    if (int rc_ = stage_enter(ctx, __func__)) return rc_;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return font_bits_stage(ctx, bgr, nullptr, bits, n, h, w, (hipStream_t)stream);
+}
+
+int llfe_font_bits_images(llfe_ctx *ctx, const uint8_t *const *images, uint64_t *bits, int32_t n, int32_t h,
+                          int32_t w, llfe_stream stream) {
+    if (!ctx || !valid_dims(n, h, w) || n < 1 || !images || !bits) return LLFE_ERR_INVALID;
+    for (int i = 0; i < n; i++)
+        if (!images[i]) return LLFE_ERR_INVALID;
+    if (int rc_ = stage_enter(ctx, __func__)) return rc_;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    // (slot 0's gather table: no batch is in flight)
+    HIPCHK(ctx, ctx->h_gather_s[0].ensure((size_t)n));
+    HIPCHK(ctx, ctx->d_gather_s[0].ensure((size_t)n));
+    for (int i = 0; i < n; i++) ctx->h_gather_s[0].p[i] = (uint64_t)(uintptr_t)images[i];
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_gather_s[0].p, ctx->h_gather_s[0].p, sizeof(uint64_t) * n, hipMemcpyHostToDevice, s));
+    return font_bits_stage(ctx, images[0], ctx->d_gather_s[0].p, bits, n, h, w, s);
+}
+
+int llfe_font_bits_tiling(int32_t h, int32_t w, int32_t *strip_w, int32_t *seg_h) {
+    if (!valid_dims(1, h, w) || !strip_w || !seg_h) return LLFE_ERR_INVALID;
+    int strips, segs, rows;
+    font_bits_tiling(h, w, &strips, &segs, &rows);
+    *strip_w = font_bits_strip_width();
+    *seg_h = rows;
     return LLFE_OK;
 }
 

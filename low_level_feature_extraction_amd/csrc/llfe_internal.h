@@ -146,7 +146,17 @@ hipError_t launch_font_select(const CtComp *comps, const int2 *refs, const int *
                               llfe_font_result *rec, hipStream_t s);
 hipError_t launch_font_regions(const CtComp *comps, const int2 *refs, const int *img_info, int n,
                                const llfe_font_result *rec, int4 *regions, int64_t cap, hipStream_t s);
-hipError_t launch_font_gray_sum(const uint8_t *bgr, int n, int h, int w, llfe_font_result *rec, hipStream_t s);
+// img_tab (device, may be null): image i at img_tab[i] instead of bgr + i * h * w * 3
+hipError_t launch_font_gray_sum(const uint8_t *bgr, int n, int h, int w, llfe_font_result *rec, hipStream_t s,
+                                const uint64_t *img_tab = nullptr);
+// BGR straight to the font bit rows (font_bits.hip): what launch_font_pack(launch_font_binary(bgr))
+// gives, in one row-streaming pass; a wave owns font_bits_strip_width() columns (whole output
+// words) and one of the `segs` row segments of `seg_rows` rows that font_bits_tiling reports.
+// img_tab as above.
+hipError_t launch_font_bits(const uint8_t *bgr, const uint64_t *img_tab, int n, int h, int w, uint64_t *bits,
+                            hipStream_t s);
+void font_bits_tiling(int h, int w, int *strips, int *segs, int *seg_rows);
+int font_bits_strip_width();
 
 inline int words_per_row(int w) { return (w + 63) / 64; }
 inline int tiles_x(int w) { return (w + kTileW - 1) / kTileW; }

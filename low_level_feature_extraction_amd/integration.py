@@ -14,6 +14,9 @@ from __future__ import annotations
 from typing import Callable, Dict, List, Mapping, Optional, Sequence, Union
 
 HOT_PATH = ("colors", "shapes", "shadows")
+# features the batcher computes only when it was made with them (MicroBatcher(features=...));
+# otherwise they come from ``extra`` as before
+BATCHABLE = ("fonts",)
 
 
 def _name(f) -> str:
@@ -33,6 +36,8 @@ def feature_results(features: Sequence, batched: Union[Mapping, BaseException, N
             out.append(batched)
         elif name in HOT_PATH and batched is not None and name in batched:
             out.append(batched[name])
+        elif name in BATCHABLE and isinstance(batched, Mapping) and name in batched:
+            out.append(batched[name])  # (a batcher bound with this feature computed it)
         elif extra and name in extra:
             try:
                 out.append(extra[name]())
@@ -49,7 +54,7 @@ async def analyze_features(image, features: Sequence, batcher,
     shared GPU launch), the others through ``extra``; positionally aligned."""
     want = [_name(f) for f in features]
     batched: Union[Mapping, BaseException, None] = None
-    if any(n in HOT_PATH for n in want):
+    if any(n in HOT_PATH or n in getattr(batcher, "features", ()) for n in want):
         try:
             batched = await batcher.analyze(image)
         except Exception as e:

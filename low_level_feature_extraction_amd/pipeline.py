@@ -8,6 +8,7 @@ per-image calls return:
 * ``shapes``  -> {"shapes", "total_shapes", "metadata"}  (ShapeAnalyzer.analyze_shapes @L184-189)
 * ``shadows`` -> {"shadow_level": "Low" | "Moderate" | "High"}  (analyze_shadow_level
   @L21-31; wrapped in a dict because UnifiedAnalysisResponse rejects a bare str)
+* ``fonts``   -> FontFeatures or None  (FontDetector.detect_font, font_detector.py:109-155)
 """
 from __future__ import annotations
 
@@ -46,7 +47,18 @@ def _shadows_result(r):
     return {"shadow_level": lv if lv is not None else shadow_level(r.shadow_sum, r.shadow_count)}
 
 
-_MAKERS = {"colors": _colors_result, "shapes": shapes_result, "shadows": _shadows_result}
+def _fonts_result(r):
+    """FontDetector.detect_font's result from the record: FontFeatures, or None when the image
+    has no text region (as detect_font returns)."""
+    from .font_detector import FontDetector
+
+    rec = getattr(r, "font", None)
+    if rec is None:
+        raise ValueError("fonts were not computed for this record")
+    return FontDetector._from_record(rec)
+
+
+_MAKERS = {"colors": _colors_result, "shapes": shapes_result, "shadows": _shadows_result, "fonts": _fonts_result}
 
 
 def assemble(r, features: Iterable[str]) -> dict:
