@@ -448,6 +448,57 @@ int llfe_decode_batch(const uint8_t *const *data, const uint64_t *sizes, int32_t
  * (NUL-terminated into buf; LLFE_ERR_CAPACITY if cap is too small) */
 int llfe_decoder_info(char *buf, int32_t cap);
 
+/* ---- JPEG decode split in two (the same cv2.imdecode(buf, IMREAD_COLOR) at utils.py:108-109
+ * and image_processor.py:208-211): the host does the entropy half (libjpeg-turbo's
+ * jpeg_read_coefficients), the device the reconstruction -- dequantisation, ISLOW inverse
+ * DCT, fancy chroma upsampling, YCbCr -> BGR -- bit for bit what llfe_decode_batch writes.
+ * Opt-in; llfe_decode_batch is unchanged.
+ *
+ * A batch of one image size is staged in slots of one stride.  Image i's slot holds its
+ * components' 64 x u16 quantisation tables (natural order) and their quantised
+ * coefficients: blocks_h rows of blocks_w blocks, a block 64 x int16 in natural order.
+ * llfe_jpeg_desc says where (byte offsets inside the slot). */
+#define LLFE_JPEG_GRAY 1 /* one component, replicated to B, G, R */
+#define LLFE_JPEG_444 2  /* YCbCr, luma sampled 1x1 */
+#define LLFE_JPEG_422 3  /* luma 2x1: chroma at half width (h2v1 fancy upsampling) */
+#define LLFE_JPEG_420 4  /* luma 2x2: chroma at half width and height (h2v2 fancy upsampling) */
+typedef struct {
+    int32_t n_comp;   /* 1 or 3; 0: nothing staged (the image was not eligible), reconstruction skips it */
+    int32_t sampling; /* LLFE_JPEG_* */
+    struct {
+        int32_t blocks_w, blocks_h; /* width_in_blocks, height_in_blocks */
+        int32_t width, height;      /* downsampled_width, downsampled_height: the component's real samples */
+        int64_t coef_offset;        /* blocks_h * blocks_w * 128 bytes, 16-byte aligned */
+        int64_t quant_offset;       /* 128 bytes, 16-byte aligned */
+    } comp[3];
+} llfe_jpeg_desc; /* 104 bytes */
+/* host only: bytes of a slot that holds any eligible height x width image (4:4:4, the
+ * worst case; a multiple of 128); LLFE_ERR_INVALID for sizes outside 1..65535 */
+int64_t llfe_jpeg_coef_slot_bytes(int32_t height, int32_t width);
+/* host only, no ctx: entropy-decode n JPEGs of one size on `threads` host threads into
+ * slots (host, n x slot_stride bytes) and descs[n].  slot_stride = llfe_jpeg_coef_slot_bytes
+ * holds every eligible image; with a smaller one (a 4:2:0 feed needs half) an image that
+ * does not fit is LLFE_ERR_UNSUPPORTED like any other this path hands back.
+ * status[i] per image; returns the first non-OK status, like llfe_decode_batch.  Eligible:
+ * 8-bit, greyscale or YCbCr with chroma 1x1 and luma 1x1 / 2x1 / 2x2, EXIF orientation 1,
+ * no libjpeg warning (a truncated scan is one), every progressive scan present; baseline,
+ * progressive, optimised-Huffman, restart-interval and arithmetic files alike.  Anything
+ * else (other formats included) is LLFE_ERR_UNSUPPORTED, or when this libjpeg lacks
+ * jpeg_read_coefficients: decode it with llfe_decode_batch.  Corrupt data is
+ * LLFE_ERR_INVALID, another size LLFE_ERR_CAPACITY.  A non-OK image's slot is not written
+ * and its descs[i].n_comp is 0. */
+int llfe_jpeg_read_coefs_batch(const uint8_t *const *data, const uint64_t *sizes, int32_t n, int32_t height,
+                               int32_t width, uint8_t *slots, int64_t slot_stride, llfe_jpeg_desc *descs,
+                               int32_t *status, int32_t threads);
+/* the device half: coefs (device, n x slot_stride bytes, 16-byte aligned, as staged above)
+ * -> out_bgr (device, n x h x w x 3 u8).  descs is a host array and is validated on the
+ * host before anything is launched: every offset and extent inside the slot, the block
+ * grids covering h x w at the sampling class; a bad descriptor is LLFE_ERR_INVALID with
+ * out_bgr untouched.  Images with n_comp == 0 are left as they are in out_bgr (the caller
+ * fills them from llfe_decode_batch).  Runs on `stream` and returns when it has finished. */
+int llfe_jpeg_reconstruct(llfe_ctx *ctx, const uint8_t *coefs, int64_t slot_stride, const llfe_jpeg_desc *descs,
+                          int32_t n, int32_t h, int32_t w, uint8_t *out_bgr, llfe_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -132,6 +132,27 @@ class LlfeFontResult(C.Structure):
     ]
 
 
+class LlfeJpegComp(C.Structure):
+    _fields_ = [
+        ("blocks_w", C.c_int32),
+        ("blocks_h", C.c_int32),
+        ("width", C.c_int32),
+        ("height", C.c_int32),
+        ("coef_offset", C.c_int64),
+        ("quant_offset", C.c_int64),
+    ]
+
+
+class LlfeJpegDesc(C.Structure):
+    _fields_ = [
+        ("n_comp", C.c_int32),
+        ("sampling", C.c_int32),
+        ("comp", LlfeJpegComp * 3),
+    ]
+
+
+JPEG_GRAY, JPEG_444, JPEG_422, JPEG_420 = 1, 2, 3, 4  # LLFE_JPEG_*
+
 # every symbol declared in include/llfe.h, with its ctypes signature
 _vp, _i32, _i64, _u32, _u64 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_uint64
 SIGNATURES = {
@@ -196,6 +217,9 @@ SIGNATURES = {
     "llfe_image_info": (C.c_int, [_vp, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "llfe_decode_batch": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32]),
     "llfe_decoder_info": (C.c_int, [C.c_char_p, _i32]),
+    "llfe_jpeg_coef_slot_bytes": (C.c_int64, [_i32, _i32]),
+    "llfe_jpeg_read_coefs_batch": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _i64, C.POINTER(LlfeJpegDesc), _vp, _i32]),
+    "llfe_jpeg_reconstruct": (C.c_int, [_vp, _vp, _i64, C.POINTER(LlfeJpegDesc), _i32, _i32, _i32, _vp, _vp]),
 }
 
 _lib = None

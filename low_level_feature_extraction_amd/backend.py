@@ -531,6 +531,28 @@ class Backend:
         self._call("llfe_font_bits", x.data_ptr(), out.data_ptr(), n, h, w, self._stream(x))
         return out
 
+    def jpeg_reconstruct(self, coefs, descs, h: int, w: int, out=None):
+        """The device half of a JPEG decode (llfe_jpeg_reconstruct): ``coefs`` an n x slot_stride
+        uint8 device tensor of staged coefficients, ``descs`` the n llfe_jpeg_desc records
+        (decode.stage_coefs) -> n x h x w x 3 BGR uint8 on the device, on the current stream.
+        Images whose descriptor has n_comp == 0 are left untouched in ``out``.  A descriptor
+        that points outside its slot raises LlfeError (LLFE_ERR_INVALID) before any launch."""
+        torch = _torch()
+        if not (_is_torch(coefs) and coefs.is_cuda and coefs.dtype == torch.uint8 and coefs.dim() == 2 and
+                coefs.is_contiguous()):
+            raise ValueError("jpeg_reconstruct: coefs must be a contiguous n x slot_stride uint8 device tensor")
+        n, stride = coefs.shape
+        if len(descs) != n:
+            raise ValueError(f"jpeg_reconstruct: {len(descs)} descriptors for {n} slots")
+        if out is None:
+            out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=coefs.device)
+        if tuple(out.shape) != (n, h, w, 3) or out.dtype != torch.uint8 or not out.is_contiguous() or \
+                out.device != coefs.device:
+            raise ValueError(f"jpeg_reconstruct: out must be a contiguous {(n, h, w, 3)} uint8 tensor on {coefs.device}")
+        self._call("llfe_jpeg_reconstruct", coefs.data_ptr(), stride, descs, n, int(h), int(w), out.data_ptr(),
+                   self._stream(coefs))
+        return out
+
     def font_detect(self, images, binary=None, regions=False) -> list:
         """FontDetector.detect_font's pixel work on the GPU (llfe_font_detect): per image
         the external contours of the font binary (or of ``binary``, n x h x w, nonzero =

@@ -16,12 +16,21 @@
 // images (OpenCV converts those with its own CMYK formula) and images with an EXIF
 // orientation other than 1 (imdecode applies the rotation; decode.py does it with
 // Pillow's exif_transpose).  Corrupt data that libjpeg rejects is LLFE_ERR_INVALID.
+//
+// The second entry point, llfe_jpeg_read_coefs_batch, stops the same decode after its entropy
+// half (jpeg_read_coefficients) and copies the quantised coefficients and quantisation tables
+// out for the device reconstruction (jpeg_recon.hip); it takes fewer files than the decoder
+// above (no libjpeg warning, complete progressive scans, 4:4:4 / 4:2:2 / 4:2:0 / grey only)
+// and hands the rest back with LLFE_ERR_UNSUPPORTED.
 #include <dlfcn.h>
 #include <setjmp.h>
 
+#include <algorithm>
+#include <atomic>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <thread>
 #include <vector>
 
 #include "llfe.h"
@@ -108,6 +117,35 @@ struct Decompress {  // struct jpeg_decompress_struct, JPEG_LIB_VERSION 80
     void *master, *main, *coef, *post, *inputctl, *marker, *entropy, *idct, *upsample, *cconvert, *cquantize;
 };
 
+// ---- the coefficient path (llfe_jpeg_read_coefs_batch): what jpeg_read_coefficients hands out
+struct QuantTbl {  // JQUANT_TBL: natural (not zigzag) order
+    uint16_t quantval[64];
+    jboolean sent_table;
+};
+
+struct ComponentInfo {  // jpeg_component_info, JPEG_LIB_VERSION 80
+    int component_id, component_index, h_samp_factor, v_samp_factor, quant_tbl_no, dc_tbl_no, ac_tbl_no;
+    JDIMENSION width_in_blocks, height_in_blocks;
+    int DCT_h_scaled_size, DCT_v_scaled_size;
+    JDIMENSION downsampled_width, downsampled_height;
+    jboolean component_needed;
+    int MCU_width, MCU_height, MCU_blocks, MCU_sample_width, last_col_width, last_row_height;
+    QuantTbl *quant_table;
+    void *dct_table;
+};
+static_assert(sizeof(ComponentInfo) == 96, "jpeg_component_info of the v8 ABI on LP64");
+
+typedef int16_t (*BlockRow)[64];  // JBLOCKROW: a row of 64-coefficient blocks
+
+struct MemoryMgr {  // struct jpeg_memory_mgr: the method table in front of its limits
+    void *alloc_small, *alloc_large, *alloc_sarray, *alloc_barray, *request_virt_sarray, *request_virt_barray,
+        *realize_virt_arrays, *access_virt_sarray;
+    BlockRow *(*access_virt_barray)(void *cinfo, void *ptr, JDIMENSION start_row, JDIMENSION num_rows,
+                                    jboolean writable);
+    void *free_pool, *self_destruct;
+    long max_memory_to_use, max_alloc_chunk;
+};
+
 struct Api {
     ErrorMgr *(*std_error)(ErrorMgr *) = nullptr;
     void (*create)(Decompress *, int, size_t) = nullptr;
@@ -117,6 +155,7 @@ struct Api {
     jboolean (*start)(Decompress *) = nullptr;
     JDIMENSION (*read_scanlines)(Decompress *, uint8_t **, JDIMENSION) = nullptr;
     jboolean (*finish)(Decompress *) = nullptr;
+    void **(*read_coefficients)(Decompress *) = nullptr;  // -> jvirt_barray_ptr[num_components]
     bool ok = false;
     Api() {
         if (const char *off = getenv("LLFE_NO_LIBJPEG"); off && *off == '1') return;
@@ -132,6 +171,8 @@ struct Api {
         finish = (jboolean(*)(Decompress *))dlsym(h, "jpeg_finish_decompress");
         ok = std_error && create && destroy && mem_src && read_header && start && read_scanlines && finish;
         if (ok) ok = abi_matches();
+        // the coefficient path only: its absence leaves the decoder above as it is
+        read_coefficients = (void **(*)(Decompress *))dlsym(h, "jpeg_read_coefficients");
     }
     // jpeg_CreateDecompress rejects a JPEG_LIB_VERSION or struct size that differs from
     // the library's own (JERR_BAD_LIB_VERSION / JERR_BAD_STRUCT_SIZE): probed once, so a
@@ -281,6 +322,119 @@ int decode(const uint8_t *data, size_t size, int32_t h, int32_t w, uint8_t *out,
     return rc;
 }
 
+// ---- coefficients for the device reconstruction (jpeg_recon.hip)
+constexpr int64_t kQuantBytes = 3 * 128;  // three 64 x u16 tables lead the slot
+
+inline int64_t div_up(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+int64_t coef_slot_bytes(int32_t h, int32_t w) {  // 4:4:4: three components of ceil(h/8) x ceil(w/8) blocks
+    return kQuantBytes + 3 * div_up(h, 8) * div_up(w, 8) * 128;
+}
+
+// entropy-decode one image and copy its quantised coefficients and tables into `slot`.
+// Every eligibility check comes before the first byte is written.
+int read_coefs(const uint8_t *data, size_t size, int32_t h, int32_t w, uint8_t *slot, int64_t slot_bytes,
+               llfe_jpeg_desc *desc) {
+    const Api &A = api();
+    if (!A.ok || !A.read_coefficients) return LLFE_ERR_UNSUPPORTED;
+    if (size < 3 || data[0] != 0xFF || data[1] != 0xD8 || data[2] != 0xFF) return LLFE_ERR_UNSUPPORTED;
+    if (exif_orientation(data, size) != 1) return LLFE_ERR_UNSUPPORTED;
+    Decompress ci;
+    Err err;
+    memset(&ci, 0, sizeof ci);
+    ci.err = A.std_error(&err.mgr);
+    err.mgr.error_exit = on_error;
+    err.mgr.output_message = on_output;
+    err.code = 0;
+    if (setjmp(err.jb)) {
+        A.destroy(&ci);
+        return err.code;
+    }
+    A.create(&ci, kJpegLibVersion, sizeof(Decompress));
+    A.mem_src(&ci, data, (unsigned long)size);
+    A.read_header(&ci, 1);
+    const int nc = ci.num_components;
+    const ComponentInfo *comp = (const ComponentInfo *)ci.comp_info;
+    volatile int rc = LLFE_OK;
+    int sampling = 0;
+    if (ci.data_precision != 8 || !comp ||
+        !((nc == 1 && ci.jpeg_color_space == JCS_GRAYSCALE) || (nc == 3 && ci.jpeg_color_space == JCS_YCbCr))) {
+        rc = LLFE_ERR_UNSUPPORTED;
+    } else if ((int32_t)ci.image_width != w || (int32_t)ci.image_height != h) {
+        rc = LLFE_ERR_CAPACITY;
+    } else if (nc == 1) {
+        sampling = LLFE_JPEG_GRAY;
+    } else {
+        const int hs = comp[0].h_samp_factor, vs = comp[0].v_samp_factor;
+        const bool chroma11 = comp[1].h_samp_factor == 1 && comp[1].v_samp_factor == 1 &&
+                              comp[2].h_samp_factor == 1 && comp[2].v_samp_factor == 1;
+        sampling = !chroma11 ? 0 : hs == 1 && vs == 1 ? LLFE_JPEG_444 : hs == 2 && vs == 1 ? LLFE_JPEG_422 :
+                   hs == 2 && vs == 2 ? LLFE_JPEG_420 : 0;
+        if (!sampling) rc = LLFE_ERR_UNSUPPORTED;
+    }
+    void **arrays = nullptr;
+    if (rc == LLFE_OK) {
+        arrays = A.read_coefficients(&ci);  // every scan: the entropy half of the decode
+        if (!arrays) rc = LLFE_ERR_INVALID;
+        // a warning (a truncated scan, say) makes the library patch the image up in ways the
+        // device pass does not restate
+        else if (err.mgr.num_warnings != 0) rc = LLFE_ERR_UNSUPPORTED;
+    }
+    // a progressive file that ends before its last refinement scan is smoothed between blocks
+    // by the decoder (do_block_smoothing): coef_bits holds the precision reached per coefficient
+    if (rc == LLFE_OK && ci.progressive_mode && ci.coef_bits) {
+        const int(*bits)[64] = (const int(*)[64])ci.coef_bits;
+        for (int c = 0; c < nc; c++)
+            for (int k = 0; k < 64; k++)
+                if (bits[c][k] != 0) rc = LLFE_ERR_UNSUPPORTED;
+    }
+    llfe_jpeg_desc d;
+    memset(&d, 0, sizeof d);
+    if (rc == LLFE_OK) {
+        d.n_comp = nc;
+        d.sampling = sampling;
+        int64_t off = kQuantBytes;
+        for (int c = 0; c < nc && rc == LLFE_OK; c++) {
+            const ComponentInfo &k = comp[c];
+            const int hs = c ? (sampling == LLFE_JPEG_422 || sampling == LLFE_JPEG_420 ? 2 : 1) : 1;
+            const int vs = c ? (sampling == LLFE_JPEG_420 ? 2 : 1) : 1;
+            // the geometry the device pass assumes, checked against the library's own
+            if (!k.quant_table || (int64_t)k.downsampled_width != div_up(w, hs) ||
+                (int64_t)k.downsampled_height != div_up(h, vs) ||
+                (int64_t)k.width_in_blocks != div_up(k.downsampled_width, 8) ||
+                (int64_t)k.height_in_blocks != div_up(k.downsampled_height, 8)) {
+                rc = LLFE_ERR_UNSUPPORTED;
+                break;
+            }
+            d.comp[c].blocks_w = (int32_t)k.width_in_blocks;
+            d.comp[c].blocks_h = (int32_t)k.height_in_blocks;
+            d.comp[c].width = (int32_t)k.downsampled_width;
+            d.comp[c].height = (int32_t)k.downsampled_height;
+            d.comp[c].quant_offset = 128 * c;
+            d.comp[c].coef_offset = off;
+            off += (int64_t)k.width_in_blocks * k.height_in_blocks * 128;
+        }
+        // a caller may stage in slots smaller than the 4:4:4 worst case (a 4:2:0 feed needs half):
+        // what does not fit is handed back like any other image this path does not take
+        if (rc == LLFE_OK && off > slot_bytes) rc = LLFE_ERR_UNSUPPORTED;
+    }
+    if (rc == LLFE_OK) {
+        const MemoryMgr *mem = (const MemoryMgr *)ci.mem;
+        for (int c = 0; c < nc; c++) {
+            memcpy(slot + d.comp[c].quant_offset, comp[c].quant_table->quantval, 128);
+            uint8_t *dst = slot + d.comp[c].coef_offset;
+            const size_t row_bytes = (size_t)d.comp[c].blocks_w * 128;
+            for (int32_t by = 0; by < d.comp[c].blocks_h; by++) {  // the real blocks, not the MCU padding
+                BlockRow *rows = mem->access_virt_barray(&ci, arrays[c], (JDIMENSION)by, 1, 0);
+                memcpy(dst + (size_t)by * row_bytes, rows[0], row_bytes);
+            }
+        }
+        *desc = d;
+    }
+    A.destroy(&ci);
+    return rc;
+}
+
 }  // namespace llfe_jpeg
 
 // used by png_decode.cpp's format-dispatching batch decoder
@@ -294,4 +448,40 @@ int llfe_jpeg_decode_one(const uint8_t *data, size_t size, int32_t h, int32_t w,
     const int rc = llfe_jpeg::decode(data, size, h, w, out, rows);
     if (rows.capacity() > (1u << 16)) std::vector<uint8_t *>().swap(rows);
     return rc;
+}
+
+extern "C" int64_t llfe_jpeg_coef_slot_bytes(int32_t height, int32_t width) {
+    if (height <= 0 || width <= 0 || height > 65535 || width > 65535) return LLFE_ERR_INVALID;  // JPEG's own limit
+    return llfe_jpeg::coef_slot_bytes(height, width);
+}
+
+extern "C" int llfe_jpeg_read_coefs_batch(const uint8_t *const *data, const uint64_t *sizes, int32_t n, int32_t height,
+                                          int32_t width, uint8_t *slots, int64_t slot_stride, llfe_jpeg_desc *descs,
+                                          int32_t *status, int32_t threads) {
+    if (n < 0 || (n && (!data || !sizes || !slots || !descs || !status)) || height <= 0 || width <= 0 ||
+        height > 65535 || width > 65535 || slot_stride < 0)
+        return LLFE_ERR_INVALID;
+    const int nt = std::max(1, std::min<int>(threads > 0 ? threads : 1, n));
+    std::atomic<int> next{0};
+    auto work = [&]() {
+        for (int i; (i = next.fetch_add(1)) < n;) {
+            int rc;
+            memset(&descs[i], 0, sizeof descs[i]);  // n_comp 0: nothing staged for this image
+            try {
+                rc = data[i] ? llfe_jpeg::read_coefs(data[i], (size_t)sizes[i], height, width,
+                                                     slots + (size_t)i * (size_t)slot_stride, slot_stride, &descs[i])
+                             : LLFE_ERR_INVALID;
+            } catch (const std::bad_alloc &) {
+                rc = LLFE_ERR_OOM;
+            }
+            status[i] = rc;
+        }
+    };
+    std::vector<std::thread> th;
+    for (int t = 1; t < nt; t++) th.emplace_back(work);
+    work();
+    for (auto &t : th) t.join();
+    for (int i = 0; i < n; i++)
+        if (status[i]) return status[i];
+    return LLFE_OK;
 }

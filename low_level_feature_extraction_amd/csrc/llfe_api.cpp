@@ -471,6 +471,11 @@ struct llfe_ctx {
     // llfe_submit_images: per slot, the gather table (n source addresses, n row pitches)
     HostBuf<uint64_t> h_gather_s[kMaxSlots];
     DevBuf<uint64_t> d_gather_s[kMaxSlots];
+    // llfe_jpeg_reconstruct: the validated descriptors (pinned, then on the device) and the
+    // u8 component planes of one chunk of images between its two kernels
+    HostBuf<llfe_jpeg_desc> h_jpeg_desc;
+    DevBuf<llfe_jpeg_desc> d_jpeg_desc;
+    DevBuf<uint8_t> d_jpeg_planes;
     Work *km_last = nullptr;  // workspace of the last k-means launch (llfe_kmeans_attempts)
     // LLFE_FEATURE_FONTS: per slot the records and counters of the chunk's font pass, whether
     // that pass ran its contours on the GPU (else finish_chunk takes the host path) and the
@@ -1854,6 +1859,62 @@ int llfe_font_bits_images(llfe_ctx *ctx, const uint8_t *const *images, uint64_t 
     for (int i = 0; i < n; i++) ctx->h_gather_s[0].p[i] = (uint64_t)(uintptr_t)images[i];
     HIPCHK(ctx, hipMemcpyAsync(ctx->d_gather_s[0].p, ctx->h_gather_s[0].p, sizeof(uint64_t) * n, hipMemcpyHostToDevice, s));
     return font_bits_stage(ctx, images[0], ctx->d_gather_s[0].p, bits, n, h, w, s);
+}
+
+// The plane workspace is bounded: images go through it in chunks on the one stream (a chunk's
+// colour kernel is ordered before the next chunk's IDCT).  256 MiB is 86 1080p 4:2:0 images
+// (1.5 plane bytes per pixel), 4 M blocks of IDCT per launch.
+constexpr int64_t kJpegPlaneBudget = (int64_t)256 << 20;
+
+int llfe_jpeg_reconstruct(llfe_ctx *ctx, const uint8_t *coefs, int64_t slot_stride, const llfe_jpeg_desc *descs,
+                          int32_t n, int32_t h, int32_t w, uint8_t *out_bgr, llfe_stream stream) {
+    if (!ctx) return LLFE_ERR_INVALID;
+    if (!valid_dims(n, h, w) || h > 65535 || w > 65535 || (n && (!coefs || !descs || !out_bgr)) || slot_stride <= 0 ||
+        (slot_stride & 15) || ((uintptr_t)coefs & 15))
+        return ctx->fail(LLFE_ERR_INVALID, "llfe_jpeg_reconstruct: bad arguments (n=%d h=%d w=%d slot_stride=%lld)", n, h,
+                         w, (long long)slot_stride);
+    int64_t plane_stride = 0;
+    int max_blocks = 0;
+    // nothing is launched on a descriptor the host check has not passed
+    if (!validate_jpeg_descs(descs, n, h, w, slot_stride, &plane_stride, &max_blocks))
+        return ctx->fail(LLFE_ERR_INVALID, "llfe_jpeg_reconstruct: a descriptor points outside its slot or does not "
+                                           "cover %dx%d", w, h);
+    if (n == 0 || max_blocks == 0) return LLFE_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    int64_t budget = kJpegPlaneBudget;
+    if (const char *e = getenv("LLFE_JPEG_PLANE_BYTES"); e && atoll(e) > 0) budget = atoll(e);  // (tests: many chunks)
+    const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(n, budget / plane_stride));
+    HIPCHK(ctx, ctx->h_jpeg_desc.ensure((size_t)n));
+    HIPCHK(ctx, ctx->d_jpeg_desc.ensure((size_t)n));
+    HIPCHK(ctx, ctx->d_jpeg_planes.ensure((size_t)chunk * (size_t)plane_stride));
+    std::memcpy(ctx->h_jpeg_desc.p, descs, sizeof(llfe_jpeg_desc) * (size_t)n);
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_jpeg_desc.p, ctx->h_jpeg_desc.p, sizeof(llfe_jpeg_desc) * (size_t)n,
+                               hipMemcpyHostToDevice, s));
+    const int prev_slot = ctx->prof.cur_slot;
+    ctx->prof.cur_slot = Profiler::kStageSlot;
+    int rc = LLFE_OK;
+    for (int i0 = 0; i0 < n && rc == LLFE_OK; i0 += chunk) {
+        const int m = std::min(chunk, n - i0);
+        const uint8_t *cf = coefs + (size_t)i0 * (size_t)slot_stride;
+        uint8_t *o = out_bgr + (size_t)i0 * (size_t)h * w * 3;
+        const llfe_jpeg_desc *dd = ctx->d_jpeg_desc.p + i0;
+        rc = [&]() -> int {
+            // coefficients in (2 B each, at most 3 per pixel), planes out; planes in, BGR out
+            TIMED(ctx, s, "k_jpeg_idct", (double)m * plane_stride * 3,
+                  launch_jpeg_reconstruct(cf, slot_stride, dd, m, h, w, max_blocks, ctx->d_jpeg_planes.p, plane_stride, o,
+                                          s, 0));
+            TIMED(ctx, s, "k_jpeg_color", (double)m * (plane_stride + (double)h * w * 3),
+                  launch_jpeg_reconstruct(cf, slot_stride, dd, m, h, w, max_blocks, ctx->d_jpeg_planes.p, plane_stride, o,
+                                          s, 1));
+            return LLFE_OK;
+        }();
+    }
+    ctx->prof.cur_slot = prev_slot;
+    if (rc != LLFE_OK) return rc;
+    HIPCHK(ctx, hipStreamSynchronize(s));  // (the pinned descriptors and the planes are free again)
+    ctx->prof.collect(Profiler::kStageSlot);
+    return LLFE_OK;
 }
 
 int llfe_font_bits_tiling(int32_t h, int32_t w, int32_t *strip_w, int32_t *seg_h) {

@@ -10,6 +10,9 @@ csrc/png_decode.cpp, and csrc/jpeg_decode.cpp over the system libjpeg-turbo with
 OpenCV's settings), fanned out over native threads; what they hand back (interlaced
 PNG, CMYK JPEG, EXIF-rotated JPEG, other formats) is decoded with Pillow.  Images
 above ``MAX_PIXELS`` (cv2's CV_IO_MAX_IMAGE_PIXELS, 2^30) fail like cv2.imdecode does.
+
+``decode_batch_device`` (opt-in, at the end of this module) returns the same batch in device
+memory: for JPEG the host stops after the entropy half and csrc/jpeg_recon.hip reconstructs.
 """
 from __future__ import annotations
 
@@ -258,3 +261,181 @@ def decode_batch(blobs, out=None, workers=None) -> np.ndarray:
     if errs:
         raise DecodeError(errs[0])
     return out
+
+
+# ------------------------------------------------------- JPEG reconstruction on the device
+# The same decode split in two (DESIGN.md §3 "JPEG reconstruction on the device"): the host
+# stops after the entropy half (llfe_jpeg_read_coefs_batch: libjpeg-turbo's
+# jpeg_read_coefficients), the quantised coefficients cross PCIe, and llfe_jpeg_reconstruct
+# (csrc/jpeg_recon.hip) writes the BGR batch in device memory, bit for bit what decode_batch
+# writes on the host.  Opt-in: nothing above calls it.
+_STAGE_RING = 3  # staging buffers per (size, count): extraction of batch k + 1 beside batch k's copy
+_STAGE = {}
+_STAGE_LOCK = _threading.Lock()
+
+
+class StagedCoefs:
+    """One batch after its host half: ``slots`` (n x slot_stride uint8, pinned when a GPU is
+    present), ``descs`` (the llfe_jpeg_desc array), ``status`` per image, the blobs (for the
+    images handed back to the host decoders) and the batch geometry."""
+
+    def __init__(self, blobs, h, w, slots, descs, status, tensor=None):
+        self.blobs, self.h, self.w = blobs, h, w
+        self.slots, self.descs, self.status, self.tensor = slots, descs, status, tensor
+
+    @property
+    def used_bytes(self) -> int:
+        """Bytes from the start of a slot that any image of the batch occupies."""
+        end = 0
+        for d in self.descs:
+            for c in range(d.n_comp):
+                k = d.comp[c]
+                end = max(end, k.coef_offset + k.blocks_w * k.blocks_h * 128, k.quant_offset + 128)
+        return end
+
+
+def coef_slot_bytes(h: int, w: int) -> int:
+    """llfe_jpeg_coef_slot_bytes: the slot of any eligible h x w image (4:4:4 worst case)."""
+    from . import _lib
+
+    n = _lib.lib().llfe_jpeg_coef_slot_bytes(int(h), int(w))
+    if n < 0:
+        raise ValueError(f"no JPEG coefficient slot for {w}x{h}")
+    return int(n)
+
+
+def _read_coefs(blobs, h, w, slots, descs, threads) -> list:
+    """llfe_jpeg_read_coefs_batch over all blobs into slots[i] / descs[i]; -> status list."""
+    import ctypes as C
+
+    from . import _lib
+
+    n = len(blobs)
+    keep = [C.c_char_p(b) for b in blobs]
+    ptrs = (C.c_void_p * n)(*[C.cast(k, C.c_void_p) for k in keep])
+    sizes = (C.c_uint64 * n)(*[len(b) for b in blobs])
+    status = (C.c_int32 * n)()
+    _lib.lib().llfe_jpeg_read_coefs_batch(ptrs, sizes, n, h, w, slots.ctypes.data, slots.strides[0], descs, status,
+                                          int(threads))
+    del keep
+    return list(status)
+
+
+def _staging(n, stride):
+    """The next of _STAGE_RING staging buffers for n slots of `stride` bytes: (numpy view,
+    descriptor array, torch tensor or None).  Pinned when torch sees a GPU."""
+    from . import _lib
+
+    with _STAGE_LOCK:
+        ring = _STAGE.setdefault((n, stride), {"next": 0, "bufs": []})
+        if len(_STAGE) > 4:  # other batch shapes: drop their pinned memory
+            for k in [k for k in _STAGE if k != (n, stride)]:
+                del _STAGE[k]
+        if len(ring["bufs"]) < _STAGE_RING:  # (filled in order, then handed out round robin)
+            tensor = None
+            try:
+                import torch
+
+                if torch.cuda.is_available():
+                    tensor = torch.empty((n, stride), dtype=torch.uint8, pin_memory=True)
+            except ImportError:  # pragma: no cover - C-only deployments
+                pass
+            arr = tensor.numpy() if tensor is not None else np.empty((n, stride), np.uint8)
+            ring["bufs"].append((arr, (_lib.LlfeJpegDesc * n)(), tensor))
+        buf = ring["bufs"][ring["next"] % _STAGE_RING]
+        ring["next"] += 1
+        return buf
+
+
+def stage_coefs(blobs, workers=None, slot_bytes=None) -> StagedCoefs:
+    """The host half of decode_batch_device: entropy-decode every eligible JPEG of a batch of
+    equally sized images into the next staging buffer of a ring of three (so a producer thread
+    may stage batch k + 1 while batch k is copied and reconstructed).  Host only.
+    ``slot_bytes`` (a multiple of 16; default coef_slot_bytes(h, w), the 4:4:4 worst case)
+    sizes a slot: a feed known to be 4:2:0 needs half, and an image that does not fit is
+    handed back to the host decoders like any other."""
+    blobs = [bytes(b) for b in blobs]
+    if not blobs:
+        raise DecodeError("empty batch")
+    hw = _image_size(blobs[0])
+    if hw is None:
+        hw = decode_bgr(blobs[0]).shape[:2]
+    h, w = hw
+    if h > 65535 or w > 65535:  # beyond JPEG: nothing to stage, the host decoders take every image
+        return StagedCoefs(blobs, h, w, None, None, [-5] * len(blobs))
+    if slot_bytes is not None and (slot_bytes <= 0 or slot_bytes % 16):
+        raise ValueError("slot_bytes must be a positive multiple of 16")
+    slots, descs, tensor = _staging(len(blobs), slot_bytes or coef_slot_bytes(h, w))
+    status = _read_coefs(blobs, h, w, slots, descs, workers or default_decode_threads())
+    return StagedCoefs(blobs, h, w, slots, descs, status, tensor)
+
+
+def _host_fill(st: StagedCoefs, todo, workers):
+    """decode_batch's treatment of the images in `todo`: the native host decoders, Pillow for
+    what they leave; -> len(todo) x h x w x 3, or DecodeError naming the image."""
+    h, w = st.h, st.w
+    sub = [st.blobs[i] for i in todo]
+    out = np.empty((len(sub), h, w, 3), np.uint8)
+    rcs = _native(sub, h, w, out, workers or default_decode_threads())
+
+    def one(k):
+        i = todo[k]
+        try:
+            im = decode_bgr(sub[k])
+        except DecodeError:
+            return f"image {i}: Failed to decode image"
+        if im.shape[:2] != (h, w):
+            return f"image {i}: size {im.shape[1]}x{im.shape[0]} differs from {w}x{h}"
+        out[k] = im
+        return None
+
+    left = [k for k, rc in enumerate(rcs) if rc != 0]
+    errs = [e for e in _pool(workers).map(one, left) if e] if left else []
+    if errs:
+        raise DecodeError(errs[0])
+    return out
+
+
+def reconstruct_staged(st: StagedCoefs, device=0, workers=None, out=None):
+    """The device half: copy the staged coefficients across and reconstruct on the current
+    stream; images the coefficient path handed back are decoded on the host (as decode_batch
+    does) and copied into their places.  -> (N, H, W, 3) uint8 tensor on the device."""
+    import torch
+
+    from .backend import Backend
+
+    n, h, w = len(st.blobs), st.h, st.w
+    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+    if out is None:
+        out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
+    if tuple(out.shape) != (n, h, w, 3) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"out must be a contiguous {(n, h, w, 3)} uint8 tensor on {dev}")
+    todo = [i for i, rc in enumerate(st.status) if rc != 0]
+    if len(todo) < n:
+        with torch.cuda.device(dev):
+            used = st.used_bytes
+            stride = st.slots.shape[1]
+            host = st.tensor if st.tensor is not None else torch.from_numpy(st.slots)
+            d_slots = torch.empty((n, stride), dtype=torch.uint8, device=dev)
+            if 4 * used > 3 * stride:
+                d_slots.copy_(host, non_blocking=True)
+            else:  # subsampled batches fill about half of a 4:4:4 slot: copy what is there
+                for i, rc in enumerate(st.status):
+                    if rc == 0:
+                        d_slots[i, :used].copy_(host[i, :used], non_blocking=True)
+            Backend.get(dev.index).jpeg_reconstruct(d_slots, st.descs, h, w, out)
+    if todo:
+        fill = torch.from_numpy(_host_fill(st, todo, workers)).to(dev)
+        out[torch.tensor(todo, device=dev)] = fill
+    return out
+
+
+def decode_batch_device(blobs, device=0, workers=None, out=None):
+    """decode_batch with the reconstruction on the GPU: equally sized images -> one
+    (N, H, W, 3) BGR uint8 tensor on ``device``, the same bytes decode_batch returns.  Eligible
+    JPEGs (8-bit greyscale or YCbCr 4:4:4 / 4:2:2 / 4:2:0, EXIF orientation 1, no decoder
+    warning) are entropy-decoded on ``workers`` host threads and reconstructed by
+    csrc/jpeg_recon.hip; everything else (PNG, CMYK, EXIF-rotated, other samplings, truncated
+    files) goes through the host decoders image by image.  Raises DecodeError as decode_batch
+    does.  The result feeds Backend.process / submit unchanged."""
+    return reconstruct_staged(stage_coefs(blobs, workers), device, workers, out)
