@@ -132,7 +132,7 @@ typedef struct {
     double bytes;  /* algorithmic HBM bytes attributed to those launches */
 } llfe_kernel_stat;
 
-/* one k-means attempt of the last llfe_process_batch (diagnostics, llfe_kmeans_attempts):
+/* one k-means attempt of the last k-means launch (diagnostics, llfe_kmeans_attempts):
  * cv2.kmeans' attempt a (color_extractor.py:192-196) -- its k-means++ centres, the centres
  * and cluster sizes after Lloyd, the Lloyd iterations and the compactness */
 typedef struct {
@@ -358,8 +358,10 @@ int llfe_kmeans(llfe_ctx *ctx, const uint32_t *keys, int64_t key_stride, const i
  * llfe_process_batch fills them (the other fields of r are left as they are). */
 int llfe_palette_rules(const uint8_t *centers_rgb, const int32_t *counts, int32_t k, llfe_image_result *r);
 /* Diagnostics: the 10 attempt records (llfe_kmeans_attempt) of each of the first n images
- * of the last chunk of the last llfe_process_batch on this context (n <= its size), for
- * n_colors <= 5 (the cube-table k-means), into out[n * 10] (host).  Replaces nothing in the
+ * of the last k-means launch on this context (n <= its size): the last chunk of
+ * llfe_process_batch / llfe_process_images, an llfe_kmeans call, or the ticket submitted
+ * last (LLFE_ERR_INVALID until every ticket is collected), for n_colors <= 5 (k_kmeans, with
+ * or without cube tables), into out[n * 10] (host).  Replaces nothing in the
  * reference: cv2.kmeans only returns the best attempt (color_extractor.py:194). */
 int llfe_kmeans_attempts(llfe_ctx *ctx, int32_t n, llfe_kmeans_attempt *out);
 /* Pillow Image.resize(size, LANCZOS, box) on u8 HWC (image_processor.py:221-224).

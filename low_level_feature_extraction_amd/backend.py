@@ -736,8 +736,11 @@ class Backend:
 
     def kmeans_attempts(self, n):
         """Diagnostics (llfe_kmeans_attempts): the 10 k-means attempts of each of the first n
-        images of the last process() chunk -> list of n lists of dicts (pp_centers, centers
-        float32 K x 3 before the uint8 truncation, counts, iters, compactness)."""
+        images of the last k-means launch on this context -- the last chunk of process() /
+        process_images(), a kmeans() call on caller keys, or the ticket submit() / submit_images()
+        issued last (refused until every ticket is collected) -- for n_colors <= 5
+        -> list of n lists of dicts (pp_centers, centers float32 5 x 3 before the uint8
+        truncation, counts, iters, compactness; rows past K unused)."""
         out = (L.LlfeKmeansAttempt * max(n * 10, 1))()
         self._call("llfe_kmeans_attempts", n, out)
         recs = []
