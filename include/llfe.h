@@ -257,7 +257,7 @@ int llfe_batch_capacity(int32_t h, int32_t w);
 
 /* ---- stage entry points (parity tests; device in/out unless noted) ------
  * The ones that use the context's workspace (llfe_shape_mask, llfe_canny,
- * llfe_shadow_stats, llfe_color_unique, llfe_kmeans, llfe_find_contours_gpu,
+ * llfe_hysteresis, llfe_shadow_stats, llfe_color_unique, llfe_kmeans, llfe_find_contours_gpu,
  * llfe_shapes_from_masks_gpu, llfe_font_detect, llfe_font_bits) and llfe_process_images return LLFE_ERR_INVALID while a
  * batch submitted with llfe_submit_batch is not yet collected. */
 /* gray = cvtColor(BGR2GRAY); out = GaussianBlur(gray, (5,5), 0)
@@ -270,6 +270,16 @@ int llfe_shape_mask(llfe_ctx *ctx, const uint8_t *bgr, uint8_t *mask, int32_t n,
 /* Canny(blur5(gray), 50, 150) as 0/255 u8: the shape mask before its dilation */
 int llfe_canny(llfe_ctx *ctx, const uint8_t *bgr, uint8_t *edges, int32_t n, int32_t h, int32_t w,
                llfe_stream stream);
+/* The hysteresis of llfe_canny / llfe_shape_mask on the caller's class maps (the
+ * counterpart of llfe_find_contours_gpu, which takes host masks).  classes: HOST n x h x w
+ * bytes, each 0 (weak), 1 (none) or 2 (strong); any other byte is LLFE_ERR_INVALID, found
+ * by a host scan before any launch.  edges (what llfe_canny gives after its stencil) and
+ * mask (edges dilated 3x3, what llfe_shape_mask gives) are HOST n x h x w buffers of
+ * 0/255; either may be null, not both.  tile_flags == 0: every 64 x 64 tile is listed;
+ * != 0: only the tiles holding a byte != 1, through the flag bytes the stencil would have
+ * written.  n above llfe_batch_capacity(h, w) is LLFE_ERR_UNSUPPORTED. */
+int llfe_hysteresis(llfe_ctx *ctx, const uint8_t *classes, int32_t n, int32_t h, int32_t w, int32_t tile_flags,
+                    uint8_t *edges, uint8_t *mask);
 /* dilate(src, ones(3,3)) of n h x w u8 images (any values; out-of-image never wins);
  * src and dst must not alias */
 int llfe_dilate3(llfe_ctx *ctx, const uint8_t *src, uint8_t *dst, int32_t n, int32_t h, int32_t w,

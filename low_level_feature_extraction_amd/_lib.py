@@ -181,6 +181,7 @@ SIGNATURES = {
     "llfe_shape_mask": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "llfe_edge_classes": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "llfe_canny": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "llfe_hysteresis": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "llfe_dilate3": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "llfe_font_binary": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "llfe_font_detect": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _i64, C.POINTER(C.c_int64), _vp]),

@@ -637,6 +637,20 @@ class Backend:
         self._call("llfe_canny", x.data_ptr(), out.data_ptr(), n, h, w, self._stream(x))
         return out
 
+    def hysteresis(self, classes, tile_flags=True):
+        """The hysteresis of canny / shape_mask on caller class maps: an n x h x w (or
+        h x w) host u8 array of 0 (weak) / 1 (none) / 2 (strong) -> (edges, mask) as
+        n x h x w 0/255 numpy arrays, mask = edges dilated 3 x 3.  ``tile_flags``: list
+        only the 64 x 64 tiles with a candidate (as after the stencil) or every tile."""
+        c = np.ascontiguousarray(classes, np.uint8)
+        if c.ndim == 2:
+            c = c[None]
+        n, h, w = c.shape
+        edges, mask = np.empty_like(c), np.empty_like(c)
+        self._call("llfe_hysteresis", c.ctypes.data, n, h, w, 1 if tile_flags else 0, edges.ctypes.data,
+                   mask.ctypes.data)
+        return edges, mask
+
     def dilate3(self, masks):
         """dilate(masks, ones(3, 3)) of an n x h x w (or h x w) u8 batch on the GPU."""
         torch = _torch()

@@ -2023,6 +2023,57 @@ int llfe_canny(llfe_ctx *ctx, const uint8_t *bgr, uint8_t *edges, int32_t n, int
     return LLFE_OK;
 }
 
+// The hysteresis of llfe_canny / llfe_shape_mask on a caller's class maps (host in / out,
+// workspace 0, synchronous).  The kernels' 16-byte and bytewise row readers agree only on
+// bytes 0 / 1 / 2 and k_ccl_border takes every byte != 1 for a labelled candidate, so any
+// other byte is refused here, before a launch.
+int llfe_hysteresis(llfe_ctx *ctx, const uint8_t *classes, int32_t n, int32_t h, int32_t w, int32_t tile_flags,
+                    uint8_t *edges, uint8_t *mask) {
+    if (!ctx || !valid_dims(n, h, w) || !classes || (!edges && !mask)) return LLFE_ERR_INVALID;
+    if (int rc_ = stage_enter(ctx, __func__)) return rc_;
+    const int cmax = chunk_for(h, w);
+    if (n > cmax) return ctx->fail(LLFE_ERR_UNSUPPORTED, "llfe_hysteresis: n > %d", cmax);
+    const size_t P = (size_t)h * w, total = (size_t)n * P;
+    const int ntx = (w + 63) >> 6, nty = (h + 63) >> 6;
+    // the per-tile flag bytes in the stencil's layout: set where the tile holds a candidate
+    std::vector<uint8_t> tflag(tile_flags ? (size_t)n * nty * ntx : 0, 0);
+    for (size_t i = 0; i < total; i++) {
+        const uint8_t b = classes[i];
+        if (b > 2) return ctx->fail(LLFE_ERR_INVALID, "llfe_hysteresis: class byte %d at %zu (0, 1 or 2)", b, i);
+        if (b != 1 && tile_flags) {
+            const size_t img = i / P, y = (i % P) / w, x = i % w;
+            tflag[img * nty * ntx + (y >> 6) * ntx + (x >> 6)] = 1;
+        }
+    }
+    if (!n) return LLFE_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipDeviceSynchronize());
+    Work &W = ctx->ws[0];
+    hipStream_t s = ctx->streams[0];
+    HIPCHK(ctx, W.d_cls.ensure(total));
+    HIPCHK(ctx, W.d_in.ensure(total));  // the 0 / 255 output of either pass
+    HIPCHK(ctx, hipMemcpyAsync(W.d_cls.p, classes, total, hipMemcpyHostToDevice, s));
+    if (tile_flags) {
+        HIPCHK(ctx, W.d_tflag.ensure(tflag.size()));
+        HIPCHK(ctx, hipMemcpyAsync(W.d_tflag.p, tflag.data(), tflag.size(), hipMemcpyHostToDevice, s));
+    }
+    for (int pass = 0; pass < 2; pass++) {
+        uint8_t *out = pass ? mask : edges;
+        if (!out) continue;
+        W.tflag_valid = tile_flags != 0;  // (hyst_work takes the flags for one pass)
+        HystWork wk;
+        const int rc = hyst_work(ctx, W, n, h, w, &wk);
+        if (rc) return rc;
+        if (pass)
+            HIPCHK(ctx, launch_hysteresis_dilate(W.d_cls.p, n, h, w, wk, nullptr, W.d_in.p, s));
+        else
+            HIPCHK(ctx, launch_canny_edges(W.d_cls.p, n, h, w, wk, W.d_in.p, s));
+        HIPCHK(ctx, hipMemcpyAsync(out, W.d_in.p, total, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipStreamSynchronize(s));
+    }
+    return LLFE_OK;
+}
+
 // dilate(src, ones(3, 3)) of the shapes path (shape pyc @L6-30) on n u8 images
 int llfe_dilate3(llfe_ctx *ctx, const uint8_t *src, uint8_t *dst, int32_t n, int32_t h, int32_t w,
                  llfe_stream stream) {

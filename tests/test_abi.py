@@ -119,6 +119,11 @@ def test_invalid_arguments_rejected():
     assert lib.llfe_thumbnail_size(10, 10, 0, 1080, C.byref(ow), C.byref(oh)) < 0
     assert lib.llfe_find_contours(None, 4, 4, None, 0, None, 0, None) < 0
     assert lib.llfe_classify_contour(None, 3, None) < 0
+    # a null ctx (the byte and null-output rejections need a context:
+    # test_gpu_hysteresis_classes.py)
+    cls = np.ones((4, 4), np.uint8)
+    out = np.empty_like(cls)
+    assert lib.llfe_hysteresis(None, cls.ctypes.data, 1, 4, 4, 0, out.ctypes.data, None) == L.LLFE_ERR_INVALID
 
 
 @pytest.mark.parametrize("wh", [(3840, 2160), (2000, 1125), (3000, 2001), (1000, 4000), (1920, 1080), (7680, 4320),
