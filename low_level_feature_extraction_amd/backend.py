@@ -553,6 +553,28 @@ class Backend:
                    self._stream(coefs))
         return out
 
+    def jpeg_entropy_decode(self, records, scans, descs, h: int, w: int, slots) -> list:
+        """The entropy half of a JPEG decode on the device (llfe_jpeg_entropy_decode): ``records``
+        an n x record_stride uint8 device tensor of staged records, ``scans`` / ``descs`` the n
+        llfe_jpeg_scan / llfe_jpeg_desc records (decode.stage_bytes), ``slots`` an
+        n x slot_stride uint8 device tensor that receives quantisation tables and coefficients
+        as decode.stage_coefs lays them out, on the current stream.  -> the per-image status
+        list: 0 for a slot that is ready for jpeg_reconstruct, LLFE_ERR_UNSUPPORTED for an image
+        that was not staged or whose scan showed an anomaly (decode it another way).  A record
+        or descriptor that points outside its buffer raises LlfeError (LLFE_ERR_INVALID) before
+        any launch."""
+        torch = _torch()
+        for name, t in (("records", records), ("slots", slots)):
+            if not (_is_torch(t) and t.is_cuda and t.dtype == torch.uint8 and t.dim() == 2 and t.is_contiguous()):
+                raise ValueError(f"jpeg_entropy_decode: {name} must be a contiguous 2-d uint8 device tensor")
+        n, stride = slots.shape
+        if records.shape[0] != n or len(scans) != n or len(descs) != n or records.device != slots.device:
+            raise ValueError(f"jpeg_entropy_decode: records, scans and descriptors for {n} slots on one device")
+        status = (C.c_int32 * n)()
+        self._call("llfe_jpeg_entropy_decode", records.data_ptr(), records.numel(), scans, descs, n, int(h), int(w),
+                   slots.data_ptr(), stride, status, self._stream(slots))
+        return list(status)
+
     def font_detect(self, images, binary=None, regions=False) -> list:
         """FontDetector.detect_font's pixel work on the GPU (llfe_font_detect): per image
         the external contours of the font binary (or of ``binary``, n x h x w, nonzero =

@@ -33,6 +33,8 @@
 #include <thread>
 #include <vector>
 
+#include "jpeg_desc_check.h"
+#include "jpeg_huff_core.h"
 #include "llfe.h"
 
 namespace llfe_jpeg {
@@ -331,6 +333,57 @@ int64_t coef_slot_bytes(int32_t h, int32_t w) {  // 4:4:4: three components of c
     return kQuantBytes + 3 * div_up(h, 8) * div_up(w, 8) * 128;
 }
 
+// what both staging paths take, decided from libjpeg's own header parse: 8-bit, greyscale or
+// YCbCr with chroma 1x1 and luma 1x1 / 2x1 / 2x2, of the batch's size
+int classify(const Decompress &ci, const ComponentInfo *comp, int32_t h, int32_t w, int *sampling) {
+    const int nc = ci.num_components;
+    if (ci.data_precision != 8 || !comp ||
+        !((nc == 1 && ci.jpeg_color_space == JCS_GRAYSCALE) || (nc == 3 && ci.jpeg_color_space == JCS_YCbCr)))
+        return LLFE_ERR_UNSUPPORTED;
+    if ((int32_t)ci.image_width != w || (int32_t)ci.image_height != h) return LLFE_ERR_CAPACITY;
+    if (nc == 1) {
+        *sampling = LLFE_JPEG_GRAY;
+        return LLFE_OK;
+    }
+    const int hs = comp[0].h_samp_factor, vs = comp[0].v_samp_factor;
+    const bool chroma11 = comp[1].h_samp_factor == 1 && comp[1].v_samp_factor == 1 &&
+                          comp[2].h_samp_factor == 1 && comp[2].v_samp_factor == 1;
+    *sampling = !chroma11 ? 0 : hs == 1 && vs == 1 ? LLFE_JPEG_444 : hs == 2 && vs == 1 ? LLFE_JPEG_422 :
+                hs == 2 && vs == 2 ? LLFE_JPEG_420 : 0;
+    return *sampling ? LLFE_OK : LLFE_ERR_UNSUPPORTED;
+}
+
+// the descriptor of an eligible image: block grids and slot offsets.  need_qt: the components'
+// quant_table pointers are set (they are once a scan has started).
+int geometry(const ComponentInfo *comp, int nc, int sampling, int32_t h, int32_t w, int64_t slot_bytes, bool need_qt,
+             llfe_jpeg_desc *out) {
+    llfe_jpeg_desc &d = *out;
+    d.n_comp = nc;
+    d.sampling = sampling;
+    int64_t off = kQuantBytes;
+    for (int c = 0; c < nc; c++) {
+        const ComponentInfo &k = comp[c];
+        const int hs = c ? (sampling == LLFE_JPEG_422 || sampling == LLFE_JPEG_420 ? 2 : 1) : 1;
+        const int vs = c ? (sampling == LLFE_JPEG_420 ? 2 : 1) : 1;
+        // the geometry the device pass assumes, checked against the library's own
+        if ((need_qt && !k.quant_table) || (int64_t)k.downsampled_width != div_up(w, hs) ||
+            (int64_t)k.downsampled_height != div_up(h, vs) ||
+            (int64_t)k.width_in_blocks != div_up(k.downsampled_width, 8) ||
+            (int64_t)k.height_in_blocks != div_up(k.downsampled_height, 8))
+            return LLFE_ERR_UNSUPPORTED;
+        d.comp[c].blocks_w = (int32_t)k.width_in_blocks;
+        d.comp[c].blocks_h = (int32_t)k.height_in_blocks;
+        d.comp[c].width = (int32_t)k.downsampled_width;
+        d.comp[c].height = (int32_t)k.downsampled_height;
+        d.comp[c].quant_offset = 128 * c;
+        d.comp[c].coef_offset = off;
+        off += (int64_t)k.width_in_blocks * k.height_in_blocks * 128;
+    }
+    // a caller may stage in slots smaller than the 4:4:4 worst case (a 4:2:0 feed needs half):
+    // what does not fit is handed back like any other image this path does not take
+    return off > slot_bytes ? LLFE_ERR_UNSUPPORTED : LLFE_OK;
+}
+
 // entropy-decode one image and copy its quantised coefficients and tables into `slot`.
 // Every eligibility check comes before the first byte is written.
 int read_coefs(const uint8_t *data, size_t size, int32_t h, int32_t w, uint8_t *slot, int64_t slot_bytes,
@@ -355,23 +408,8 @@ int read_coefs(const uint8_t *data, size_t size, int32_t h, int32_t w, uint8_t *
     A.read_header(&ci, 1);
     const int nc = ci.num_components;
     const ComponentInfo *comp = (const ComponentInfo *)ci.comp_info;
-    volatile int rc = LLFE_OK;
     int sampling = 0;
-    if (ci.data_precision != 8 || !comp ||
-        !((nc == 1 && ci.jpeg_color_space == JCS_GRAYSCALE) || (nc == 3 && ci.jpeg_color_space == JCS_YCbCr))) {
-        rc = LLFE_ERR_UNSUPPORTED;
-    } else if ((int32_t)ci.image_width != w || (int32_t)ci.image_height != h) {
-        rc = LLFE_ERR_CAPACITY;
-    } else if (nc == 1) {
-        sampling = LLFE_JPEG_GRAY;
-    } else {
-        const int hs = comp[0].h_samp_factor, vs = comp[0].v_samp_factor;
-        const bool chroma11 = comp[1].h_samp_factor == 1 && comp[1].v_samp_factor == 1 &&
-                              comp[2].h_samp_factor == 1 && comp[2].v_samp_factor == 1;
-        sampling = !chroma11 ? 0 : hs == 1 && vs == 1 ? LLFE_JPEG_444 : hs == 2 && vs == 1 ? LLFE_JPEG_422 :
-                   hs == 2 && vs == 2 ? LLFE_JPEG_420 : 0;
-        if (!sampling) rc = LLFE_ERR_UNSUPPORTED;
-    }
+    volatile int rc = classify(ci, comp, h, w, &sampling);
     void **arrays = nullptr;
     if (rc == LLFE_OK) {
         arrays = A.read_coefficients(&ci);  // every scan: the entropy half of the decode
@@ -390,34 +428,7 @@ int read_coefs(const uint8_t *data, size_t size, int32_t h, int32_t w, uint8_t *
     }
     llfe_jpeg_desc d;
     memset(&d, 0, sizeof d);
-    if (rc == LLFE_OK) {
-        d.n_comp = nc;
-        d.sampling = sampling;
-        int64_t off = kQuantBytes;
-        for (int c = 0; c < nc && rc == LLFE_OK; c++) {
-            const ComponentInfo &k = comp[c];
-            const int hs = c ? (sampling == LLFE_JPEG_422 || sampling == LLFE_JPEG_420 ? 2 : 1) : 1;
-            const int vs = c ? (sampling == LLFE_JPEG_420 ? 2 : 1) : 1;
-            // the geometry the device pass assumes, checked against the library's own
-            if (!k.quant_table || (int64_t)k.downsampled_width != div_up(w, hs) ||
-                (int64_t)k.downsampled_height != div_up(h, vs) ||
-                (int64_t)k.width_in_blocks != div_up(k.downsampled_width, 8) ||
-                (int64_t)k.height_in_blocks != div_up(k.downsampled_height, 8)) {
-                rc = LLFE_ERR_UNSUPPORTED;
-                break;
-            }
-            d.comp[c].blocks_w = (int32_t)k.width_in_blocks;
-            d.comp[c].blocks_h = (int32_t)k.height_in_blocks;
-            d.comp[c].width = (int32_t)k.downsampled_width;
-            d.comp[c].height = (int32_t)k.downsampled_height;
-            d.comp[c].quant_offset = 128 * c;
-            d.comp[c].coef_offset = off;
-            off += (int64_t)k.width_in_blocks * k.height_in_blocks * 128;
-        }
-        // a caller may stage in slots smaller than the 4:4:4 worst case (a 4:2:0 feed needs half):
-        // what does not fit is handed back like any other image this path does not take
-        if (rc == LLFE_OK && off > slot_bytes) rc = LLFE_ERR_UNSUPPORTED;
-    }
+    if (rc == LLFE_OK) rc = geometry(comp, nc, sampling, h, w, slot_bytes, true, &d);
     if (rc == LLFE_OK) {
         const MemoryMgr *mem = (const MemoryMgr *)ci.mem;
         for (int c = 0; c < nc; c++) {
@@ -433,6 +444,257 @@ int read_coefs(const uint8_t *data, size_t size, int32_t h, int32_t w, uint8_t *
     }
     A.destroy(&ci);
     return rc;
+}
+
+// ---- the host half of the device entropy decode (jpeg_huff.hip): headers only
+struct Dht {
+    bool present = false;
+    uint8_t counts[17] = {0};
+    uint8_t vals[256] = {0};
+};
+
+// canonical codes of a DHT -> the decoder's table; false for an over-subscribed code (and, as
+// libjpeg's jpeg_make_d_derived_tbl does, for one that uses the all-ones code of any length)
+bool build_tab(const Dht &h, llfe_huff::Tab *t) {
+    memset(t, 0, sizeof *t);
+    uint32_t code = 0;
+    int k = 0;
+    for (int l = 1; l <= 16; l++) {
+        t->off[l] = k - (int)code;
+        code += h.counts[l];
+        k += h.counts[l];
+        if (code >= (1u << l)) return false;
+        t->lim[l] = code << (16 - l);
+        code <<= 1;
+    }
+    t->lim[17] = t->lim[16];
+    memcpy(t->vals, h.vals, 256);
+    return k > 0 && k <= 256;
+}
+
+struct Walk {
+    int nc = 0;
+    uint8_t cid[3] = {0}, hv[3] = {0}, td[3] = {0}, ta[3] = {0};
+    size_t scan_begin = 0, scan_end = 0;
+};
+
+// The marker walk: one SOF0 / SOF1, the DHTs, exactly one SOS with every component and the
+// whole spectrum, no restart interval, and the scan ending at an FF D9 that is the first marker
+// after it.  Everything else is for another decoder.
+int walk(const uint8_t *d, size_t n, Dht (&dht)[4], Walk &W) {
+    size_t p = 2;
+    bool sof = false;
+    for (;;) {
+        if (p + 4 > n || d[p] != 0xFF) return LLFE_ERR_UNSUPPORTED;
+        const uint8_t m = d[p + 1];
+        if (m == 0xFF || m == 0x00 || m == 0x01 || (m >= 0xD0 && m <= 0xD9)) return LLFE_ERR_UNSUPPORTED;
+        const size_t len = (size_t)d[p + 2] << 8 | d[p + 3];
+        if (len < 2 || p + 2 + len > n) return LLFE_ERR_UNSUPPORTED;
+        const uint8_t *s = d + p + 4;
+        const size_t sl = len - 2;
+        if (m == 0xC0 || m == 0xC1) {
+            if (sof || sl < 6 || s[0] != 8) return LLFE_ERR_UNSUPPORTED;
+            W.nc = s[5];
+            if ((W.nc != 1 && W.nc != 3) || sl != 6 + 3 * (size_t)W.nc) return LLFE_ERR_UNSUPPORTED;
+            for (int c = 0; c < W.nc; c++) {
+                W.cid[c] = s[6 + 3 * c];
+                W.hv[c] = s[7 + 3 * c];
+            }
+            sof = true;
+        } else if (m == 0xC4) {
+            size_t q = 0;
+            while (q < sl) {
+                const int cls = s[q] >> 4, id = s[q] & 15;
+                if (cls > 1 || id > 1 || q + 17 > sl) return LLFE_ERR_UNSUPPORTED;
+                Dht &t = dht[cls * 2 + id];
+                t = Dht();
+                size_t total = 0;
+                for (int l = 1; l <= 16; l++) total += (t.counts[l] = s[q + l]);
+                if (total > 256 || q + 17 + total > sl) return LLFE_ERR_UNSUPPORTED;
+                memcpy(t.vals, s + q + 17, total);
+                t.present = true;
+                q += 17 + total;
+            }
+        } else if (m >= 0xC2 && m <= 0xCF) {  // progressive, lossless, arithmetic, DAC
+            return LLFE_ERR_UNSUPPORTED;
+        } else if (m == 0xDD) {
+            if (sl != 2 || s[0] || s[1]) return LLFE_ERR_UNSUPPORTED;  // a restart interval
+        } else if (m == 0xDA) {
+            if (!sof || sl < 1 || s[0] != W.nc || sl != 4 + 2 * (size_t)W.nc) return LLFE_ERR_UNSUPPORTED;
+            for (int c = 0; c < W.nc; c++) {
+                if (s[1 + 2 * c] != W.cid[c]) return LLFE_ERR_UNSUPPORTED;  // (frame order)
+                W.td[c] = s[2 + 2 * c] >> 4;
+                W.ta[c] = s[2 + 2 * c] & 15;
+                if (W.td[c] > 1 || W.ta[c] > 1 || !dht[W.td[c]].present || !dht[2 + W.ta[c]].present)
+                    return LLFE_ERR_UNSUPPORTED;
+            }
+            const uint8_t *e = s + 1 + 2 * W.nc;
+            if (e[0] != 0 || e[1] != 63 || e[2] != 0) return LLFE_ERR_UNSUPPORTED;
+            W.scan_begin = p + 2 + len;
+            size_t q = W.scan_begin;
+            for (;;) {
+                const uint8_t *f = q < n ? (const uint8_t *)memchr(d + q, 0xFF, n - q) : nullptr;
+                if (!f || (size_t)(f - d) + 1 >= n) return LLFE_ERR_UNSUPPORTED;  // no EOI: truncated
+                q = (size_t)(f - d);
+                if (d[q + 1] == 0x00) {
+                    q += 2;
+                    continue;
+                }
+                if (d[q + 1] != 0xD9) return LLFE_ERR_UNSUPPORTED;  // RSTn, another scan, fill bytes
+                W.scan_end = q;
+                return W.scan_end > W.scan_begin ? LLFE_OK : LLFE_ERR_UNSUPPORTED;
+            }
+        }
+        p += 2 + len;
+    }
+}
+
+// parse one image and stage its record; every eligibility check comes before the first byte is
+// written
+int parse_one(const uint8_t *data, size_t size, int32_t h, int32_t w, uint8_t *rec, int64_t record_offset,
+              int64_t record_stride, int64_t slot_bytes, llfe_jpeg_desc *desc, llfe_jpeg_scan *scan) {
+    const Api &A = api();
+    if (!A.ok) return LLFE_ERR_UNSUPPORTED;
+    if (size < 3 || data[0] != 0xFF || data[1] != 0xD8 || data[2] != 0xFF) return LLFE_ERR_UNSUPPORTED;
+    if (exif_orientation(data, size) != 1) return LLFE_ERR_UNSUPPORTED;
+    Decompress ci;
+    Err err;
+    memset(&ci, 0, sizeof ci);
+    ci.err = A.std_error(&err.mgr);
+    err.mgr.error_exit = on_error;
+    err.mgr.output_message = on_output;
+    err.code = 0;
+    if (setjmp(err.jb)) {
+        A.destroy(&ci);
+        return err.code;
+    }
+    A.create(&ci, kJpegLibVersion, sizeof(Decompress));
+    A.mem_src(&ci, data, (unsigned long)size);
+    A.read_header(&ci, 1);
+    const int nc = ci.num_components;
+    const ComponentInfo *comp = (const ComponentInfo *)ci.comp_info;
+    int sampling = 0;
+    volatile int rc = classify(ci, comp, h, w, &sampling);
+    if (rc == LLFE_OK && (ci.progressive_mode || ci.arith_code || ci.restart_interval != 0 || err.mgr.num_warnings != 0))
+        rc = LLFE_ERR_UNSUPPORTED;
+    llfe_jpeg_desc d;
+    memset(&d, 0, sizeof d);
+    if (rc == LLFE_OK) rc = geometry(comp, nc, sampling, h, w, slot_bytes, false, &d);
+    Dht dht[4];
+    Walk W;
+    if (rc == LLFE_OK) rc = walk(data, size, dht, W);
+    const QuantTbl *qt[3] = {nullptr, nullptr, nullptr};
+    if (rc == LLFE_OK) {  // this walk and the library's agree on the frame
+        if (W.nc != nc) rc = LLFE_ERR_UNSUPPORTED;
+        for (int c = 0; c < nc && rc == LLFE_OK; c++) {
+            const ComponentInfo &k = comp[c];
+            if (W.cid[c] != k.component_id || W.hv[c] != (k.h_samp_factor << 4 | k.v_samp_factor) || k.quant_tbl_no < 0 ||
+                k.quant_tbl_no > 3 || !(qt[c] = (const QuantTbl *)ci.quant_tbl_ptrs[k.quant_tbl_no]))
+                rc = LLFE_ERR_UNSUPPORTED;
+        }
+    }
+    llfe_huff::Tab tabs[4];
+    memset(tabs, 0, sizeof tabs);
+    if (rc == LLFE_OK) {
+        for (int c = 0; c < nc; c++)
+            for (int t : {(int)W.td[c], 2 + (int)W.ta[c]})
+                if (!build_tab(dht[t], &tabs[t])) rc = LLFE_ERR_UNSUPPORTED;
+    }
+    const int64_t scan_bytes = (int64_t)W.scan_end - (int64_t)W.scan_begin;
+    const int64_t padded = ((scan_bytes + 15) & ~(int64_t)15) + 16;
+    if (rc == LLFE_OK && (scan_bytes >= (1 << 28) || LLFE_JPEG_RECORD_HEADER + padded > record_stride))
+        rc = LLFE_ERR_UNSUPPORTED;
+    if (rc == LLFE_OK) {
+        llfe_jpeg_scan s;
+        memset(&s, 0, sizeof s);
+        s.record_offset = record_offset;
+        s.quant_offset = 0;
+        s.table_offset = (int32_t)kQuantBytes;
+        s.scan_offset = LLFE_JPEG_RECORD_HEADER;
+        s.scan_bytes = (int32_t)scan_bytes;
+        const int H = nc == 1 ? 1 : comp[0].h_samp_factor, V = nc == 1 ? 1 : comp[0].v_samp_factor;
+        // a one-component scan is not interleaved: its MCU is one block and there is no padding
+        s.mcus_w = nc == 1 ? d.comp[0].blocks_w : (int32_t)div_up(w, 8 * H);
+        s.mcus_h = nc == 1 ? d.comp[0].blocks_h : (int32_t)div_up(h, 8 * V);
+        int b = 0;
+        for (int c = 0; c < nc; c++) {
+            s.comp_hs[c] = (uint8_t)(c ? 1 : H);
+            s.comp_vs[c] = (uint8_t)(c ? 1 : V);
+            for (int y = 0; y < s.comp_vs[c]; y++)
+                for (int x = 0; x < s.comp_hs[c]; x++, b++) {
+                    s.blk_comp[b] = (uint8_t)c;
+                    s.blk_x[b] = (uint8_t)x;
+                    s.blk_y[b] = (uint8_t)y;
+                    s.blk_dc[b] = W.td[c];
+                    s.blk_ac[b] = W.ta[c];
+                }
+        }
+        s.blocks_in_mcu = b;
+        memset(rec, 0, LLFE_JPEG_RECORD_HEADER);
+        for (int c = 0; c < nc; c++) memcpy(rec + s.quant_offset + 128 * c, qt[c]->quantval, 128);
+        memcpy(rec + s.table_offset, tabs, sizeof tabs);
+        memcpy(rec + s.scan_offset, data + W.scan_begin, (size_t)scan_bytes);
+        memset(rec + s.scan_offset + scan_bytes, 0, (size_t)(padded - scan_bytes));
+        *desc = d;
+        *scan = s;
+    }
+    A.destroy(&ci);
+    return rc;
+}
+
+// One image of llfe_jpeg_entropy_reference: the phases of jpeg_huff.hip, serially.
+int reference_one(const uint8_t *rec, const llfe_jpeg_scan &sc, const llfe_jpeg_desc &d, uint8_t *slot, bool one_piece) {
+    using namespace llfe_huff;
+    static const uint8_t nat[64] = {LLFE_JPEG_NATURAL_ORDER};
+    const uint8_t *scan = rec + sc.scan_offset;
+    const Tab *tabs = (const Tab *)(rec + sc.table_offset);
+    const int len = sc.scan_bytes;
+    const int total = sc.mcus_w * sc.mcus_h * sc.blocks_in_mcu;
+    for (int c = 0; c < d.n_comp; c++) {  // phase 1
+        memcpy(slot + d.comp[c].quant_offset, rec + sc.quant_offset + 128 * c, 128);
+        memset(slot + d.comp[c].coef_offset, 0, (size_t)d.comp[c].blocks_w * d.comp[c].blocks_h * 128);
+    }
+    const int nsub = one_piece ? 1 : subsequences(len);
+    auto end_of = [&](int i) { return one_piece ? len : std::min(len, (i + 1) * kSub); };
+    const State start{0, 0};
+    const Geometry g{&sc, &d, slot};
+    std::vector<State> in((size_t)nsub), out((size_t)nsub), prev;
+    std::vector<int> cnt((size_t)nsub, 0), first((size_t)nsub, 0);
+    for (int i = 0; i < nsub; i++) {  // phase 2: every lane from its guess ...
+        in[i] = i ? State{sub_start(scan, len, i), 0} : start;
+        out[i] = decode_sub<false>(scan, len, tabs, sc, in[i], end_of(i), &cnt[i], nat, g, nullptr, 0, 0);
+    }
+    for (int r = 0; r < nsub; r++) {  // ... then rounds from the predecessor's exit state
+        prev = out;
+        bool changed = false;
+        for (int i = 1; i < nsub; i++)
+            if (prev[i - 1].pos != kNone && !same(prev[i - 1], in[i])) {
+                in[i] = prev[i - 1];
+                out[i] = decode_sub<false>(scan, len, tabs, sc, in[i], end_of(i), &cnt[i], nat, g, nullptr, 0, 0);
+                changed = true;
+            }
+        if (!changed) break;
+    }
+    int sum = 0;  // phases 3 and 4
+    for (int i = 0; i < nsub; i++) {
+        if (out[i].pos == kNone || !same(in[i], i ? out[i - 1] : start)) return LLFE_ERR_UNSUPPORTED;
+        first[i] = sum;
+        sum += cnt[i];
+    }
+    if (sum != total || out[nsub - 1].pos != (uint32_t)len * 8u || out[nsub - 1].bz != 0) return LLFE_ERR_UNSUPPORTED;
+    std::vector<int16_t> dcd((size_t)total, 0);
+    for (int i = 0; i < nsub; i++) {  // phase 5
+        int n = 0;
+        decode_sub<true>(scan, len, tabs, sc, in[i], end_of(i), &n, nat, g, dcd.data(), first[i], total);
+    }
+    int dc[3] = {0, 0, 0};  // phase 6
+    for (int blk = 0; blk < total; blk++) {
+        int c;
+        int16_t *dst = locate(g, blk, &c);
+        dc[c] += dcd[(size_t)blk];
+        if (dst) dst[0] = (int16_t)dc[c];
+    }
+    return LLFE_OK;
 }
 
 }  // namespace llfe_jpeg
@@ -483,5 +745,62 @@ extern "C" int llfe_jpeg_read_coefs_batch(const uint8_t *const *data, const uint
     for (auto &t : th) t.join();
     for (int i = 0; i < n; i++)
         if (status[i]) return status[i];
+    return LLFE_OK;
+}
+
+extern "C" int llfe_jpeg_parse_batch(const uint8_t *const *data, const uint64_t *sizes, int32_t n, int32_t height,
+                                     int32_t width, uint8_t *staging, int64_t record_stride, int64_t slot_stride,
+                                     llfe_jpeg_desc *descs, llfe_jpeg_scan *scans, int32_t *status, int32_t threads) {
+    if (n < 0 || (n && (!data || !sizes || !staging || !descs || !scans || !status)) || height <= 0 || width <= 0 ||
+        height > 65535 || width > 65535 || slot_stride < 0 || record_stride < LLFE_JPEG_RECORD_HEADER ||
+        (record_stride & 15))
+        return LLFE_ERR_INVALID;
+    const int nt = std::max(1, std::min<int>(threads > 0 ? threads : 1, n));
+    std::atomic<int> next{0};
+    auto work = [&]() {
+        for (int i; (i = next.fetch_add(1)) < n;) {
+            int rc;
+            memset(&descs[i], 0, sizeof descs[i]);  // n_comp 0, blocks_in_mcu 0: nothing staged for this image
+            memset(&scans[i], 0, sizeof scans[i]);
+            try {
+                const int64_t off = (int64_t)i * record_stride;
+                rc = data[i] ? llfe_jpeg::parse_one(data[i], (size_t)sizes[i], height, width, staging + off, off,
+                                                    record_stride, slot_stride, &descs[i], &scans[i])
+                             : LLFE_ERR_INVALID;
+            } catch (const std::bad_alloc &) {
+                rc = LLFE_ERR_OOM;
+            }
+            status[i] = rc;
+        }
+    };
+    std::vector<std::thread> th;
+    for (int t = 1; t < nt; t++) th.emplace_back(work);
+    work();
+    for (auto &t : th) t.join();
+    for (int i = 0; i < n; i++)
+        if (status[i]) return status[i];
+    return LLFE_OK;
+}
+
+extern "C" int llfe_jpeg_entropy_reference(const uint8_t *staging, int64_t staging_bytes, const llfe_jpeg_scan *scans,
+                                           const llfe_jpeg_desc *descs, int32_t n, int32_t h, int32_t w, uint8_t *slots,
+                                           int64_t slot_stride, int32_t *status, int32_t one_piece) {
+    if (n < 0 || (n && (!staging || !scans || !descs || !slots || !status)) || h <= 0 || w <= 0 || h > 65535 ||
+        w > 65535 || slot_stride <= 0 || staging_bytes < 0 || ((uintptr_t)staging & 15))
+        return LLFE_ERR_INVALID;
+    int64_t plane_stride = 0;
+    int mb = 0, max_sub = 0, max_blocks = 0;
+    if (!llfe::check_jpeg_descs(descs, n, h, w, slot_stride, &plane_stride, &mb) ||
+        !llfe_huff::validate_scans(scans, descs, n, staging_bytes, &max_sub, &max_blocks))
+        return LLFE_ERR_INVALID;
+    try {
+        for (int i = 0; i < n; i++)
+            status[i] = scans[i].blocks_in_mcu == 0
+                            ? LLFE_ERR_UNSUPPORTED
+                            : llfe_jpeg::reference_one(staging + scans[i].record_offset, scans[i], descs[i],
+                                                       slots + (size_t)i * (size_t)slot_stride, one_piece != 0);
+    } catch (const std::bad_alloc &) {
+        return LLFE_ERR_OOM;
+    }
     return LLFE_OK;
 }

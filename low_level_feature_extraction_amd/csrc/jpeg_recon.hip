@@ -26,6 +26,7 @@
 // offsets inside the slot, block grids that cover the image, planes inside the workspace.
 #include <algorithm>
 
+#include "jpeg_desc_check.h"
 #include "llfe_internal.h"
 
 namespace llfe {
@@ -92,16 +93,6 @@ __device__ __forceinline__ void idct8(const int (&x)[8], int (&out)[8]) {
 }
 
 __device__ __forceinline__ int clamp8(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
-
-// the planes of one image in the workspace: component c is blocks_h * 8 rows of blocks_w * 8 bytes
-__host__ __device__ inline int64_t plane_bytes(const llfe_jpeg_desc &d, int c) {
-    return (int64_t)d.comp[c].blocks_w * d.comp[c].blocks_h * 64;
-}
-__host__ __device__ inline int64_t plane_offset(const llfe_jpeg_desc &d, int c) {
-    int64_t o = 0;
-    for (int k = 0; k < c; k++) o += plane_bytes(d, k);
-    return o;
-}
 
 __global__ __launch_bounds__(JT) void k_jpeg_idct(const uint8_t *__restrict__ coefs, int64_t slot_stride,
                                                   const llfe_jpeg_desc *__restrict__ descs,
@@ -269,41 +260,7 @@ __global__ __launch_bounds__(JT) void k_jpeg_color(const llfe_jpeg_desc *__restr
 
 bool validate_jpeg_descs(const llfe_jpeg_desc *descs, int n, int h, int w, int64_t slot_stride,
                          int64_t *plane_stride, int *max_blocks) {
-    int64_t ps = 0;
-    int mb = 0;
-    auto div_up = [](int a, int b) { return (a + b - 1) / b; };
-    for (int i = 0; i < n; i++) {
-        const llfe_jpeg_desc &d = descs[i];
-        if (d.n_comp == 0) continue;
-        const int cls = d.sampling;
-        if (!((d.n_comp == 1 && cls == LLFE_JPEG_GRAY) ||
-              (d.n_comp == 3 && (cls == LLFE_JPEG_444 || cls == LLFE_JPEG_422 || cls == LLFE_JPEG_420))))
-            return false;
-        for (int c = 0; c < d.n_comp; c++) {
-            const auto &k = d.comp[c];
-            const int hs = c && (cls == LLFE_JPEG_422 || cls == LLFE_JPEG_420) ? 2 : 1;
-            const int vs = c && cls == LLFE_JPEG_420 ? 2 : 1;
-            // the component's real samples and a block grid that covers them
-            if (k.width != div_up(w, hs) || k.height != div_up(h, vs)) return false;
-            if (k.blocks_w < div_up(k.width, 8) || k.blocks_h < div_up(k.height, 8) || k.blocks_w > 8192 ||
-                k.blocks_h > 8192)
-                return false;
-            const int64_t bytes = (int64_t)k.blocks_w * k.blocks_h * 128;
-            if (k.coef_offset < 0 || (k.coef_offset & 15) || k.coef_offset > slot_stride ||
-                bytes > slot_stride - k.coef_offset)
-                return false;
-            if (k.quant_offset < 0 || (k.quant_offset & 15) || k.quant_offset > slot_stride ||
-                128 > slot_stride - k.quant_offset)
-                return false;
-            mb = std::max<int64_t>(mb, (int64_t)k.blocks_w * k.blocks_h);
-        }
-        if (d.n_comp == 3 && (d.comp[1].blocks_w != d.comp[2].blocks_w || d.comp[1].blocks_h != d.comp[2].blocks_h))
-            return false;
-        ps = std::max(ps, plane_offset(d, d.n_comp));
-    }
-    *plane_stride = (ps + 15) & ~(int64_t)15;
-    *max_blocks = mb;
-    return true;
+    return check_jpeg_descs(descs, n, h, w, slot_stride, plane_stride, max_blocks);  // jpeg_desc_check.h
 }
 
 hipError_t launch_jpeg_reconstruct(const uint8_t *coefs, int64_t slot_stride, const llfe_jpeg_desc *d_descs, int n,

@@ -30,6 +30,7 @@
 
 #include "../../include/llfe.h"
 #include "contours.h"
+#include "jpeg_huff_core.h"
 #include "llfe_internal.h"
 
 using namespace llfe;
@@ -476,6 +477,13 @@ struct llfe_ctx {
     HostBuf<llfe_jpeg_desc> h_jpeg_desc;
     DevBuf<llfe_jpeg_desc> d_jpeg_desc;
     DevBuf<uint8_t> d_jpeg_planes;
+    // llfe_jpeg_entropy_decode: the validated scan records, the per-image status and the
+    // kernels' workspace (subsequence states, block counts, DC differences)
+    HostBuf<llfe_jpeg_scan> h_jpeg_scan;
+    DevBuf<llfe_jpeg_scan> d_jpeg_scan;
+    HostBuf<int32_t> h_jpeg_status;
+    DevBuf<int32_t> d_jpeg_status;
+    DevBuf<uint8_t> d_jpeg_huff_ws;
     Work *km_last = nullptr;  // workspace of the last k-means launch (llfe_kmeans_attempts)
     // LLFE_FEATURE_FONTS: per slot the records and counters of the chunk's font pass, whether
     // that pass ran its contours on the GPU (else finish_chunk takes the host path) and the
@@ -1914,6 +1922,74 @@ int llfe_jpeg_reconstruct(llfe_ctx *ctx, const uint8_t *coefs, int64_t slot_stri
     if (rc != LLFE_OK) return rc;
     HIPCHK(ctx, hipStreamSynchronize(s));  // (the pinned descriptors and the planes are free again)
     ctx->prof.collect(Profiler::kStageSlot);
+    return LLFE_OK;
+}
+
+int llfe_jpeg_entropy_decode(llfe_ctx *ctx, const uint8_t *staging, int64_t staging_bytes, const llfe_jpeg_scan *scans,
+                             const llfe_jpeg_desc *descs, int32_t n, int32_t h, int32_t w, uint8_t *slots,
+                             int64_t slot_stride, int32_t *status_out, llfe_stream stream) {
+    if (!ctx) return LLFE_ERR_INVALID;
+    if (!valid_dims(n, h, w) || h > 65535 || w > 65535 || n > 65535 ||
+        (n && (!staging || !scans || !descs || !slots || !status_out)) || slot_stride <= 0 || (slot_stride & 15) ||
+        ((uintptr_t)slots & 15) || staging_bytes < 0 || ((uintptr_t)staging & 15))
+        return ctx->fail(LLFE_ERR_INVALID, "llfe_jpeg_entropy_decode: bad arguments (n=%d h=%d w=%d slot_stride=%lld)", n,
+                         h, w, (long long)slot_stride);
+    int64_t plane_stride = 0;
+    int recon_blocks = 0, max_sub = 0, max_blocks = 0;
+    // nothing is launched on a descriptor or a record the host check has not passed
+    if (!validate_jpeg_descs(descs, n, h, w, slot_stride, &plane_stride, &recon_blocks))
+        return ctx->fail(LLFE_ERR_INVALID, "llfe_jpeg_entropy_decode: a descriptor points outside its slot or does not "
+                                           "cover %dx%d", w, h);
+    if (!llfe_huff::validate_scans(scans, descs, n, staging_bytes, &max_sub, &max_blocks))
+        return ctx->fail(LLFE_ERR_INVALID, "llfe_jpeg_entropy_decode: a scan record points outside the staging buffer or "
+                                           "its MCU geometry does not cover the block grids");
+    int64_t max_coef_bytes = 0;
+    for (int i = 0; i < n; i++) {
+        status_out[i] = scans[i].blocks_in_mcu ? LLFE_OK : LLFE_ERR_UNSUPPORTED;
+        for (int c = 0; c < descs[i].n_comp; c++)
+            max_coef_bytes = std::max<int64_t>(max_coef_bytes, (int64_t)descs[i].comp[c].blocks_w * descs[i].comp[c].blocks_h * 128);
+    }
+    if (n == 0 || max_sub == 0) return LLFE_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(ctx, ctx->h_jpeg_desc.ensure((size_t)n));
+    HIPCHK(ctx, ctx->d_jpeg_desc.ensure((size_t)n));
+    HIPCHK(ctx, ctx->h_jpeg_scan.ensure((size_t)n));
+    HIPCHK(ctx, ctx->d_jpeg_scan.ensure((size_t)n));
+    HIPCHK(ctx, ctx->h_jpeg_status.ensure((size_t)n));
+    HIPCHK(ctx, ctx->d_jpeg_status.ensure((size_t)n));
+    HIPCHK(ctx, ctx->d_jpeg_huff_ws.ensure(jpeg_huff_workspace_bytes(n, max_sub, max_blocks)));
+    std::memcpy(ctx->h_jpeg_desc.p, descs, sizeof(llfe_jpeg_desc) * (size_t)n);
+    std::memcpy(ctx->h_jpeg_scan.p, scans, sizeof(llfe_jpeg_scan) * (size_t)n);
+    std::memcpy(ctx->h_jpeg_status.p, status_out, sizeof(int32_t) * (size_t)n);
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_jpeg_desc.p, ctx->h_jpeg_desc.p, sizeof(llfe_jpeg_desc) * (size_t)n,
+                               hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_jpeg_scan.p, ctx->h_jpeg_scan.p, sizeof(llfe_jpeg_scan) * (size_t)n,
+                               hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_jpeg_status.p, ctx->h_jpeg_status.p, sizeof(int32_t) * (size_t)n,
+                               hipMemcpyHostToDevice, s));
+    const int prev_slot = ctx->prof.cur_slot;
+    ctx->prof.cur_slot = Profiler::kStageSlot;
+    const int passes = jpeg_huff_passes(max_sub);  // the cross-workgroup passes, fixed here from the scan lengths
+    auto launch = [&](int stage, int pass) {
+        return launch_jpeg_huff(stage, pass, staging, ctx->d_jpeg_scan.p, ctx->d_jpeg_desc.p, n, max_sub, max_blocks,
+                                max_coef_bytes, slots, slot_stride, ctx->d_jpeg_huff_ws.p, ctx->d_jpeg_status.p, s);
+    };
+    const int rc = [&]() -> int {
+        TIMED(ctx, s, "k_huff_init", (double)n * max_coef_bytes, launch(0, 0));
+        for (int p = 0; p < passes; p++) TIMED(ctx, s, "k_huff_sync", (double)staging_bytes, launch(1, p));
+        TIMED(ctx, s, "k_huff_verify", (double)n * max_sub * 20, launch(2, 0));
+        TIMED(ctx, s, "k_huff_write", (double)staging_bytes + (double)n * max_blocks * 2, launch(3, 0));
+        TIMED(ctx, s, "k_huff_dc", (double)n * max_blocks * 6, launch(4, 0));
+        return LLFE_OK;
+    }();
+    ctx->prof.cur_slot = prev_slot;
+    if (rc != LLFE_OK) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_jpeg_status.p, ctx->d_jpeg_status.p, sizeof(int32_t) * (size_t)n,
+                               hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));  // (the pinned records and the workspace are free again)
+    ctx->prof.collect(Profiler::kStageSlot);
+    std::memcpy(status_out, ctx->h_jpeg_status.p, sizeof(int32_t) * (size_t)n);
     return LLFE_OK;
 }
 

@@ -381,4 +381,18 @@ hipError_t launch_jpeg_reconstruct(const uint8_t *coefs, int64_t slot_stride, co
                                    int h, int w, int max_blocks, uint8_t *planes, int64_t plane_stride, uint8_t *out,
                                    hipStream_t s, int stage);
 
+// llfe_jpeg_entropy_decode (jpeg_huff.hip).  The scans and descriptors are validated on the
+// host first (jpeg_huff_core.h validate_scans, validate_jpeg_descs above); max_sub / max_blocks
+// are what that check returned.  workspace: jpeg_huff_workspace_bytes of device memory,
+// d_status: n ints, non-zero for the images to skip.  Stages, in this order on one stream:
+// 0 = zero the coefficient areas (max_coef_bytes: the largest component of an image) and copy the
+// quantisation tables, 1 = a synchronisation pass (pass = 0 .. jpeg_huff_passes - 1),
+// 2 = verification and block scan (sets d_status of an image that fails), 3 = the write pass,
+// 4 = the DC sums.
+size_t jpeg_huff_workspace_bytes(int n, int max_sub, int max_blocks);
+int jpeg_huff_passes(int max_sub);
+hipError_t launch_jpeg_huff(int stage, int pass, const uint8_t *staging, const llfe_jpeg_scan *d_scans,
+                            const llfe_jpeg_desc *d_descs, int n, int max_sub, int max_blocks, int64_t max_coef_bytes,
+                            uint8_t *slots, int64_t slot_stride, uint8_t *workspace, int *d_status, hipStream_t s);
+
 }  // namespace llfe

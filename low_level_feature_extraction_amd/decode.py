@@ -12,7 +12,8 @@ PNG, CMYK JPEG, EXIF-rotated JPEG, other formats) is decoded with Pillow.  Image
 above ``MAX_PIXELS`` (cv2's CV_IO_MAX_IMAGE_PIXELS, 2^30) fail like cv2.imdecode does.
 
 ``decode_batch_device`` (opt-in, at the end of this module) returns the same batch in device
-memory: for JPEG the host stops after the entropy half and csrc/jpeg_recon.hip reconstructs.
+memory: for JPEG the host stops after the entropy half and csrc/jpeg_recon.hip reconstructs;
+with ``entropy="device"`` baseline files are entropy-decoded on the device too (csrc/jpeg_huff.hip).
 """
 from __future__ import annotations
 
@@ -347,17 +348,18 @@ def _staging(n, stride):
         return buf
 
 
-def stage_coefs(blobs, workers=None, slot_bytes=None) -> StagedCoefs:
+def stage_coefs(blobs, workers=None, slot_bytes=None, size=None) -> StagedCoefs:
     """The host half of decode_batch_device: entropy-decode every eligible JPEG of a batch of
     equally sized images into the next staging buffer of a ring of three (so a producer thread
     may stage batch k + 1 while batch k is copied and reconstructed).  Host only.
     ``slot_bytes`` (a multiple of 16; default coef_slot_bytes(h, w), the 4:4:4 worst case)
     sizes a slot: a feed known to be 4:2:0 needs half, and an image that does not fit is
-    handed back to the host decoders like any other."""
+    handed back to the host decoders like any other.  ``size`` (h, w) names the batch's image
+    size instead of reading it from the first blob (a part of a batch staged on its own)."""
     blobs = [bytes(b) for b in blobs]
     if not blobs:
         raise DecodeError("empty batch")
-    hw = _image_size(blobs[0])
+    hw = size or _image_size(blobs[0])
     if hw is None:
         hw = decode_bgr(blobs[0]).shape[:2]
     h, w = hw
@@ -430,12 +432,191 @@ def reconstruct_staged(st: StagedCoefs, device=0, workers=None, out=None):
     return out
 
 
-def decode_batch_device(blobs, device=0, workers=None, out=None):
+# ------------------------------------------------------------ JPEG entropy decode on the device
+# The entropy half on the device too (DESIGN.md §3 "JPEG entropy decode on the device"): the host
+# only parses the headers (llfe_jpeg_parse_batch), the file's scan bytes cross PCIe instead of
+# its coefficients, and llfe_jpeg_entropy_decode (csrc/jpeg_huff.hip) writes the coefficient
+# slots stage_coefs writes.  For baseline single-scan files without restart markers; every
+# other image, and every image whose scan shows an anomaly, takes the paths above.
+class StagedBytes:
+    """One batch after llfe_jpeg_parse_batch: ``records`` (n x record_stride uint8, pinned when
+    a GPU is present), ``descs`` / ``scans`` (the llfe_jpeg_desc / llfe_jpeg_scan arrays),
+    ``status`` per image, the blobs, the batch geometry and the slot stride the descriptors'
+    offsets were laid out for."""
+
+    def __init__(self, blobs, h, w, records, descs, scans, status, slot_bytes, tensor=None):
+        self.blobs, self.h, self.w = blobs, h, w
+        self.records, self.descs, self.scans, self.status = records, descs, scans, status
+        self.slot_bytes, self.tensor = slot_bytes, tensor
+
+    @property
+    def used_bytes(self) -> int:
+        """Bytes from the start of a record that any image of the batch occupies."""
+        from . import _lib
+
+        return max([_lib.JPEG_RECORD_HEADER + ((s.scan_bytes + 15) & ~15) + 16 for s in self.scans if s.blocks_in_mcu],
+                   default=0)
+
+
+_BYTES_STAGE = {}
+
+
+def _bytes_staging(n, stride):
+    """_staging for the records of stage_bytes (a ring of _STAGE_RING per (count, stride))."""
+    from . import _lib
+
+    with _STAGE_LOCK:
+        ring = _BYTES_STAGE.setdefault((n, stride), {"next": 0, "bufs": []})
+        if len(_BYTES_STAGE) > 4:
+            for k in [k for k in _BYTES_STAGE if k != (n, stride)]:
+                del _BYTES_STAGE[k]
+        if len(ring["bufs"]) < _STAGE_RING:
+            tensor = None
+            try:
+                import torch
+
+                if torch.cuda.is_available():
+                    tensor = torch.empty((n, stride), dtype=torch.uint8, pin_memory=True)
+            except ImportError:  # pragma: no cover - C-only deployments
+                pass
+            arr = tensor.numpy() if tensor is not None else np.empty((n, stride), np.uint8)
+            ring["bufs"].append((arr, (_lib.LlfeJpegDesc * n)(), (_lib.LlfeJpegScan * n)(), tensor))
+        buf = ring["bufs"][ring["next"] % _STAGE_RING]
+        ring["next"] += 1
+        return buf
+
+
+def stage_bytes(blobs, workers=None, slot_bytes=None) -> StagedBytes:
+    """The host half of decode_batch_device(entropy="device"): parse the headers of every
+    eligible JPEG of a batch of equally sized images (llfe_jpeg_parse_batch: baseline Huffman,
+    one interleaved scan, no restart markers, and what stage_coefs asks) and stage quantisation
+    tables, decode tables and the scan's bytes in the next buffer of a ring of three.  Host
+    only; no entropy decoding happens here.  The record stride is a power-of-two bucket of the
+    longest blob, so batches of like files reuse their pinned buffers."""
+    import ctypes as C
+
+    from . import _lib
+
+    blobs = [bytes(b) for b in blobs]
+    if not blobs:
+        raise DecodeError("empty batch")
+    hw = _image_size(blobs[0])
+    if hw is None:
+        hw = decode_bgr(blobs[0]).shape[:2]
+    h, w = hw
+    n = len(blobs)
+    if h > 65535 or w > 65535:  # beyond JPEG: nothing to stage
+        return StagedBytes(blobs, h, w, None, None, None, [-5] * n, 0)
+    if slot_bytes is not None and (slot_bytes <= 0 or slot_bytes % 16):
+        raise ValueError("slot_bytes must be a positive multiple of 16")
+    slot_bytes = slot_bytes or coef_slot_bytes(h, w)
+    longest = max(len(b) for b in blobs)
+    stride = _lib.JPEG_RECORD_HEADER + max(4096, 1 << (longest + 32).bit_length())
+    records, descs, scans, tensor = _bytes_staging(n, stride)
+    keep = [C.c_char_p(b) for b in blobs]
+    ptrs = (C.c_void_p * n)(*[C.cast(k, C.c_void_p) for k in keep])
+    sizes = (C.c_uint64 * n)(*[len(b) for b in blobs])
+    status = (C.c_int32 * n)()
+    _lib.lib().llfe_jpeg_parse_batch(ptrs, sizes, n, h, w, records.ctypes.data, stride, slot_bytes, descs, scans, status,
+                                     int(workers or default_decode_threads()))
+    del keep
+    return StagedBytes(blobs, h, w, records, descs, scans, list(status), slot_bytes, tensor)
+
+
+def entropy_reference(sb: StagedBytes, one_piece=False):
+    """llfe_jpeg_entropy_reference, the host twin of csrc/jpeg_huff.hip, over a StagedBytes:
+    -> (n x slot_bytes uint8 slots, status list).  For tests and for debugging the kernels."""
+    import ctypes as C
+
+    from . import _lib
+
+    n = len(sb.blobs)
+    slots = np.zeros((n, sb.slot_bytes), np.uint8)
+    status = (C.c_int32 * n)()
+    rc = _lib.lib().llfe_jpeg_entropy_reference(sb.records.ctypes.data, sb.records.size, sb.scans, sb.descs, n, sb.h,
+                                                sb.w, slots.ctypes.data, sb.slot_bytes, status, int(bool(one_piece)))
+    if rc != 0:
+        raise ValueError(f"llfe_jpeg_entropy_reference: {rc}")
+    return slots, list(status)
+
+
+def entropy_decode_staged(sb: StagedBytes, device=0):
+    """The device half of the entropy decode: one H2D of the staged records, then
+    llfe_jpeg_entropy_decode on the current stream.  -> (n x slot_bytes uint8 device tensor of
+    coefficient slots, the descriptors of the images the device took (n_comp 0 for the others),
+    the device's status list)."""
+    import torch
+
+    from . import _lib
+    from .backend import Backend
+
+    n = len(sb.blobs)
+    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+    with torch.cuda.device(dev):
+        used = sb.used_bytes
+        host = sb.tensor if sb.tensor is not None else torch.from_numpy(sb.records)
+        d_rec = torch.empty((n, sb.records.shape[1]), dtype=torch.uint8, device=dev)
+        for i, rc in enumerate(sb.status):  # (a record fills what its file is long, not the bucket)
+            if rc == 0:
+                d_rec[i, :used].copy_(host[i, :used], non_blocking=True)
+        d_slots = torch.empty((n, sb.slot_bytes), dtype=torch.uint8, device=dev)
+        status = Backend.get(dev.index).jpeg_entropy_decode(d_rec, sb.scans, sb.descs, sb.h, sb.w, d_slots)
+    descs = (_lib.LlfeJpegDesc * n).from_buffer_copy(sb.descs)
+    for i, rc in enumerate(status):
+        if rc != 0:
+            descs[i].n_comp = 0
+    return d_slots, descs, status
+
+
+def decode_staged_bytes(sb: StagedBytes, device=0, workers=None, out=None):
+    """The device half of decode_batch_device(entropy="device"): the staged records across, the
+    entropy kernels, llfe_jpeg_reconstruct with the descriptors of the images that passed, and
+    for the others the host coefficient path (stage_coefs / reconstruct_staged), which leaves
+    what it cannot take to the host decoders.  -> (N, H, W, 3) uint8 tensor on the device."""
+    import torch
+
+    from .backend import Backend
+
+    n, h, w = len(sb.blobs), sb.h, sb.w
+    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+    if out is None:
+        out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
+    if tuple(out.shape) != (n, h, w, 3) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"out must be a contiguous {(n, h, w, 3)} uint8 tensor on {dev}")
+    status = [-5] * n
+    if any(rc == 0 for rc in sb.status):
+        d_slots, descs, status = entropy_decode_staged(sb, dev)
+        if any(rc == 0 for rc in status):
+            with torch.cuda.device(dev):
+                Backend.get(dev.index).jpeg_reconstruct(d_slots, descs, h, w, out)
+    todo = [i for i, rc in enumerate(status) if rc != 0]
+    if todo:  # the host coefficient path first, the host decoders for what that hands back
+        sub = torch.empty((len(todo), h, w, 3), dtype=torch.uint8, device=dev)
+        try:
+            reconstruct_staged(stage_coefs([sb.blobs[i] for i in todo], workers, size=(h, w)), dev, workers, sub)
+        except DecodeError as e:  # name the image by its place in the whole batch
+            head, sep, tail = str(e).partition(":")
+            k = head[len("image "):]
+            raise DecodeError(f"image {todo[int(k)]}:{tail}" if sep and k.isdigit() else str(e)) from None
+        out[torch.tensor(todo, device=dev)] = sub
+    return out
+
+
+def decode_batch_device(blobs, device=0, workers=None, out=None, entropy="host"):
     """decode_batch with the reconstruction on the GPU: equally sized images -> one
     (N, H, W, 3) BGR uint8 tensor on ``device``, the same bytes decode_batch returns.  Eligible
     JPEGs (8-bit greyscale or YCbCr 4:4:4 / 4:2:2 / 4:2:0, EXIF orientation 1, no decoder
     warning) are entropy-decoded on ``workers`` host threads and reconstructed by
     csrc/jpeg_recon.hip; everything else (PNG, CMYK, EXIF-rotated, other samplings, truncated
     files) goes through the host decoders image by image.  Raises DecodeError as decode_batch
-    does.  The result feeds Backend.process / submit unchanged."""
-    return reconstruct_staged(stage_coefs(blobs, workers), device, workers, out)
+    does.  The result feeds Backend.process / submit unchanged.
+
+    ``entropy="device"`` moves the entropy decode of baseline single-scan JPEGs without restart
+    markers to the device as well (csrc/jpeg_huff.hip): the file bytes cross PCIe, not the
+    coefficients.  Images it does not take, and images whose scan the kernels find anomalous,
+    go through the ``entropy="host"`` path; the result is the same bytes in every case."""
+    if entropy == "host":
+        return reconstruct_staged(stage_coefs(blobs, workers), device, workers, out)
+    if entropy != "device":
+        raise ValueError('entropy must be "host" or "device"')
+    return decode_staged_bytes(stage_bytes(blobs, workers), device, workers, out)

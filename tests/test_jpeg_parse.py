@@ -1,0 +1,228 @@
+"""The host half of the device entropy decode (llfe_jpeg_parse_batch, csrc/jpeg_decode.cpp) and
+the plain C++ twin of the kernels (llfe_jpeg_entropy_reference, the same csrc/jpeg_huff_core.h
+the kernels of csrc/jpeg_huff.hip compile), CPU only.
+
+The parser must take exactly the baseline, single-scan, restart-free files, with the
+descriptors decode.stage_coefs computes, and write nothing for the others.  The twin -- the
+kernels' subsequences, rounds, verification, block scan, write pass and DC sums run serially --
+must reproduce the coefficient slots of stage_coefs (libjpeg-turbo's jpeg_read_coefficients)
+bit for bit, also on flat images that never self-synchronise and on the seams of the
+subsequence size, and must hand corrupt scans back.
+"""
+import ctypes as C
+import io
+
+import numpy as np
+import pytest
+from PIL import Image
+
+from low_level_feature_extraction_amd import _lib, decode, synth
+from tests import jpeg_huff_cases as H
+from tests import jpeg_restate as R
+
+
+def _parse(blobs, h, w, fill=0xA5, threads=1, stride=None, slot_bytes=None):
+    """llfe_jpeg_parse_batch into pre-filled records, so a write shows."""
+    n = len(blobs)
+    stride = stride or _lib.JPEG_RECORD_HEADER + ((max(len(b) for b in blobs) + 15) & ~15) + 16
+    rec = np.full((n, stride), fill, np.uint8)
+    descs, scans = (_lib.LlfeJpegDesc * n)(), (_lib.LlfeJpegScan * n)()
+    keep = [C.c_char_p(b) for b in blobs]
+    ptrs = (C.c_void_p * n)(*[C.cast(k, C.c_void_p) for k in keep])
+    sizes = (C.c_uint64 * n)(*[len(b) for b in blobs])
+    status = (C.c_int32 * n)()
+    rc = _lib.lib().llfe_jpeg_parse_batch(ptrs, sizes, n, h, w, rec.ctypes.data, stride,
+                                          slot_bytes or decode.coef_slot_bytes(h, w),
+                                          descs, scans, status, threads)
+    return rc, list(status), rec, descs, scans
+
+
+def _reference_equals_stage_coefs(blobs, one_piece=False):
+    sb = decode.stage_bytes(blobs, workers=2)
+    st = decode.stage_coefs(blobs, workers=2)
+    assert sb.status == [0] * len(blobs) and st.status == [0] * len(blobs)
+    slots, status = decode.entropy_reference(sb, one_piece)
+    assert status == [0] * len(blobs)
+    for i in range(len(blobs)):
+        assert bytes(sb.descs[i]) == bytes(st.descs[i])
+        assert H.slots_equal(slots[i], st.slots[i], st.descs[i]), f"image {i}"
+    return sb
+
+
+@pytest.mark.parametrize("h,w", R.SIZES)
+def test_parser_takes_exactly_the_baseline_single_scan_files(h, w):
+    blobs = [R.blob(h, w, k) for k in range(len(R.SETTINGS))]
+    rc, status, rec, descs, scans = _parse(blobs, h, w, threads=3)
+    assert status == [0 if k in H.ACCEPTED else H.UNSUPPORTED for k in range(len(blobs))]
+    assert rc == H.UNSUPPORTED  # the first non-OK status
+    st = decode.stage_coefs(blobs, workers=2)
+    for k in range(len(blobs)):
+        if k in H.ACCEPTED:
+            assert bytes(descs[k]) == bytes(st.descs[k])
+            s = scans[k]
+            assert s.record_offset == k * rec.shape[1] and s.scan_offset % 16 == 0 and s.scan_bytes >= 1
+            nc = descs[k].n_comp
+            assert s.blocks_in_mcu == (1 if nc == 1 else 2 + s.comp_hs[0] * s.comp_vs[0])
+            # the scan as it is in the file, up to the EOI, and zero padding behind it
+            b = blobs[k]
+            end = b.rindex(b"\xff\xd9")
+            assert bytes(rec[k, s.scan_offset:s.scan_offset + s.scan_bytes]) == b[end - s.scan_bytes:end]
+            assert not rec[k, s.scan_offset + s.scan_bytes:s.scan_offset + ((s.scan_bytes + 15) & ~15) + 16].any()
+        else:  # nothing staged
+            assert (rec[k] == 0xA5).all() and descs[k].n_comp == 0 and scans[k].blocks_in_mcu == 0
+
+
+@pytest.mark.parametrize("h,w", R.SIZES)
+@pytest.mark.parametrize("one_piece", [False, True])
+def test_reference_reproduces_the_coefficient_slots(h, w, one_piece):
+    _reference_equals_stage_coefs([R.blob(h, w, k) for k in H.ACCEPTED], one_piece)
+
+
+def test_refused_files_leave_nothing_written():
+    h, w = 64, 96
+    rng = np.random.default_rng(5)
+    arr = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
+    ok = R.jpeg(arr, quality=80)
+    ex = Image.Exif()
+    ex[0x0112] = 6
+    rot = io.BytesIO()
+    Image.fromarray(arr).save(rot, "JPEG", exif=ex.tobytes())
+    cmyk = io.BytesIO()
+    Image.fromarray(rng.integers(0, 256, (h, w, 4), dtype=np.uint8), "CMYK").save(cmyk, "JPEG")
+    truncated = ok[:len(ok) // 2]  # the scan never reaches an EOI
+    over = bytearray(ok)
+    dht = bytes(over).index(b"\xff\xc4")
+    counts = dht + 5  # counts[1..16] of the first table: move one code from its longest length to 2 bits
+    longest = max(l for l in range(16) if over[counts + l])
+    over[counts + longest] -= 1
+    over[counts + 1] += 1
+    other_size = R.jpeg(arr[:10], quality=80)
+    blobs = [ok, synth.encode_png(arr), rot.getvalue(), truncated, bytes(over), cmyk.getvalue(), other_size, ok]
+    for threads in (1, 3):
+        rc, status, rec, descs, scans = _parse(blobs, h, w, threads=threads)
+        assert status == [0, H.UNSUPPORTED, H.UNSUPPORTED, H.UNSUPPORTED, H.UNSUPPORTED, H.UNSUPPORTED, -3, 0]
+        for i, s in enumerate(status):
+            if s:
+                assert (rec[i] == 0xA5).all() and descs[i].n_comp == 0 and scans[i].blocks_in_mcu == 0
+            else:
+                assert descs[i].n_comp == 3 and not (rec[i] == 0xA5).all()
+        assert np.array_equal(rec[0], rec[7])
+    # a record stride too small for the scan hands the image back; bad arguments are refused
+    rc, status, rec, descs, scans = _parse([ok], h, w, stride=_lib.JPEG_RECORD_HEADER + 64)
+    assert status == [H.UNSUPPORTED] and (rec == 0xA5).all()
+    assert _parse([ok], h, w, stride=_lib.JPEG_RECORD_HEADER - 16)[0] == H.INVALID
+    assert _parse([ok], 0, w, slot_bytes=4096)[0] == H.INVALID
+
+
+@pytest.mark.parametrize("sub", [2, 1, 0])
+@pytest.mark.parametrize("stripe", [False, True])
+def test_reference_on_phase_locked_images(sub, stripe):
+    """A flat image's MCUs are bit-identical, so guessed states stay out of phase (4:2:0: for
+    ever): the true state has to be carried through lane by lane."""
+    sb = _reference_equals_stage_coefs([H.flat(sub, stripe)])
+    if sub == 2 and not stripe:
+        assert -(-sb.scans[0].scan_bytes // H.SUB) == 33
+
+
+def test_reference_on_the_seams_of_the_subsequence_size():
+    tiny = R.jpeg(np.random.default_rng(3).integers(0, 256, (8, 8), dtype=np.uint8), quality=1)
+    assert len(H.scan_bytes(tiny)) < H.SUB
+    _reference_equals_stage_coefs([tiny])
+    for target in (H.SUB - 2, H.SUB - 1, H.SUB, H.SUB + 1, H.SUB + 3, 2 * H.SUB - 2, 2 * H.SUB, 2 * H.SUB + 1, 2 * H.SUB + 3):
+        _reference_equals_stage_coefs([H.scan_of_length(target)])
+    blob, hits = H.stuffed_boundary()
+    d = H.scan_bytes(blob)
+    assert hits and all(d[k] == 0 and d[k - 1] == 0xFF and k % H.SUB == 0 for k in hits)
+    _reference_equals_stage_coefs([blob])
+    rng = np.random.default_rng(8)
+    for h, w in ((17, 33), (9, 260)):  # MCU padding in both directions
+        _reference_equals_stage_coefs([R.jpeg(rng.integers(0, 256, (h, w, 3), dtype=np.uint8), quality=q, subsampling=2,
+                                              optimize=o) for q, o in ((85, False), (100, False), (60, True))])
+
+
+def test_reference_hands_corrupt_scans_back():
+    good = R.blob(240, 321, 0)
+    blobs = [good, H.flipped(good), H.cut(good), good]
+    sb = decode.stage_bytes(blobs, workers=2)
+    assert sb.status == [0, 0, 0, 0]  # the headers are fine: the scan is what is wrong
+    slots, status = decode.entropy_reference(sb)
+    assert status[0] == status[3] == 0 and status[2] == H.UNSUPPORTED
+    st = decode.stage_coefs(blobs, workers=2)
+    for i in (0, 3):
+        assert H.slots_equal(slots[i], st.slots[i], st.descs[i])
+    if status[1] == 0:  # a flip the code absorbs is a valid file of another image
+        assert st.status[1] == 0 and H.slots_equal(slots[1], st.slots[1], st.descs[1])
+
+
+def test_reference_validates_records_before_decoding():
+    blobs = [R.blob(37, 53, k) for k in (0, 2, 11)]
+    sb = decode.stage_bytes(blobs, workers=1)
+    n = len(blobs)
+
+    def refused(edit):
+        scans = (_lib.LlfeJpegScan * n).from_buffer_copy(sb.scans)
+        descs = (_lib.LlfeJpegDesc * n).from_buffer_copy(sb.descs)
+        edit(scans, descs)
+        slots = np.full((n, sb.slot_bytes), 77, np.uint8)
+        status = (C.c_int32 * n)()
+        rc = _lib.lib().llfe_jpeg_entropy_reference(sb.records.ctypes.data, sb.records.size, scans, descs, n, sb.h, sb.w,
+                                                    slots.ctypes.data, sb.slot_bytes, status, 0)
+        assert rc == H.INVALID and (slots == 77).all()
+
+    def scan_too_long(s, d):
+        s[2].scan_bytes = sb.records.shape[1]
+
+    def table_outside(s, d):
+        s[1].table_offset = sb.records.size
+
+    def record_outside(s, d):
+        s[2].record_offset = sb.records.size - 16
+
+    def selector(s, d):
+        s[0].blk_ac[1] = 2
+
+    def component(s, d):
+        s[0].blk_comp[0] = 3
+
+    def grid_too_small(s, d):
+        s[0].mcus_w -= 1
+
+    def coef_outside(s, d):
+        d[1].comp[2].coef_offset = sb.slot_bytes - 64
+
+    for edit in (scan_too_long, table_outside, record_outside, selector, component, grid_too_small, coef_outside):
+        refused(edit)
+
+
+def test_scan_layout_matches_header_via_compiler(tmp_path):
+    import os
+    import subprocess
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    src = tmp_path / "lay.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "llfe.h"\nint main(void){'
+                   'printf("%zu %zu %zu %zu %zu %zu %d %d\\n", sizeof(llfe_jpeg_scan), offsetof(llfe_jpeg_scan, scan_bytes),'
+                   'offsetof(llfe_jpeg_scan, blocks_in_mcu), offsetof(llfe_jpeg_scan, blk_comp),'
+                   'offsetof(llfe_jpeg_scan, blk_ac), offsetof(llfe_jpeg_scan, comp_vs),'
+                   'LLFE_JPEG_HUFF_TABLE_BYTES, LLFE_JPEG_RECORD_HEADER);return 0;}')
+    exe = tmp_path / "lay"
+    subprocess.run(["gcc", "-std=c99", "-I", os.path.join(root, "include"), str(src), "-o", str(exe)], check=True)
+    got = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
+    S = _lib.LlfeJpegScan
+    assert got == [C.sizeof(S), S.scan_bytes.offset, S.blocks_in_mcu.offset, S.blk_comp.offset, S.blk_ac.offset,
+                   S.comp_vs.offset, _lib.JPEG_HUFF_TABLE_BYTES, _lib.JPEG_RECORD_HEADER]
+    assert C.sizeof(S) == 88
+
+
+def test_stage_bytes_ring_and_mixed_batch_statuses():
+    imgs = [synth.synth_numpy(i, 40, 56, seed=4) for i in range(3)]
+    blobs = [R.jpeg(imgs[0][:, :, ::-1].copy(), quality=90), synth.encode_png(imgs[1]),
+             R.jpeg(imgs[2][:, :, 1].copy(), quality=70, progressive=True)]
+    seen = []
+    for _ in range(4):
+        sb = decode.stage_bytes(blobs, workers=2)
+        assert sb.status == [0, H.UNSUPPORTED, H.UNSUPPORTED] and (sb.h, sb.w) == (40, 56)
+        assert [d.n_comp for d in sb.descs] == [3, 0, 0]
+        assert sb.used_bytes <= sb.records.shape[1] and sb.records.shape[1] % 16 == 0
+        seen.append(sb.records.ctypes.data)
+    assert len(set(seen[:3])) == 3 and seen[3] == seen[0]  # a ring of three staging buffers

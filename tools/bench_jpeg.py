@@ -13,9 +13,15 @@ JPEG leg are not touched: this tool measures the opt-in path beside them.
            A = decode.decode_batch into pinned BGR, submitted as a host batch, or
            B = decode.stage_coefs into pinned coefficient slots, then
                decode.reconstruct_staged (H2D + llfe_jpeg_reconstruct) and the device batch
-               submitted.
-           A and B alternate in one process, --legs each; then the isolated kernel times
-           (llfe_kernel_stats) and the H2D time of one batch of coefficients.
+               submitted, or
+           C = decode.stage_bytes (headers parsed, scan bytes into pinned records), then
+               decode.decode_staged_bytes (H2D of the records, llfe_jpeg_entropy_decode,
+               llfe_jpeg_reconstruct) and the device batch submitted.
+           A, B and C alternate in one process, --legs each; then the producers alone, the
+           isolated kernel times (llfe_kernel_stats) and the H2D times of one batch of
+           coefficients and of one batch of records.  The bar B had to clear over A is applied
+           to C over B: every C leg above every B leg, medians further apart than three times
+           B's min-max range.
 One JSON line per mode on stdout.
 """
 from __future__ import annotations
@@ -121,6 +127,8 @@ def gpu(args):
         def produce(k):
             if kind == "A":
                 return decode.decode_batch(blobs, bufs[k % 3], threads)
+            if kind == "C":
+                return decode.stage_bytes(blobs, threads, slot_bytes=slot_bytes)
             return decode.stage_coefs(blobs, threads, slot_bytes=slot_bytes)
 
         with ThreadPoolExecutor(max_workers=1) as prod:
@@ -134,6 +142,9 @@ def gpu(args):
                 if kind == "B":
                     with torch.cuda.stream(side):
                         item = decode.reconstruct_staged(item, 0, threads, out=outs[k % 3])
+                elif kind == "C":
+                    with torch.cuda.stream(side):
+                        item = decode.decode_staged_bytes(item, 0, threads, out=outs[k % 3])
                 pending.append(be.submit(item, feats, seed=args.seed + k))
                 if len(pending) == 2:
                     be.collect(pending.pop(0))
@@ -141,11 +152,15 @@ def gpu(args):
                 be.collect(pending.pop(0))
             return B * steps / (time.perf_counter() - t0)
 
-    leg("A"), leg("B")  # warm both: pinned rings, workspaces, thread pools
-    va, vb = [], []
+    with torch.cuda.stream(side):
+        dev = decode.decode_batch_device(blobs[:4], workers=threads, entropy="device")
+    assert np.array_equal(dev.cpu().numpy(), decode.decode_batch(blobs[:4], workers=threads))
+    leg("A"), leg("B"), leg("C")  # warm all three: pinned rings, workspaces, thread pools
+    va, vb, vc = [], [], []
     for _ in range(args.legs):
         va.append(leg("A"))
         vb.append(leg("B"))
+        vc.append(leg("C"))
     # producers alone, warm: what bounds each leg from the host side
     t = time.perf_counter()
     decode.decode_batch(blobs, bufs[0], threads)
@@ -153,6 +168,10 @@ def gpu(args):
     t = time.perf_counter()
     st = decode.stage_coefs(blobs, threads, slot_bytes=slot_bytes)
     prod_b = time.perf_counter() - t
+    t = time.perf_counter()
+    sb = decode.stage_bytes(blobs, threads, slot_bytes=slot_bytes)
+    prod_c = time.perf_counter() - t
+    assert sb.status == [0] * B
     # H2D of one batch of coefficients, and the kernels alone
     d_slots = torch.empty((B, slot_bytes), dtype=torch.uint8, device="cuda:0")
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -171,16 +190,44 @@ def gpu(args):
     kern = {k: {"ms": round(v["total_ms"] / 3, 3), "launches": v["launches"] // 3,
                 "GB_per_s": round(v["bytes"] / max(v["total_ms"], 1e-9) / 1e6, 1)}
             for k, v in ks.items() if k.startswith("k_jpeg")}
-    a, b = _spread(va), _spread(vb)
+    # the same for leg C: H2D of one batch of records (what the file is long, row by row), the
+    # entropy kernels alone, and how many images they took
+    used = sb.used_bytes
+    d_rec = torch.empty((B, sb.records.shape[1]), dtype=torch.uint8, device="cuda:0")
+    h2d_c = []
+    for _ in range(3):
+        e0.record()
+        for i in range(B):
+            d_rec[i, :used].copy_(sb.tensor[i, :used], non_blocking=True)
+        e1.record()
+        e1.synchronize()
+        h2d_c.append(e0.elapsed_time(e1))
+    be.set_profiling(True)
+    for _ in range(3):
+        taken = be.jpeg_entropy_decode(d_rec, sb.scans, sb.descs, h, w, d_slots)
+    ks = be.kernel_stats()
+    be.set_profiling(False)
+    kern_c = {k: {"ms": round(v["total_ms"] / 3, 3), "launches": v["launches"] // 3}
+              for k, v in ks.items() if k.startswith("k_huff")}
+    scan_total = sum(s_.scan_bytes for s_ in sb.scans)
+    a, b, c = _spread(va), _spread(vb), _spread(vc)
     bar = min(vb) > max(va) and (b["median"] - a["median"]) > 3 * (a["max"] - a["min"])
+    bar_c = min(vc) > max(vb) and (c["median"] - b["median"]) > 3 * (b["max"] - b["min"])
     print(json.dumps({
         "mode": "gpu", "unit": "images/s", "batch": B, "image": f"{w}x{h} quality-85 4:2:0 synth", "steps_per_leg": steps,
         "decode_threads": threads, "features": list(feats), "A_decode_batch": a, "B_coefficients": b,
-        "A_legs": [round(v, 1) for v in va], "B_legs": [round(v, 1) for v in vb],
+        "C_device_entropy": c,
+        "A_legs": [round(v, 1) for v in va], "B_legs": [round(v, 1) for v in vb], "C_legs": [round(v, 1) for v in vc],
         "B_over_A_medians": round(b["median"] / a["median"], 3), "bar_met": bool(bar),
-        "producer_alone_ms_per_batch": {"A_decode_batch": round(prod_a * 1e3, 1), "B_stage_coefs": round(prod_b * 1e3, 1)},
+        "C_over_B_medians": round(c["median"] / b["median"], 3), "C_bar_met": bool(bar_c),
+        "producer_alone_ms_per_batch": {"A_decode_batch": round(prod_a * 1e3, 1), "B_stage_coefs": round(prod_b * 1e3, 1),
+                                        "C_stage_bytes": round(prod_c * 1e3, 1)},
         "slot_bytes": slot_bytes, "coef_MiB_per_batch": round(B * slot_bytes / 2**20, 1),
-        "h2d_ms_per_batch": _spread(h2d), "kernel_ms_per_batch": kern}))
+        "h2d_ms_per_batch": _spread(h2d), "kernel_ms_per_batch": kern,
+        "C_record_MiB_per_batch": round(B * used / 2**20, 1), "C_scan_MiB_per_batch": round(scan_total / 2**20, 1),
+        "C_subsequences_per_image_max": max(-(-s_.scan_bytes // 128) for s_ in sb.scans),
+        "C_h2d_ms_per_batch": _spread(h2d_c), "C_kernel_ms_per_batch": kern_c,
+        "C_images_taken_by_device": sum(1 for rc in taken if rc == 0)}))
 
 
 def main():
