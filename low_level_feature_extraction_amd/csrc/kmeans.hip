@@ -37,6 +37,7 @@
 #include "kmeans_common.h"
 
 #include <mutex>
+#include <type_traits>
 
 namespace llfe {
 namespace {
@@ -175,6 +176,15 @@ constexpr int SEL_U = 4;
 #define LLFE_KM_UNROLL 2  // failing cubes per push trip (2: the 256-entry ring that fits four
                           // 256-thread workgroups per CU)
 #endif
+#ifndef LLFE_KM_SPLIT_MIN
+#define LLFE_KM_SPLIT_MIN 12  // two-centre failing cubes in a 64-cube batch (cells path) from which the Lloyd
+                              // sweep splits them in place by their bisector (bisector_signs); 65: never.
+                              // Tuning only: both paths give the same sums (sweep: profiles/km_bisector/)
+#endif
+constexpr int kSplitMin = LLFE_KM_SPLIT_MIN;
+// (trace) a lane's split counters in one word: colours below (<= 64 per cube, <= 2^12 batches of a
+// 2^18-cube table per sweep), cubes above
+constexpr int kSplPtsBits = 19;
 #ifndef LLFE_KM_PPRUN
 #define LLFE_KM_PPRUN 4
 #endif
@@ -226,6 +236,7 @@ struct KmSmem {
     int task;                            // work-queue item of the workgroup (persistent launches)
     int next_chunk;                      // next 64-cube chunk to hand out (cube sweeps)
     unsigned long long fail_pts;  // keys read point by point in this Lloyd sweep
+    unsigned long long split_cubes, split_pts;  // (trace) cubes the attempt's sweeps split in place, colours they decided
     // cube-based k-means++ (pp_cubes)
     unsigned long long psum[3][kParts];  // per trial and red-quarter partition: the trial's gain sum(D) - T_j
     unsigned long long pD[kParts];       // per partition: sum of D (the winning trial)
@@ -362,6 +373,70 @@ __device__ __forceinline__ uint32_t lane_offset(int lane) {
 }
 __device__ __forceinline__ uint32_t cube_origin_key(uint32_t id) {
     return ((((id >> 12) & 63u) * 4u) << 16) | ((((id >> 6) & 63u) * 4u) << 8) | ((id & 63u) * 4u);
+}
+
+// ------------------------------------------------------------ bisector split of a two-centre cube
+// A cube that fails the Lloyd margin test against exactly one centre j (owner k) holds only
+// colours OpenCV labels k or j: every other centre is at least 1 farther than c_k on the whole
+// cube in exact arithmetic.  Which of the two is decided by the sign of the linear form
+//     F(u) = d_j(o + u) - d_k(o + u) = a . (2 o - c_j - c_k) + 2 a . u,   a = c_k - c_j,
+// over the cube's 64 positions u (o = the cube origin): F > 0 labels k, F < 0 labels j.  One
+// lane handles one cube: it walks the 64 positions in fixed point (kBisFrac fractional bits)
+// with one add per position and collects the sign bits of kBisBand - F ("surely k") and of
+// F + kBisBand ("surely j") in two 64-bit masks; the colours inside the band |F| <= kBisBand
+// are left to label5p, which also takes the first minimum on an exact tie.
+//
+// The band.  With eps = 2^-24 and centres in [0, 255] (float32, as OpenCV holds them):
+//   a_d = c_k - c_j            |a_d| <= 255, error <= 2^-17 (half an ulp below 256)
+//   b_d = 2 o_d - (c_j + c_k)  |b_d| <= 510, error <= 2^-16 + 2^-16 = 2^-15 (two roundings below 512)
+//   a_d b_d                    inherits 510 x 2^-17 + 255 x 2^-15 < 0.0117 per component, 0.0351 in all
+//   F(0) = a_x b_x, fma, fma   one rounding below 2^17 (2^-8) and two below 2^19 (2^-6 each): 0.0352
+//   fixed point                F(0): half a unit; the three steps 2 a_d: (2^-16 + half a unit) each,
+//                              taken at most 3 times each: (1/2 + 9/2) 2^-10 + 9 x 2^-16 < 0.0051
+// so the walked F differs from the exact form of the float32 centres by less than 0.076 (the adds
+// themselves are integer and exact; |F| 2^10 < 2^29 never overflows).  OpenCV's normL2Sqr at these
+// magnitudes is within 0.04 of the exact distance (three roundings below 2^18, 2^-7 each, and
+// (p - c)^2 from a difference that is off by <= 2^-17: 3 x 510 x 2^-17), so its d_j - d_k has the
+// sign of the exact F wherever |F| > 0.08.  A colour is decided here only when the walked
+// |F| > kBisBand = 0.5, i.e. the exact |F| > 0.424: more than five times what is needed.
+constexpr int kBisFrac = 10;
+constexpr int kBisBand = 1 << (kBisFrac - 1);  // 0.5 in fixed point
+
+// the sign masks of one lane's cube: x | y << 32 = positions with F > band, z | w << 32 = those
+// with F < -band.  p = band - F at position 63 (u = (3, 3, 3)); walking down, b, then j, then i
+// step back by one: s1 = step of b, s2 = step of j less three of b, s3 = step of i less three of
+// j and b (steps of F in fixed point).  A real call: the 64 unrolled positions stay out of the
+// sweep's three inlined cube bodies and its register budget.
+__device__ __noinline__ uint4 bisector_signs(int p, int s1, int s2, int s3) {
+    int n = 2 * kBisBand - p;  // F + band
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int bit = 63; bit >= 0; bit--) {
+        const int h = bit >> 5;
+        w[h] = __builtin_amdgcn_alignbit(w[h], (uint32_t)p, 31);          // (w << 1) | sign(p)
+        w[2 + h] = __builtin_amdgcn_alignbit(w[2 + h], (uint32_t)n, 31);
+        if (bit > 0) {
+            const int s = (bit & 15) == 0 ? s3 : ((bit & 3) == 0 ? s2 : s1);
+            p += s;
+            n -= s;
+        }
+    }
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// n and the sums of u over the positions of mask m (bit = i*16 + j*4 + b): each sum is the
+// popcount of the coordinate's low bit plane plus twice that of its high plane
+struct MaskMoments {
+    uint32_t n, sx, sy, sz;
+};
+__device__ __forceinline__ MaskMoments mask_moments(uint32_t lo, uint32_t hi) {
+    MaskMoments r;
+    const uint32_t nh = __popc(hi);
+    r.n = __popc(lo) + nh;
+    r.sx = __popc(lo & 0xFFFF0000u) + __popc(hi & 0xFFFF0000u) + 2u * nh;
+    r.sy = __popc(lo & 0xF0F0F0F0u) + __popc(hi & 0xF0F0F0F0u) + 2u * (__popc(lo & 0xFF00FF00u) + __popc(hi & 0xFF00FF00u));
+    r.sz = __popc(lo & 0xAAAAAAAAu) + __popc(hi & 0xAAAAAAAAu) + 2u * (__popc(lo & 0xCCCCCCCCu) + __popc(hi & 0xCCCCCCCCu));
+    return r;
 }
 
 // Boundary colours are packed densely into the wave's lanes before they are labelled:
@@ -1336,6 +1411,7 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
             o->n_cubes = 0;
             o->t_sel = 0;
             o->ll_pts = 0;
+            o->split_cubes = o->split_pts = 0;
             o->t_sw = 0;
             o->drift_hist = 0;
             o->pad = 0;
@@ -1365,7 +1441,7 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
     uint64_t t_sel = 0, ll_pts = 0;
     // plain path: k-means++ + compactness passes; the cube path adds what its passes read
     unsigned long long bytes = use_cubes ? 0ull : 4ull * (unsigned long long)N * (unsigned long long)(K + 1);
-    if (tid == 0) sm.fail_pts = 0;
+    if (tid == 0) sm.fail_pts = sm.split_cubes = sm.split_pts = 0;
 #define SSLOT(slot) (ss + (size_t)(slot) * (size_t)M)
 
     if (kPhase & 1) {
@@ -1704,6 +1780,7 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
             uint32_t *stg = sm.stage[wid];
             const uint32_t loff = lane_offset(lane);
             int head = 0, tail = 0;  // wave-uniform ring counters
+            uint32_t spl = 0;        // (trace) per lane: cubes split in place << kSplPtsBits | colours they decided
             auto label_stage = [&](int count) {
                 __builtin_amdgcn_wave_barrier();
                 if (lane < count) {
@@ -1739,9 +1816,12 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
                 if (lane == 0) b = atomicAdd(&sm.next_chunk, 64);
                 return b;  // (lane 0's; read with readfirstlane one chunk later)
             };
-            auto cube_body = [&](const CubeEnt &e, const bool valid) __attribute__((always_inline)) {
-                bool pass = false;
-                int k = 0;
+            // (split_here: the cubes of failing cells, whose batches are dense in failing cubes; the
+            // cubes-only sweep of a small table has one or two per batch and keeps the plain path)
+            auto cube_body = [&](const CubeEnt &e, const bool valid, auto split_here) __attribute__((always_inline)) {
+                constexpr bool kSplitHere = decltype(split_here)::value && kSplitMin <= 64;
+                bool pass = false, two = false;
+                int k = 0, jc = 0;
                 if (valid) {
                     const float qx = (float)((e.id >> 12) & 63u) * 4.f + 1.5f, qy = (float)((e.id >> 6) & 63u) * 4.f + 1.5f,
                                 qz = (float)(e.id & 63u) * 4.f + 1.5f;
@@ -1761,6 +1841,14 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
                     const float *tk = &sm.thrL[0][k * kMaxK];
                     pass = (dv[0] - m1 > tk[0]) & (dv[1] - m1 > tk[1]) & (dv[2] - m1 > tk[2]) &
                            (dv[3] - m1 > tk[3]) & (dv[4] - m1 > tk[4]);
+                    if (kSplitHere) {
+                        // the contenders: the centres that fail the owner's margin row
+                        const uint32_t cm = (uint32_t)(dv[0] - m1 <= tk[0]) | ((uint32_t)(dv[1] - m1 <= tk[1]) << 1) |
+                                            ((uint32_t)(dv[2] - m1 <= tk[2]) << 2) | ((uint32_t)(dv[3] - m1 <= tk[3]) << 3) |
+                                            ((uint32_t)(dv[4] - m1 <= tk[4]) << 4);
+                        two = !pass && (cm & (cm - 1u)) == 0u && cm != 0u;
+                        jc = __builtin_ctz(cm | 32u);
+                    }
                 }
                 if (pass) {
                     const CubeGeo g = cube_geo(e);
@@ -1769,14 +1857,55 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
                     atomicAdd(&sm.accB[k][tid], (unsigned long long)(g.n * g.oz + g.sz) |
                                                     ((unsigned long long)g.n << 32));
                 }
+                bool fail = valid && !pass;
+                uint32_t mlo = (uint32_t)e.mask, mhi = (uint32_t)(e.mask >> 32);
+                // Two-centre cubes (exactly one contender j): when the batch holds enough of them,
+                // each lane splits its own cube by the bisector of c_k and c_j (bisector_signs),
+                // adds the two sides' moments like a passing cube's, and only the colours inside the
+                // band go on to the ring below.
+                if (kSplitHere) {
+                    const unsigned long long tb = __ballot(two);
+                    if (__popcll(tb) >= kSplitMin) {
+                        if (two) {
+                            const int ox = (int)((e.id >> 12) & 63u) * 4, oy = (int)((e.id >> 6) & 63u) * 4,
+                                      oz = (int)(e.id & 63u) * 4;
+                            int p, s1, s2, s3;
+                            {
+                                const float *ck = sm.c[k], *cj = sm.c[jc];
+                                const float ax = ck[0] - cj[0], ay = ck[1] - cj[1], az = ck[2] - cj[2];
+                                const float bx = (float)(2 * ox) - (cj[0] + ck[0]), by = (float)(2 * oy) - (cj[1] + ck[1]),
+                                            bz = (float)(2 * oz) - (cj[2] + ck[2]);
+                                const float f0 = __builtin_fmaf(az, bz, __builtin_fmaf(ay, by, ax * bx));
+                                constexpr float sc = (float)(1 << kBisFrac);
+                                const int gx = (int)__builtin_rintf(ax * (2.f * sc)), gy = (int)__builtin_rintf(ay * (2.f * sc)),
+                                          gz = (int)__builtin_rintf(az * (2.f * sc));
+                                p = kBisBand - ((int)__builtin_rintf(f0 * sc) + 3 * (gx + gy + gz));
+                                s1 = gz;
+                                s2 = gy - 3 * gz;
+                                s3 = gx - 3 * (gy + gz);
+                            }
+                            const uint4 sg = bisector_signs(p, s1, s2, s3);
+                            const MaskMoments a = mask_moments(mlo & sg.x, mhi & sg.y), b = mask_moments(mlo & sg.z, mhi & sg.w);
+                            atomicAdd(&sm.accA[k][tid], (unsigned long long)(a.n * (uint32_t)ox + a.sx) |
+                                                            ((unsigned long long)(a.n * (uint32_t)oy + a.sy) << 32));
+                            atomicAdd(&sm.accB[k][tid], (unsigned long long)(a.n * (uint32_t)oz + a.sz) | ((unsigned long long)a.n << 32));
+                            atomicAdd(&sm.accA[jc][tid], (unsigned long long)(b.n * (uint32_t)ox + b.sx) |
+                                                             ((unsigned long long)(b.n * (uint32_t)oy + b.sy) << 32));
+                            atomicAdd(&sm.accB[jc][tid], (unsigned long long)(b.n * (uint32_t)oz + b.sz) | ((unsigned long long)b.n << 32));
+                            mlo &= ~(sg.x | sg.z);
+                            mhi &= ~(sg.y | sg.w);
+                            fail = (mlo | mhi) != 0u;
+                            spl += (1u << kSplPtsBits) + a.n + b.n;
+                        }
+                    }
+                }
                 // cubes straddling a boundary: their colours (enumerated from the
                 // occupancy mask, no key loads) packed densely into the lanes and
                 // labelled 64 at a time
-                unsigned long long fm = __ballot(valid && !pass);
+                unsigned long long fm = __ballot(fail);
                 // per lane: the origin key of its cube (read back per failing cube with one
                 // readlane instead of rebuilding it in scalar code)
                 const uint32_t okey = cube_origin_key(e.id);
-                const uint32_t mlo = (uint32_t)e.mask, mhi = (uint32_t)(e.mask >> 32);
                 // LLFE_KM_UNROLL failing cubes per trip: independent readlane / mbcnt chains
                 // interleave; the ring (kStage) holds <= 127 pending + UNROLL x 64 new colours
                 auto push = [&](int src) {
@@ -1878,7 +2007,7 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
                             // in flight (integer sums, any order gives the same totals)
                             while (head - tail >= 64) label_stage(64);
 #endif
-                            cube_body(ce, v);
+                            cube_body(ce, v, std::true_type{});
                         }
                         __builtin_amdgcn_wave_barrier();  // (the next batch rewrites the list)
                     }
@@ -1972,7 +2101,7 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
                     const int nb = __builtin_amdgcn_readfirstlane(ahead);
                     if (nb + lane < C) en = ctab[nb + lane];
                     if (nb < C) ahead = grab();
-                    cube_body(e, valid);
+                    cube_body(e, valid, std::false_type{});
                     base = nb;
                 }
             }
@@ -1981,6 +2110,13 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
 #undef LABEL_FULL
             fails = (unsigned long long)head;
             if (lane == 0 && fails) atomicAdd(&sm.fail_pts, fails);
+            if (kSplitMin <= 64 && __ballot(spl != 0u)) {
+                const uint32_t nc = wave_sum(spl >> kSplPtsBits), np = wave_sum(spl & ((1u << kSplPtsBits) - 1u));
+                if (lane == 0) {
+                    atomicAdd(&sm.split_cubes, (unsigned long long)nc);
+                    atomicAdd(&sm.split_pts, (unsigned long long)np);
+                }
+            }
         } else {
         // The sweep is load-latency bound: keep the next PF steps' 16-B loads in flight
         // while the current PF steps are labelled.
@@ -2272,6 +2408,8 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
                 o->t_sel = t_sel;
             }
             o->ll_pts = ll_pts;
+            o->split_cubes = sm.split_cubes;
+            o->split_pts = sm.split_pts;
             o->t_sw = t_sw;
             o->n_cubes = (uint32_t)C;
             o->drift_hist = drift_hist;

@@ -197,6 +197,8 @@ struct KmeansAttemptOut {
     uint32_t pp_pts, n_cubes;  // colours k-means++ read one by one; cube count
     uint64_t t_sel;            // k-means++ time in the selection scans (ticks)
     uint64_t ll_pts;           // colours Lloyd labelled one by one (all sweeps)
+    uint64_t split_cubes;      // two-centre cubes Lloyd split in place by their bisector (all sweeps)
+    uint64_t split_pts;        // ... and the colours that decided without labelling
     uint64_t t_sw;             // Lloyd time in the labelling sweeps (ticks)
     uint64_t drift_hist;       // Lloyd iterations by largest centre move (8 x u8 bins)
     uint64_t qtot;             // sum of |p|^2 over the image's colours (k-means++ -> Lloyd launch)

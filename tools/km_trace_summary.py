@@ -25,6 +25,8 @@ def main():
     t_sel = a.T[14] / 100.0 if a.shape[1] >= 15 else z
     ll_pts = a.T[15] if a.shape[1] >= 16 else z
     t_sw = a.T[16] / 100.0 if a.shape[1] >= 17 else z
+    # cubes split in place by their bisector, colours they decided (0 0 in traces of older builds)
+    sp_cubes, sp_pts = (a.T[17], a.T[18]) if a.shape[1] >= 19 else (z, z)
     dh = a.T[19].astype(np.uint64) if a.shape[1] >= 20 else z.astype(np.uint64)
     ok = it > 1
     pp = (tpp - t0) / 100.0
@@ -39,7 +41,9 @@ def main():
             continue
         print(f"{name:5s} n={m.sum():4d} U={U[m].mean():9.0f} iters={it[m].mean():5.1f}  PP {pp[m].mean()/1e3:6.3f} ms"
               f"  Lloyd {ll[m].mean()/1e3:6.3f} ms ({(ll[m] / (it[m] - 1)).mean():6.1f} us/iter,"
-              f" {np.mean(ll_pts[m] / (it[m] - 1) / U[m]):.3f} of the colours labelled one by one)  compact {cp[m].mean()/1e3:6.3f} ms")
+              f" {np.mean(ll_pts[m] / (it[m] - 1) / U[m]):.3f} of the colours labelled one by one,"
+              f" {np.mean(sp_pts[m] / (it[m] - 1) / U[m]):.3f} decided in {np.mean(sp_cubes[m] / (it[m] - 1)):.0f} split cubes"
+              f" per iteration)  compact {cp[m].mean()/1e3:6.3f} ms")
         if ncub[m].any():
             print(f"      cubes/U {np.mean(ncub[m] / U[m]):.3f}  k-means++ colours read one by one / U"
                   f" {np.mean(pp_pts[m] / U[m]):.3f} (undecided cubes) + {np.mean(pp_sel[m] / U[m]):.3f} (selection);"
