@@ -52,22 +52,8 @@ constexpr int kCellMinCubes = LLFE_KM_CELL_MIN;  // cube count from which the sw
 #ifndef LLFE_KM_LLOYD_QUEUE
 #define LLFE_KM_LLOYD_QUEUE 0  // (split) Lloyd as a work queue too (1) or one workgroup per attempt (0)
 #endif
-#ifndef LLFE_KM_PP_CALL
-#define LLFE_KM_PP_CALL (!LLFE_KM_SPLIT)  // pp_cubes as a call in the one-launch kernel (its register budget)
-#endif  // the sweeps test cells before cubes from this cube count on
 #ifndef LLFE_KM_SUPS
 #define LLFE_KM_SUPS 1  // Lloyd tests 4 x 16 x 16 super-cells before cells
-#endif
-#ifndef LLFE_KM_PP_SUPS
-#define LLFE_KM_PP_SUPS 0  // k-means++ sweeps test 4 x 16 x 16 super-cells before cells (measured slower, also
-                           // with the gain form)
-#endif
-#ifndef LLFE_KM_PP_SUPS_KK
-#define LLFE_KM_PP_SUPS_KK 0  // ... in the rounds with at most this many chosen centres (0: none -- the first round takes no sweep)
-#endif
-#ifndef LLFE_KM_PP_ZSKIP
-#define LLFE_KM_PP_ZSKIP 1  // a partition change whose three gain accumulators are all zero skips its wave
-                            // sums and atomics (a partition far from the trials adds nothing)
 #endif
 #ifndef LLFE_KM_WIDE
 #define LLFE_KM_WIDE 0  // 1: the second build of this file (_build.py: 512 threads, unroll 4) as
@@ -544,15 +530,9 @@ __device__ __forceinline__ uint32_t key_layout(KmSmem &sm, const uint32_t *__res
     return __shfl(kb, P) + (idx - __shfl(pb, P));
 }
 
-// A call in the one-launch kernel (inlined there it spilled 37 VGPRs); inlined into the
-// split build's k-means++ kernel (105 VGPRs, no scratch; as a call that kernel needed 128
-// VGPRs with 2 spilled).
-#if LLFE_KM_PP_CALL
-__device__
-#else
-__device__ __forceinline__
-#endif
-void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, int K, uint64_t &rng,
+// A call, not inlined: that is how the kernel keeps its register budget (inlined it spilled
+// 37 VGPRs).
+__device__ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, int K, uint64_t &rng,
                          const CubeEnt *__restrict__ ctab, int C, const CellEnt *__restrict__ ltab, int L,
                          const SupEnt *__restrict__ stab, int S, const uint32_t *__restrict__ part_uq, const uint32_t *__restrict__ hist,
                          const uint64_t *__restrict__ mom, unsigned long long &bytes, uint32_t &pp_pts, uint32_t &pp_sel, uint64_t &t_sel) {
@@ -1041,8 +1021,9 @@ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, int K, uint64
                 if (Pseg != Pcur) {
                     if (Pcur >= 0) {
                         flush_pk();
-                        // (gains: a partition far from the three trials adds nothing)
-                        if (!LLFE_KM_PP_ZSKIP || __ballot((acc0 | acc1 | acc2) != 0)) {
+                        // (gains: a partition far from the three trials adds nothing, and then skips
+                        // its wave sums and atomics)
+                        if (__ballot((acc0 | acc1 | acc2) != 0)) {
                             const unsigned long long a0 = wave_sum(acc0), a1 = wave_sum(acc1), a2 = wave_sum(acc2);
                             if (lane == 0) {
                                 atomicAdd(&sm.psum[0][Pcur], a0);
@@ -1108,86 +1089,8 @@ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, int K, uint64
                         __builtin_amdgcn_wave_barrier();  // (the list is rewritten next)
                     }
                 };
-                // super-cells only with LLFE_KM_PP_SUPS, or in the rounds up to LLFE_KM_PP_SUPS_KK chosen
-                // centres (measured slower, with the sums and again with the gains, which decide more
-                // super-cells: DESIGN.md §3; the first round takes no sweep)
-                if (stab && (LLFE_KM_PP_SUPS || KK <= LLFE_KM_PP_SUPS_KK)) {
-                    // super-cells first, the same closed forms with extents (3, 15, 15); the
-                    // cells of the undecided ones (one partition at a time) are listed in the wave's
-                    // cell list (sm.cs) and go through the cell path, 64 at a time
-                    const int *MKs = sm.margs, *NAs = sm.margs + kMaxK * kMaxK, *NBs = sm.margs + kMaxK * kMaxK + 3 * kMaxK;
-                    int *qs = sm.cs[wid];
-                    int run = __builtin_amdgcn_readfirstlane(grab());  // the current run's first super-cell
-                    int base = run;
-                    int ahead = grab();
-                    SupEnt en{0u, 0u, 0u, 0u};
-                    if (base + lane < S) en = stab[base + lane];
-                    while (base < S) {
-                        const bool valid = base + lane < S;
-                        const SupEnt e = en;
-                        int nb = base + 64;
-                        if (nb >= run + kRun || nb >= S) {  // (uniform) next run
-                            run = __builtin_amdgcn_readfirstlane(ahead);
-                            nb = run;
-                            if (nb < S) ahead = grab();
-                        }
-                        if (nb + lane < S) en = stab[nb + lane];
-                        const int P = valid ? (int)((e.id >> 8) & 63u) : kParts;
-                        uint32_t v0 = 0, v1 = 0, v2 = 0;
-                        bool fail = false;
-                        if (valid)
-                            box_vals((int)((e.id >> 8) & 63u) * 4, (int)((e.id >> 4) & 15u) * 16, (int)(e.id & 15u) * 16,
-                                     (int)((e.id >> 18) & 2047u), (int)(e.srg & 4095u), (int)(e.srg >> 12),
-                                     (int)(e.sb & 16383u), (int)((e.sb >> 14) | (((e.id >> 29) & 1u) << 18)), MKs, NAs,
-                                     NBs, 3, 15, 15, v0, v1, v2, fail);
-                        // lanes hold ascending super-cell ids: visit the batch's partitions in order
-                        int Pseg = __shfl(P, 0);
-                        for (;;) {
-                            next_part(Pseg);
-                            const bool mine = P == Pseg;
-                            if (mine && !fail) {
-                                acc0 += v0;
-                                acc1 += v1;
-                                acc2 += v2;
-                            }
-                            const bool sf = mine && fail;
-                            const uint32_t c0 = (e.id >> 14) & 3u, ns1 = c0 + ((e.id >> 16) & 3u) - 1u;
-                            const unsigned long long F = __ballot(sf), B0 = __ballot(sf && (ns1 & 1u)),
-                                                     B1 = __ballot(sf && (ns1 & 2u));
-                            if (F) {
-                                const uint32_t pre = mrank(F) + mrank(B0) + 2u * mrank(B1);
-                                const int total = __popcll(F) + __popcll(B0) + 2 * __popcll(B1);
-                                if (sf) {
-    #pragma unroll
-                                    for (uint32_t jj = 0; jj < 4; jj++)
-                                        if (jj <= ns1)
-                                            qs[pre + jj] = (int)(jj < c0 ? (e.first & 0xFFFFu) + jj : (e.first >> 16) + jj - c0);
-                                }
-                                __builtin_amdgcn_wave_barrier();
-                                for (int b = 0; b < total; b += 64) {
-                                    const bool cv = b + lane < total;
-                                    CellEnt ce{0u, 0u, 0u, 0u};
-                                    if (cv) ce = ltab[qs[b + lane]];
-                                    uint32_t c0v = 0, c1v = 0, c2v = 0;
-                                    bool cfail = false;
-                                    if (cv) cell_vals(ce, c0v, c1v, c2v, cfail);
-                                    if (cv && !cfail) {
-                                        acc0 += c0v;
-                                        acc1 += c1v;
-                                        acc2 += c2v;
-                                    }
-                                    cell_cubes(ce, cv && cfail);
-                                }
-                                __builtin_amdgcn_wave_barrier();  // (the list is rewritten next)
-                            }
-                            const unsigned long long rest = __ballot(P > Pseg && P < kParts);
-                            if (!rest) break;
-                            Pseg = __shfl(P, (int)__builtin_ctzll(rest));
-                        }
-                        base = nb;
-                    }
-                } else
-                {
+                // (no super-cell level here: measured slower with the sums and again with the gains,
+                // which decide more super-cells -- DESIGN.md §3)
                 int run = __builtin_amdgcn_readfirstlane(grab());  // the current run's first cell
                 int base = run;
                 int ahead = grab();
@@ -1223,7 +1126,6 @@ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, int K, uint64
                         Pseg = __shfl(P, (int)__builtin_ctzll(rest));
                     }
                     base = nb;
-                }
                 }
             } else {
                 int run = __builtin_amdgcn_readfirstlane(grab());  // the current run's first cube
@@ -1339,25 +1241,9 @@ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, int K, uint64
 // keep the plain path's register-heavy prefetch out of the hot kernels.  (The body stays
 // in the kernel: as an inlined device function the Lloyd sweep lost its register budget
 // and spilled 20 VGPRs.)
-#ifndef LLFE_KM_HIDE
-#define LLFE_KM_HIDE 0  // Lloyd: label staged colours between a list gather's issue and its use
-                        // (bit-identical, measured no faster: 14.54-14.59 vs 14.56-14.62 ms)
-#endif
-#ifndef LLFE_KM_XCD
-#define LLFE_KM_XCD 0  // measured slower: 14.45-14.48 -> 14.61-14.63 ms pipelined
-#endif
-// XCD-aware task order (round 6 experiment): workgroup b runs on XCD b mod 8 (in-order dispatch), and
-// the ten attempts of an image read the same cube / cell / super-cell tables and keys, so the
-// attempts of image slot i (LPT order) all go to XCD i mod 8 -- its r-th workgroup takes
-// attempt r mod 10 of its (r / 10)-th image -- and share that XCD's L2 instead of pulling the
-// tables into all eight.  The tasks of the last n mod 8 images keep their places.
-__device__ __forceinline__ int xcd_task(int b, int n_tasks) {
-    constexpr int X = 8;
-    const int t8 = n_tasks / (X * kAttempts) * (X * kAttempts);
-    if (!LLFE_KM_XCD || b >= t8) return b;
-    const int x = b % X, r = b / X;
-    return (x + X * (r / kAttempts)) * kAttempts + r % kAttempts;
-}
+// Tried and not kept: the attempts of an image on one XCD (task order by b mod 8:
+// slower, 14.45-14.48 -> 14.61-14.63 ms pipelined), and labelling staged colours between a list
+// gather's issue and its use in the Lloyd sweep (no faster, 14.54-14.59 vs 14.56-14.62 ms).
 
 template <bool kCubes, int kPhase, bool kQueue>
 __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__restrict__ keys, long long key_stride,
@@ -1371,7 +1257,7 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     KmSmem &sm = *reinterpret_cast<KmSmem *>(smem_raw);
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    int task = kQueue ? (int)blockIdx.x : xcd_task((int)blockIdx.x, n_tasks);
+    int task = (int)blockIdx.x;
     if (kQueue) {
         if (tid == 0) sm.task = atomicAdd(queue, 1);
         __syncthreads();
@@ -2002,11 +1888,6 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
                             ce.id = 0;
                             ce.sums = 0;
                             if (v) ce = ctab[ql[b + lane]];
-#if LLFE_KM_HIDE
-                            // staged boundary colours need no ce: label them while the gather is
-                            // in flight (integer sums, any order gives the same totals)
-                            while (head - tail >= 64) label_stage(64);
-#endif
                             cube_body(ce, v, std::true_type{});
                         }
                         __builtin_amdgcn_wave_barrier();  // (the next batch rewrites the list)
@@ -2061,9 +1942,6 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
                                 const bool v = b + lane < total;
                                 CellEnt ce{0u, 0u, 0u, 0u};
                                 if (v) ce = ltab[qs[b + lane]];
-#if LLFE_KM_HIDE
-                                while (head - tail >= 64) label_stage(64);  // (as above)
-#endif
                                 cell_body(ce, v);
                             }
                             __builtin_amdgcn_wave_barrier();
