@@ -32,7 +32,9 @@
 // centres cuts it, which the sums themselves could not decide.  Where c_k owns the box and
 // t_j is at least as close everywhere the box adds sum d(., c_k) - sum d(., t_j), in which the
 // sum |p|^2 terms cancel; an undecided cube's colours add max(0, H_t - max_m H_m) (H_c(p) =
-// 2 p.c - |c|^2), again without |p|^2.  All integers: every T_j, every prefix and every
+// 2 p.c - |c|^2), again without |p|^2 -- unless c_k owns the cube and its cells-path batch holds
+// enough such cubes: then the lane sums its own cube in place from the sign mask of the trial's
+// linear form (split_owned / gain_signs below).  All integers: every T_j, every prefix and every
 // choice is bit-identical to the plain sums.
 #include "kmeans_common.h"
 
@@ -168,6 +170,12 @@ constexpr int SEL_U = 4;
                               // Tuning only: both paths give the same sums (sweep: profiles/km_bisector/)
 #endif
 constexpr int kSplitMin = LLFE_KM_SPLIT_MIN;
+#ifndef LLFE_KM_PP_SPLIT_MIN
+#define LLFE_KM_PP_SPLIT_MIN 8  // owned failing cubes in a 64-cube batch (cells path) from which the k-means++ sweep sums them
+                                // in place by the trial's exact linear form (gain_signs); 65: never.
+                                // Tuning only: both paths give the same gains (sweep: profiles/pp_split/)
+#endif
+constexpr int kPPSplitMin = LLFE_KM_PP_SPLIT_MIN;
 // (trace) a lane's split counters in one word: colours below (<= 64 per cube, <= 2^12 batches of a
 // 2^18-cube table per sweep), cubes above
 constexpr int kSplPtsBits = 19;
@@ -425,6 +433,40 @@ __device__ __forceinline__ MaskMoments mask_moments(uint32_t lo, uint32_t hi) {
     return r;
 }
 
+// ------------------------------------------------------------ trial split of an owned cube (k-means++)
+// On a cube that chosen centre c_k owns, D = d(., c_k), so trial t's gain on the colour o + u is
+// max(0, G(u)) with the integer linear form
+//     G(u) = d(o + u, c_k) - d(o + u, t) = -f + 2 (t - c_k) . u,   f = d(o, t) - d(o, c_k),
+// and the cube's gain is n+ (-f) + 2 (t - c_k) . S_u+ over the occupied positions with G > 0 (count
+// n+, offset sums S_u+: mask_moments).  Centres and trials are colours, so nothing is rounded: no
+// band, and a tie G = 0 adds 0 on whichever side it falls.
+//
+// gain_signs: x | y << 32 = the positions with G > 0, one lane per cube.  q = -G at position 63
+// (u = (3, 3, 3)); s1..s3 are the steps of G combined for the walk order as bisector_signs' are.
+// Every walked value is -G at a position of the cube, a difference of two squared distances between
+// colours: |q| <= 3 x 255^2 = 195 075 < 2^18, and |s| <= 2 x 255 x 7 = 3 570: no overflow.  A real
+// call, as bisector_signs is: the 64 unrolled positions exist once, outside the sweep bodies.
+__device__ __noinline__ uint2 gain_signs(int q, int s1, int s2, int s3) {
+    uint32_t w[2] = {0u, 0u};
+#pragma unroll
+    for (int bit = 63; bit >= 0; bit--) {
+        const int h = bit >> 5;
+        w[h] = __builtin_amdgcn_alignbit(w[h], (uint32_t)q, 31);  // (w << 1) | (G > 0)
+        if (bit > 0) q += (bit & 15) == 0 ? s3 : ((bit & 3) == 0 ? s2 : s1);
+    }
+    return make_uint2(w[0], w[1]);
+}
+
+// what box_vals knows about a failing cube that the split needs: the trials that are neither A nor B
+// on a cube its owner candidate owns (bit j; 0 when the cube is not owned), their f, the owner's
+// doubled coordinates
+struct PPSplit {
+    uint32_t und;
+    int f[3];
+    u16x2 krb;
+    int ky;
+};
+
 // Boundary colours are packed densely into the wave's lanes before they are labelled:
 // the colours of cube (m, origin key) go to lanes [fill, fill + popc(m)) of pk (ds_permute
 // push; lane b's rank among the set bits comes from mbcnt).  fill + popc(m) <= 64;
@@ -535,7 +577,8 @@ __device__ __forceinline__ uint32_t key_layout(KmSmem &sm, const uint32_t *__res
 __device__ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, int K, uint64_t &rng,
                          const CubeEnt *__restrict__ ctab, int C, const CellEnt *__restrict__ ltab, int L,
                          const SupEnt *__restrict__ stab, int S, const uint32_t *__restrict__ part_uq, const uint32_t *__restrict__ hist,
-                         const uint64_t *__restrict__ mom, unsigned long long &bytes, uint32_t &pp_pts, uint32_t &pp_sel, uint64_t &t_sel) {
+                         const uint64_t *__restrict__ mom, unsigned long long &bytes, uint32_t &pp_pts, uint32_t &pp_sel, uint64_t &t_sel,
+                         uint32_t &pp_split_cubes, uint32_t &pp_split_pts) {
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const uint32_t c0 = cvrng_next(rng) % (uint32_t)N;  // (every thread advances its rng copy)
     if (wid == 0) {
@@ -791,6 +834,7 @@ __device__ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, in
             if (tid == 0) sm.next_chunk = 0;
             __syncthreads();
             unsigned long long acc0 = 0, acc1 = 0, acc2 = 0, fails = 0;
+            uint32_t spl_cubes = 0, spl_pts = 0;  // (trace) cubes split in place (wave-uniform), their colours (per lane)
             int Pcur = -1;
             // Round constants (wave-uniform).  Every test below is linear in the cube origin o:
             // with D_c(o) = |c|^2 - 2 o.c, d(o, c) = |o|^2 + D_c(o), so
@@ -918,7 +962,7 @@ __device__ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, in
             // margins.
             auto box_vals = [&](int ox, int oy, int oz, int n, int sx, int sy, int sz, int s2, const int *MK,
                                 const int *NAx, const int *NBx, int ex, int ey, int ez, uint32_t &v0, uint32_t &v1,
-                                uint32_t &v2, bool &fail) __attribute__((always_inline)) {
+                                uint32_t &v2, bool &fail, PPSplit *sp) __attribute__((always_inline)) {
                 fail = false;
                 // owner candidate: nearest chosen centre to the box centre q = o + ext / 2:
                 // argmin_m |q - c_m|^2 = argmin_m (D_m(o) - ext . c_m), first minimum.
@@ -975,7 +1019,7 @@ __device__ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, in
                 // < 2^32: n <= 1024 colours of at most 195 075 each).
                 const int sk = sdot(krb, ky);
                 bool dec = true;
-                uint32_t vv[3];
+                uint32_t vv[3], und = 0u;
     #pragma unroll
                 for (int j = 0; j < 3; j++) {
                     const int f = T2[j] - odot(trb[j], tg2[j]) - Dk;
@@ -983,16 +1027,76 @@ __device__ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, in
                     const bool B = f + NBx[j * kMaxK + k] <= 0;  // t_j always at least as close
                     dec = dec & (A | (owned & B));
                     vv[j] = A ? 0u : (uint32_t)(sdot(trb[j], tg2[j]) - sk - __mul24(n, f));
+                    if (sp) {  // (cubes: what the split of an owned failing cube starts from)
+                        sp->f[j] = f;
+                        und |= (uint32_t)(owned & !A & !B) << j;
+                    }
+                }
+                if (sp) {
+                    sp->und = und;
+                    sp->krb = krb;
+                    sp->ky = ky;
                 }
                 v0 = vv[0];
                 v1 = vv[1];
                 v2 = vv[2];
                 fail = !dec;
             };
-            auto cube_vals = [&](const CubeEnt &e, uint32_t &v0, uint32_t &v1, uint32_t &v2,
-                                 bool &fail) __attribute__((always_inline)) {
+            auto cube_vals = [&](const CubeEnt &e, uint32_t &v0, uint32_t &v1, uint32_t &v2, bool &fail,
+                                 PPSplit *sp) __attribute__((always_inline)) {
                 const CubeGeo g = cube_geo(e);
-                box_vals(g.ox, g.oy, g.oz, g.n, g.sx, g.sy, g.sz, g.s2, Mkk, NA, NB, 3, 3, 3, v0, v1, v2, fail);
+                box_vals(g.ox, g.oy, g.oz, g.n, g.sx, g.sy, g.sz, g.s2, Mkk, NA, NB, 3, 3, 3, v0, v1, v2, fail, sp);
+            };
+            // Owned failing cubes (`fail`, false in idle lanes): when the batch holds at least kPPSplitMin
+            // of them each lane sums its own cube in place.  A decided trial adds what a decided cube's
+            // does (A: v = 0, B: the closed form v); an undecided one adds the exact gain over the
+            // positions where it is strictly closer than the owner (gain_signs).  Lanes with a second
+            // or third undecided trial repeat the pass; the others idle through it.  Such a lane
+            // leaves `fail` cleared, the rest go on to push_cubes.
+            auto split_owned = [&](const CubeEnt &e, const PPSplit &sp, uint32_t v0, uint32_t v1, uint32_t v2,
+                                   bool &fail) __attribute__((always_inline)) {
+                if (kPPSplitMin > 64) return;
+                const bool so = fail && sp.und != 0u;
+                const unsigned long long sb = __ballot(so);
+                if (__popcll(sb) < kPPSplitMin) return;
+                spl_cubes += (uint32_t)__popcll(sb);
+                uint32_t und = 0u;
+                if (so) {
+                    und = sp.und;
+                    acc0 += (und & 1u) ? 0u : v0;
+                    acc1 += (und & 2u) ? 0u : v1;
+                    acc2 += (und & 4u) ? 0u : v2;
+                    spl_pts += e.sums & 127u;
+                    fail = false;
+                }
+                const uint32_t mlo = (uint32_t)e.mask, mhi = (uint32_t)(e.mask >> 32);
+                // the trials' doubled (B, R) as one word each (selected per lane below)
+                const uint32_t tw0 = __builtin_bit_cast(uint32_t, trb[0]), tw1 = __builtin_bit_cast(uint32_t, trb[1]),
+                               tw2 = __builtin_bit_cast(uint32_t, trb[2]);
+                const uint32_t kw = __builtin_bit_cast(uint32_t, sp.krb);
+                while (__ballot(und != 0u)) {
+                    if (und) {
+                        // the lane's first undecided trial j as three all-ones / zero words (bit masks,
+                        // not an index: an indexed choice turns the three trials' values into a
+                        // private array in scratch)
+                        const uint32_t m0 = 0u - (und & 1u), m1 = ~m0 & (0u - ((und >> 1) & 1u)), m2 = ~(m0 | m1);
+                        und &= und - 1u;
+                        const int f = (int)(((uint32_t)sp.f[0] & m0) | ((uint32_t)sp.f[1] & m1) | ((uint32_t)sp.f[2] & m2));
+                        const uint32_t tw = (tw0 & m0) | (tw1 & m1) | (tw2 & m2);
+                        const int tg = (int)(((uint32_t)tg2[0] & m0) | ((uint32_t)tg2[1] & m1) | ((uint32_t)tg2[2] & m2));
+                        // the steps of G per axis, 2 (t - c_k), from the doubled constants
+                        const int gx = (int)(tw >> 16) - (int)(kw >> 16), gy = tg - sp.ky,
+                                  gz = (int)(tw & 0xFFFFu) - (int)(kw & 0xFFFFu);
+                        const uint2 pos = gain_signs(f - 3 * (gx + gy + gz), gz, gy - 3 * gz, gx - 3 * (gy + gz));
+                        const MaskMoments a = mask_moments(mlo & pos.x, mhi & pos.y);
+                        // 0 <= gain <= 64 x 195 075; every factor fits 24 bits
+                        const uint32_t g = (uint32_t)(__mul24(gx, (int)a.sx) + __mul24(gy, (int)a.sy) + __mul24(gz, (int)a.sz) -
+                                                      __mul24((int)a.n, f));
+                        acc0 += g & m0;
+                        acc1 += g & m1;
+                        acc2 += g & m2;
+                    }
+                }
             };
             // undecided cubes among the lanes of `fm`: their colours (enumerated from the
             // occupancy mask) packed densely into the lanes, summed 64 at a time
@@ -1052,7 +1156,7 @@ __device__ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, in
                                      bool &fail) __attribute__((always_inline)) {
                     box_vals((int)((e.id >> 10) & 63u) * 4, (int)((e.id >> 5) & 31u) * 8, (int)(e.id & 31u) * 8,
                              (int)((e.id >> 18) & 511u), (int)(e.sums & 1023u), (int)((e.sums >> 10) & 2047u),
-                             (int)(e.sums >> 21), (int)e.s2, MKc, NAc, NBc, 3, 7, 7, v0, v1, v2, fail);
+                             (int)(e.sums >> 21), (int)e.s2, MKc, NAc, NBc, 3, 7, 7, v0, v1, v2, fail, nullptr);
                 };
                 // the failing cells among the lanes of cf (one partition): their cubes, 64 at a time
                 auto cell_cubes = [&](const CellEnt &e, const bool cf) __attribute__((always_inline)) {
@@ -1077,12 +1181,15 @@ __device__ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, in
                             if (cv) ce = ctab[ql[b + lane]];
                             uint32_t c0 = 0, c1 = 0, c2 = 0;
                             bool cfail = false;
-                            if (cv) cube_vals(ce, c0, c1, c2, cfail);
+                            PPSplit sp;
+                            sp.und = 0u;
+                            if (cv) cube_vals(ce, c0, c1, c2, cfail, &sp);
                             if (cv && !cfail) {
                                 acc0 += c0;
                                 acc1 += c1;
                                 acc2 += c2;
                             }
+                            split_owned(ce, sp, c0, c1, c2, cfail);
                             const unsigned long long fm = __ballot(cv && cfail);
                             if (fm) push_cubes(fm, ce);
                         }
@@ -1149,7 +1256,7 @@ __device__ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, in
                     const int P = valid ? (int)((e.id >> 12) & 63u) : kParts;
                     uint32_t v0 = 0, v1 = 0, v2 = 0;
                     bool fail = false;
-                    if (valid) cube_vals(e, v0, v1, v2, fail);
+                    if (valid) cube_vals(e, v0, v1, v2, fail, nullptr);
                     // lanes hold ascending cube ids: visit the batch's partitions in order
                     int Pseg = __shfl(P, 0);
                     for (;;) {
@@ -1160,6 +1267,8 @@ __device__ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, in
                             acc1 += v1;
                             acc2 += v2;
                         }
+                        // (no split here: a small table's batches seldom hold kPPSplitMin owned failing cubes,
+                        // and with it the ui class measured slower, profiles/pp_split/)
                         const unsigned long long fm = __ballot(mine && fail);
                         if (fm) push_cubes(fm, e);
                         const unsigned long long rest = __ballot(P > Pseg && P < kParts);
@@ -1179,6 +1288,13 @@ __device__ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, in
                 }
             }
             if (lane == 0 && fails) atomicAdd(&sm.fail_pts, fails);
+            if (spl_cubes) {  // (uniform; kept in Lloyd's counters, which pp_cubes hands back zeroed)
+                const uint32_t np = wave_sum(spl_pts);
+                if (lane == 0) {
+                    atomicAdd(&sm.split_cubes, (unsigned long long)spl_cubes);
+                    atomicAdd(&sm.split_pts, (unsigned long long)np);
+                }
+            }
         };
         switch (kk) {
             case 1: sweep(std::integral_constant<int, 1>{}); break;
@@ -1222,7 +1338,9 @@ __device__ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, in
         bytes += 16ull * (unsigned long long)C * (unsigned long long)K + 4ull * sm.sel_pts;
         pp_pts = (uint32_t)sm.fail_pts;
         pp_sel = (uint32_t)sm.sel_pts;
-        sm.fail_pts = 0;
+        pp_split_cubes = (uint32_t)sm.split_cubes;
+        pp_split_pts = (uint32_t)sm.split_pts;
+        sm.fail_pts = sm.split_cubes = sm.split_pts = 0;
     }
     __syncthreads();
 }
@@ -1294,6 +1412,7 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
             o->iters = 0;
             o->bytes = 0;
             o->pp_pts = 0;
+            o->pp_split_cubes = o->pp_split_pts = 0;
             o->n_cubes = 0;
             o->t_sel = 0;
             o->ll_pts = 0;
@@ -1323,7 +1442,7 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
     constexpr bool use_cubes = kCubes;
     const int C = use_cubes ? cubes.n_cubes[img] : 0;
     const CubeEnt *ctab = use_cubes ? cubes.cubes + (size_t)img * cubes.cube_stride : nullptr;
-    uint32_t pp_pts = 0, pp_sel = 0;
+    uint32_t pp_pts = 0, pp_sel = 0, pp_split_cubes = 0, pp_split_pts = 0;
     uint64_t t_sel = 0, ll_pts = 0;
     // plain path: k-means++ + compactness passes; the cube path adds what its passes read
     unsigned long long bytes = use_cubes ? 0ull : 4ull * (unsigned long long)N * (unsigned long long)(K + 1);
@@ -1340,7 +1459,7 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
         pp_cubes(sm, pts, N, K, rng, ctab, C, cubes.cells + (size_t)img * cubes.cell_stride, cubes.n_cells[img],
                  cubes.sups ? cubes.sups + (size_t)img * cubes.sup_stride : nullptr, cubes.sups ? cubes.n_sups[img] : 0,
                  cubes.part_uq + (size_t)img * kParts, cubes.part_hist ? cubes.part_hist + (size_t)img * kParts : nullptr,
-                 cubes.moments + (size_t)img * kPartMoments * kParts, bytes, pp_pts, pp_sel, t_sel);
+                 cubes.moments + (size_t)img * kPartMoments * kParts, bytes, pp_pts, pp_sel, t_sel, pp_split_cubes, pp_split_pts);
     } else {
     int cur = 0;
     {
@@ -1566,6 +1685,8 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
             o->qtot = sm.qtot;
             o->bytes = bytes;
             o->pp_pts = pp_pts;
+            o->pp_split_cubes = pp_split_cubes;
+            o->pp_split_pts = pp_split_pts;
             o->pad = (int32_t)pp_sel;
             o->t_sel = t_sel;
         }
@@ -2282,6 +2403,8 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
             o->bytes = bytes;
             if (kPhase & 1) {
                 o->pp_pts = pp_pts;
+                o->pp_split_cubes = pp_split_cubes;
+                o->pp_split_pts = pp_split_pts;
                 o->pad = (int32_t)pp_sel;
                 o->t_sel = t_sel;
             }

@@ -463,6 +463,7 @@ __global__ __launch_bounds__(BT) void k_kmeans_big(const uint32_t *__restrict__ 
         o->iters = iter;
         o->bytes = 4ull * (unsigned long long)N * (unsigned long long)(K + iter);
         o->pp_pts = 0;
+        o->pp_split_cubes = o->pp_split_pts = 0;
         o->pad = 0;
         o->n_cubes = 0;
         o->t_sel = 0;

@@ -27,6 +27,8 @@ def main():
     t_sw = a.T[16] / 100.0 if a.shape[1] >= 17 else z
     # cubes split in place by their bisector, colours they decided (0 0 in traces of older builds)
     sp_cubes, sp_pts = (a.T[17], a.T[18]) if a.shape[1] >= 19 else (z, z)
+    # owned straddling cubes k-means++ summed in place, their colours (the line's last two columns)
+    pps_cubes, pps_pts = (a.T[23], a.T[24]) if a.shape[1] >= 25 else (z, z)
     dh = a.T[19].astype(np.uint64) if a.shape[1] >= 20 else z.astype(np.uint64)
     ok = it > 1
     pp = (tpp - t0) / 100.0
@@ -48,6 +50,8 @@ def main():
             print(f"      cubes/U {np.mean(ncub[m] / U[m]):.3f}  k-means++ colours read one by one / U"
                   f" {np.mean(pp_pts[m] / U[m]):.3f} (undecided cubes) + {np.mean(pp_sel[m] / U[m]):.3f} (selection);"
                   f" selection time {t_sel[m].mean() / 1e3:.3f} ms; Lloyd sweeps {t_sw[m].mean() / 1e3:.3f} ms")
+            print(f"      k-means++ split in place: {pps_cubes[m].mean():.0f} cubes, {np.mean(pps_pts[m] / U[m]):.3f} U of colours per attempt"
+                  f" (sums over the class: {pps_cubes[m].sum()} cubes, {pps_pts[m].sum()} colours)")
         if dh[m].any():
             bins = np.stack([((dh[m] >> np.uint64(8 * b)) & np.uint64(255)).astype(np.int64) for b in range(8)], 1)
             print("      iterations by largest centre move [<.25 <.5 <1 <2 <4 <8 <16 >=16]:",
