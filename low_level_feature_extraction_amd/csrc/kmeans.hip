@@ -24,7 +24,7 @@
 //
 // k-means++ trial sums as gains (pp_cubes).  A round needs T_j = sum_p min(D(p), d(p, t_j))
 // per trial, in total and per red-quarter partition; the round before left sum(D) exactly
-// (sum0, sm.pD[P]), so the sweep accumulates g_j = sum_p max(0, D(p) - d(p, t_j)) and the
+// (sum0, sm.ppw.pD[P]), so the sweep accumulates g_j = sum_p max(0, D(p) - d(p, t_j)) and the
 // round end takes T_j = sum(D) - g_j, pD[P] -= g_best[P].  g_j is non-zero only where t_j
 // is strictly closer than every chosen centre: on a box (cube, cell, super-cell) where t_j
 // is never strictly closer than the chosen centre c_k nearest to the box centre,
@@ -165,20 +165,21 @@ constexpr int SEL_U = 4;
                           // 256-thread workgroups per CU)
 #endif
 #ifndef LLFE_KM_SPLIT_MIN
-#define LLFE_KM_SPLIT_MIN 12  // two-centre failing cubes in a 64-cube batch (cells path) from which the Lloyd
-                              // sweep splits them in place by their bisector (bisector_signs); 65: never.
-                              // Tuning only: both paths give the same sums (sweep: profiles/km_bisector/)
+#define LLFE_KM_SPLIT_MIN 1  // <= 64: the Lloyd sweep lists every two-centre failing cube of the cells path and splits
+                             // them 64 at a time by their bisector (split_drain); 65: never (all go to the ring).
+                             // Both give the same sums
 #endif
-constexpr int kSplitMin = LLFE_KM_SPLIT_MIN;
+constexpr bool kSplitOn = LLFE_KM_SPLIT_MIN <= 64;
+// per-wave LDS list of two-centre cubes awaiting their walk (a ring, indices masked): drained at 64, so it
+// holds <= 63 pending + the 64 of one cube batch.  Entry: cube index (< 2^18) | owner k << 18 | contender j << 21
+constexpr int kPend = 128;
+constexpr int kPendIdxBits = 18;
 #ifndef LLFE_KM_PP_SPLIT_MIN
 #define LLFE_KM_PP_SPLIT_MIN 8  // owned failing cubes in a 64-cube batch (cells path) from which the k-means++ sweep sums them
                                 // in place by the trial's exact linear form (gain_signs); 65: never.
                                 // Tuning only: both paths give the same gains (sweep: profiles/pp_split/)
 #endif
 constexpr int kPPSplitMin = LLFE_KM_PP_SPLIT_MIN;
-// (trace) a lane's split counters in one word: colours below (<= 64 per cube, <= 2^12 batches of a
-// 2^18-cube table per sweep), cubes above
-constexpr int kSplPtsBits = 19;
 #ifndef LLFE_KM_PPRUN
 #define LLFE_KM_PPRUN 4
 #endif
@@ -231,9 +232,22 @@ struct KmSmem {
     int next_chunk;                      // next 64-cube chunk to hand out (cube sweeps)
     unsigned long long fail_pts;  // keys read point by point in this Lloyd sweep
     unsigned long long split_cubes, split_pts;  // (trace) cubes the attempt's sweeps split in place, colours they decided
+    uint32_t split_walks, split_partial;        // (trace) ... in this many 64-lane walks, these of them not full
     // cube-based k-means++ (pp_cubes)
-    unsigned long long psum[3][kParts];  // per trial and red-quarter partition: the trial's gain sum(D) - T_j
-    unsigned long long pD[kParts];       // per partition: sum of D (the winning trial)
+    union {
+        struct {
+            unsigned long long psum[3][kParts];  // per trial and red-quarter partition: the trial's gain sum(D) - T_j
+            unsigned long long pD[kParts];       // per partition: sum of D (the winning trial)
+            unsigned long long wchunk[3][KW];    // per trial: sum of D over each wave's chunk
+            int marg[kMaxK * kMaxK + 6 * kMaxK]; // k-means++ corner margins: centre pairs, trial vs centre (+/-)
+            int margc[kMaxK * kMaxK + 6 * kMaxK];  // the same for the 4 x 8 x 8 cells
+            int margs[kMaxK * kMaxK + 6 * kMaxK];  // ... and the 4 x 16 x 16 super-cells
+        } ppw;
+        // (Lloyd sweep) per-wave list of two-centre cubes awaiting their walk.  The fields above live only
+        // inside pp_cubes, which writes each before it reads it: pD from the partition moments at its start,
+        // psum, the margins and the chunk sums in every round
+        uint32_t pend[KW][kPend];
+    };
     unsigned long long pex[3];
     unsigned long long S[3];
     uint32_t pbase[kParts + 1];          // first sorted key of each partition (np.unique index)
@@ -243,14 +257,10 @@ struct KmSmem {
     int pj[3];
     int icc[kMaxK][3];                   // chosen centres (integer colours)
     unsigned long long sel_pts;          // colours the selection scans read
-    unsigned long long wchunk[3][KW];    // per trial: sum of D over each wave's chunk
     uint32_t stage[KW][kStage + 64];     // per-wave ring of boundary colours (+ a dummy row)
     float thrL[3][kMaxK * kMaxK];        // Lloyd margin thresholds [cube / cell / super-cell][owner k][j]
     int cq[KW][256];                     // per-wave list of the cubes of a chunk's failing cells
     unsigned long long qtot;             // sum of |p|^2 over all colours (exact)
-    int marg[kMaxK * kMaxK + 6 * kMaxK]; // k-means++ corner margins: centre pairs, trial vs centre (+/-)
-    int margc[kMaxK * kMaxK + 6 * kMaxK];  // the same for the 4 x 8 x 8 cells
-    int margs[kMaxK * kMaxK + 6 * kMaxK];  // ... and the 4 x 16 x 16 super-cells
 };
 
 // 1024 / KT workgroups per CU (160 KB of LDS): two of 512 threads, four of 256
@@ -259,6 +269,11 @@ static_assert(sizeof(KmSmem) * (1024 / KT) <= 160 * 1024, "KmSmem must leave roo
 static_assert(offsetof(KmSmem, accB) == sizeof(((KmSmem *)nullptr)->accA) &&
                   3 * KW * kSelSteps * sizeof(uint32_t) <= 2 * sizeof(((KmSmem *)nullptr)->accA),
               "selection step sums overflow the Lloyd accumulators (KT too small)");
+// neither build has the LDS for the pending-cube lists: they alias k-means++ state (KmSmem::ppw).  The four-wave
+// build's fit inside it; the eight-wave build's are larger and take what its two workgroups per CU leave free
+static_assert(KW > 4 || sizeof(((KmSmem *)nullptr)->pend) <= sizeof(((KmSmem *)nullptr)->ppw),
+              "pending-cube lists overflow the k-means++ state they alias");
+static_assert(kPend >= 63 + 64 && (kPend & (kPend - 1)) == 0, "pending-cube list too small");
 
 __device__ __forceinline__ Cent load_centres(const float (*c)[3]) {
     Cent r;
@@ -399,9 +414,8 @@ constexpr int kBisBand = 1 << (kBisFrac - 1);  // 0.5 in fixed point
 // the sign masks of one lane's cube: x | y << 32 = positions with F > band, z | w << 32 = those
 // with F < -band.  p = band - F at position 63 (u = (3, 3, 3)); walking down, b, then j, then i
 // step back by one: s1 = step of b, s2 = step of j less three of b, s3 = step of i less three of
-// j and b (steps of F in fixed point).  A real call: the 64 unrolled positions stay out of the
-// sweep's three inlined cube bodies and its register budget.
-__device__ __noinline__ uint4 bisector_signs(int p, int s1, int s2, int s3) {
+// j and b (steps of F in fixed point).  Inlined into split_drain, its one caller.
+__device__ __forceinline__ uint4 bisector_signs(int p, int s1, int s2, int s3) {
     int n = 2 * kBisBand - p;  // F + band
     uint32_t w[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
@@ -433,6 +447,53 @@ __device__ __forceinline__ MaskMoments mask_moments(uint32_t lo, uint32_t hi) {
     return r;
 }
 
+// One 64-lane walk of the Lloyd sweep: lane < n takes entry first + lane of its wave's pending list `pl`
+// (KmSmem::pend), gathers the cube, splits it by the bisector of its owner k and contender j (centres in
+// sm.c) and adds the two sides' moments to its own accumulator slots like a passing cube's.  Returns what
+// the caller still has to label one by one and count: x | y << 32 = the occupied positions inside the band,
+// z = the cube's origin key, w = the colours decided here (zeros for lane >= n).  Inlined at the sweep's three
+// drain sites (the two cells-path cube bodies and the sweep-end flush): as a real call it kept the walk once per
+// kernel but cost the cube loops their caller-saved registers, 35.4k against 36.4k images/s (profiles/km_compact/).
+__device__ __forceinline__ uint4 split_drain(KmSmem &sm, const CubeEnt *__restrict__ ctab, const uint32_t *pl, int first, int n) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    uint4 r = make_uint4(0u, 0u, 0u, 0u);
+    if (lane < n) {
+        const uint32_t ent = pl[(first + lane) & (kPend - 1)];
+        const CubeEnt e = ctab[ent & ((1u << kPendIdxBits) - 1u)];
+        const int k = (int)((ent >> kPendIdxBits) & 7u), jc = (int)(ent >> (kPendIdxBits + 3));
+        const int ox = (int)((e.id >> 12) & 63u) * 4, oy = (int)((e.id >> 6) & 63u) * 4, oz = (int)(e.id & 63u) * 4;
+        int p, s1, s2, s3;
+        {
+            const float *ck = sm.c[k], *cj = sm.c[jc];
+            const float ax = ck[0] - cj[0], ay = ck[1] - cj[1], az = ck[2] - cj[2];
+            const float bx = (float)(2 * ox) - (cj[0] + ck[0]), by = (float)(2 * oy) - (cj[1] + ck[1]),
+                        bz = (float)(2 * oz) - (cj[2] + ck[2]);
+            const float f0 = __builtin_fmaf(az, bz, __builtin_fmaf(ay, by, ax * bx));
+            constexpr float sc = (float)(1 << kBisFrac);
+            const int gx = (int)__builtin_rintf(ax * (2.f * sc)), gy = (int)__builtin_rintf(ay * (2.f * sc)),
+                      gz = (int)__builtin_rintf(az * (2.f * sc));
+            p = kBisBand - ((int)__builtin_rintf(f0 * sc) + 3 * (gx + gy + gz));
+            s1 = gz;
+            s2 = gy - 3 * gz;
+            s3 = gx - 3 * (gy + gz);
+        }
+        const uint32_t mlo = (uint32_t)e.mask, mhi = (uint32_t)(e.mask >> 32);
+        const uint4 sg = bisector_signs(p, s1, s2, s3);
+        const MaskMoments a = mask_moments(mlo & sg.x, mhi & sg.y), b = mask_moments(mlo & sg.z, mhi & sg.w);
+        atomicAdd(&sm.accA[k][tid], (unsigned long long)(a.n * (uint32_t)ox + a.sx) |
+                                        ((unsigned long long)(a.n * (uint32_t)oy + a.sy) << 32));
+        atomicAdd(&sm.accB[k][tid], (unsigned long long)(a.n * (uint32_t)oz + a.sz) | ((unsigned long long)a.n << 32));
+        atomicAdd(&sm.accA[jc][tid], (unsigned long long)(b.n * (uint32_t)ox + b.sx) |
+                                         ((unsigned long long)(b.n * (uint32_t)oy + b.sy) << 32));
+        atomicAdd(&sm.accB[jc][tid], (unsigned long long)(b.n * (uint32_t)oz + b.sz) | ((unsigned long long)b.n << 32));
+        r.x = mlo & ~(sg.x | sg.z);
+        r.y = mhi & ~(sg.y | sg.w);
+        r.z = cube_origin_key(e.id);
+        r.w = a.n + b.n;
+    }
+    return r;
+}
+
 // ------------------------------------------------------------ trial split of an owned cube (k-means++)
 // On a cube that chosen centre c_k owns, D = d(., c_k), so trial t's gain on the colour o + u is
 // max(0, G(u)) with the integer linear form
@@ -445,7 +506,7 @@ __device__ __forceinline__ MaskMoments mask_moments(uint32_t lo, uint32_t hi) {
 // (u = (3, 3, 3)); s1..s3 are the steps of G combined for the walk order as bisector_signs' are.
 // Every walked value is -G at a position of the cube, a difference of two squared distances between
 // colours: |q| <= 3 x 255^2 = 195 075 < 2^18, and |s| <= 2 x 255 x 7 = 3 570: no overflow.  A real
-// call, as bisector_signs is: the 64 unrolled positions exist once, outside the sweep bodies.
+// call: the 64 unrolled positions exist once, outside the sweep bodies.
 __device__ __noinline__ uint2 gain_signs(int q, int s1, int s2, int s3) {
     uint32_t w[2] = {0u, 0u};
 #pragma unroll
@@ -610,7 +671,7 @@ __device__ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, in
         const unsigned long long cx = (unsigned long long)sm.icc[0][0], cy = (unsigned long long)sm.icc[0][1],
                                  cz = (unsigned long long)sm.icc[0][2];
         const unsigned long long d = mq[4] + mq[0] * (cx * cx + cy * cy + cz * cz) - 2ull * (cx * mq[1] + cy * mq[2] + cz * mq[3]);
-        sm.pD[lane] = d;
+        sm.ppw.pD[lane] = d;
         const unsigned long long s = wave_sum(d), qt = wave_sum(mq[4]);
         if (lane == 0) {
             sm.S[0] = s;
@@ -636,7 +697,7 @@ __device__ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, in
             for (int j = 0; j < 3; j++) p[j] = cvrng_double(rng) * (double)sum0;
             // ---- partition holding prefix(D) >= p_j
             if (wid == 0) {
-                const unsigned long long v = sm.pD[lane];
+                const unsigned long long v = sm.ppw.pD[lane];
                 unsigned long long x = v;
 #pragma unroll
                 for (int off = 1; off < 64; off <<= 1) {
@@ -722,7 +783,7 @@ __device__ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, in
     #pragma unroll
                     for (int j = 0; j < 3; j++) {
                         const unsigned long long ws = wave_sum((unsigned long long)csum_lo[j]);
-                        if (lane == 0) sm.wchunk[j][wid] = ws;
+                        if (lane == 0) sm.ppw.wchunk[j][wid] = ws;
                     }
                     if (lane == 0) atomicAdd(&sm.sel_pts, cnt);
                 }
@@ -743,8 +804,8 @@ __device__ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, in
                         unsigned long long e = sm.pex[j];
                         int w = 0;
                         for (; w < KW - 1; w++) {
-                            if ((double)(e + sm.wchunk[src][w]) >= pj) break;
-                            e += sm.wchunk[src][w];
+                            if ((double)(e + sm.ppw.wchunk[src][w]) >= pj) break;
+                            e += sm.ppw.wchunk[src][w];
                         }
                         const uint32_t w0 = A + min(nst, (uint32_t)w * per) * STEP, w1 = A + min(nst, (uint32_t)(w + 1) * per) * STEP;
                         const int ns = (int)((w1 - w0) / STEP);
@@ -830,7 +891,7 @@ __device__ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, in
         // the centre loops become straight-line code without per-centre guards
         auto sweep = [&](auto KKc) __attribute__((always_inline)) {
             constexpr int KK = decltype(KKc)::value;
-            if (tid < 3 * kParts) (&sm.psum[0][0])[tid] = 0;
+            if (tid < 3 * kParts) (&sm.ppw.psum[0][0])[tid] = 0;
             if (tid == 0) sm.next_chunk = 0;
             __syncthreads();
             unsigned long long acc0 = 0, acc1 = 0, acc2 = 0, fails = 0;
@@ -899,7 +960,7 @@ __device__ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, in
             };
             if (tid < kMaxK * kMaxK) {  // Mkk[m][k] = 6 sum max(c_m - c_k, 0)
                 const int m = tid / kMaxK, k2 = tid % kMaxK;
-                sm.marg[tid] = 6 * (max(sm.icc[m][0] - sm.icc[k2][0], 0) + max(sm.icc[m][1] - sm.icc[k2][1], 0) +
+                sm.ppw.marg[tid] = 6 * (max(sm.icc[m][0] - sm.icc[k2][0], 0) + max(sm.icc[m][1] - sm.icc[k2][1], 0) +
                                     max(sm.icc[m][2] - sm.icc[k2][2], 0));
             } else if (tid < kMaxK * kMaxK + 6 * kMaxK) {  // NA[j][k], NB[j][k]
                 const int q = tid - kMaxK * kMaxK, j = (q / kMaxK) % 3, k2 = q % kMaxK;
@@ -909,38 +970,38 @@ __device__ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, in
                 int acc = 0;
     #pragma unroll
                 for (int d = 0; d < 3; d++) acc += max(sg * (t[d] - sm.icc[k2][d]), 0);
-                sm.marg[tid] = 6 * acc;
+                sm.ppw.marg[tid] = 6 * acc;
             }
             // the same corner margins for a 4 x 8 x 8 cell: 2 (3, 7, 7) . max(+-(a - b), 0)
             if (tid >= 64 && tid < 64 + kMaxK * kMaxK) {
                 const int q = tid - 64, m = q / kMaxK, k2 = q % kMaxK;
-                sm.margc[q] = 6 * max(sm.icc[m][0] - sm.icc[k2][0], 0) + 14 * max(sm.icc[m][1] - sm.icc[k2][1], 0) +
+                sm.ppw.margc[q] = 6 * max(sm.icc[m][0] - sm.icc[k2][0], 0) + 14 * max(sm.icc[m][1] - sm.icc[k2][1], 0) +
                               14 * max(sm.icc[m][2] - sm.icc[k2][2], 0);
             } else if (tid >= 64 + kMaxK * kMaxK && tid < 64 + kMaxK * kMaxK + 6 * kMaxK) {
                 const int q = tid - 64 - kMaxK * kMaxK, j = (q / kMaxK) % 3, k2 = q % kMaxK;
                 const int t[3] = {j == 0 ? tx[0] : (j == 1 ? tx[1] : tx[2]), j == 0 ? ty[0] : (j == 1 ? ty[1] : ty[2]),
                                   j == 0 ? tz[0] : (j == 1 ? tz[1] : tz[2])};
                 const int sg = q < 3 * kMaxK ? 1 : -1;
-                sm.margc[kMaxK * kMaxK + q] = 6 * max(sg * (t[0] - sm.icc[k2][0]), 0) +
+                sm.ppw.margc[kMaxK * kMaxK + q] = 6 * max(sg * (t[0] - sm.icc[k2][0]), 0) +
                                               14 * max(sg * (t[1] - sm.icc[k2][1]), 0) +
                                               14 * max(sg * (t[2] - sm.icc[k2][2]), 0);
             }
             // ... and for a 4 x 16 x 16 super-cell: 2 (3, 15, 15) . max(+-(a - b), 0)
             if (tid >= 128 && tid < 128 + kMaxK * kMaxK) {
                 const int q = tid - 128, m = q / kMaxK, k2 = q % kMaxK;
-                sm.margs[q] = 6 * max(sm.icc[m][0] - sm.icc[k2][0], 0) + 30 * max(sm.icc[m][1] - sm.icc[k2][1], 0) +
+                sm.ppw.margs[q] = 6 * max(sm.icc[m][0] - sm.icc[k2][0], 0) + 30 * max(sm.icc[m][1] - sm.icc[k2][1], 0) +
                               30 * max(sm.icc[m][2] - sm.icc[k2][2], 0);
             } else if (tid >= 128 + kMaxK * kMaxK && tid < 128 + kMaxK * kMaxK + 6 * kMaxK) {
                 const int q = tid - 128 - kMaxK * kMaxK, j = (q / kMaxK) % 3, k2 = q % kMaxK;
                 const int t[3] = {j == 0 ? tx[0] : (j == 1 ? tx[1] : tx[2]), j == 0 ? ty[0] : (j == 1 ? ty[1] : ty[2]),
                                   j == 0 ? tz[0] : (j == 1 ? tz[1] : tz[2])};
                 const int sg = q < 3 * kMaxK ? 1 : -1;
-                sm.margs[kMaxK * kMaxK + q] = 6 * max(sg * (t[0] - sm.icc[k2][0]), 0) +
+                sm.ppw.margs[kMaxK * kMaxK + q] = 6 * max(sg * (t[0] - sm.icc[k2][0]), 0) +
                                               30 * max(sg * (t[1] - sm.icc[k2][1]), 0) +
                                               30 * max(sg * (t[2] - sm.icc[k2][2]), 0);
             }
             __syncthreads();
-            const int *Mkk = sm.marg, *NA = sm.marg + kMaxK * kMaxK, *NB = sm.marg + kMaxK * kMaxK + 3 * kMaxK;
+            const int *Mkk = sm.ppw.marg, *NA = sm.ppw.marg + kMaxK * kMaxK, *NB = sm.ppw.marg + kMaxK * kMaxK + 3 * kMaxK;
             // waves take 64-cube chunks from a shared LDS counter, read two chunks ahead
             // (ascending per wave, so the partition bookkeeping below still sees its
             // partitions in order)
@@ -1130,9 +1191,9 @@ __device__ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, in
                         if (__ballot((acc0 | acc1 | acc2) != 0)) {
                             const unsigned long long a0 = wave_sum(acc0), a1 = wave_sum(acc1), a2 = wave_sum(acc2);
                             if (lane == 0) {
-                                atomicAdd(&sm.psum[0][Pcur], a0);
-                                atomicAdd(&sm.psum[1][Pcur], a1);
-                                atomicAdd(&sm.psum[2][Pcur], a2);
+                                atomicAdd(&sm.ppw.psum[0][Pcur], a0);
+                                atomicAdd(&sm.ppw.psum[1][Pcur], a1);
+                                atomicAdd(&sm.ppw.psum[2][Pcur], a2);
                             }
                         }
                     }
@@ -1147,7 +1208,7 @@ __device__ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, in
                 // cells first: a decided cell adds its closed forms; the cubes of the undecided
                 // cells of a chunk (per partition) are listed in the wave's LDS list and go through
                 // the cube path above, 64 at a time
-                const int *MKc = sm.margc, *NAc = sm.margc + kMaxK * kMaxK, *NBc = sm.margc + kMaxK * kMaxK + 3 * kMaxK;
+                const int *MKc = sm.ppw.margc, *NAc = sm.ppw.margc + kMaxK * kMaxK, *NBc = sm.ppw.margc + kMaxK * kMaxK + 3 * kMaxK;
                 int *ql = sm.cq[wid];
                 auto mrank = [&](unsigned long long m) {
                     return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
@@ -1282,9 +1343,9 @@ __device__ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, in
                 flush_pk();
                 const unsigned long long a0 = wave_sum(acc0), a1 = wave_sum(acc1), a2 = wave_sum(acc2);
                 if (lane == 0) {
-                    atomicAdd(&sm.psum[0][Pcur], a0);
-                    atomicAdd(&sm.psum[1][Pcur], a1);
-                    atomicAdd(&sm.psum[2][Pcur], a2);
+                    atomicAdd(&sm.ppw.psum[0][Pcur], a0);
+                    atomicAdd(&sm.ppw.psum[1][Pcur], a1);
+                    atomicAdd(&sm.ppw.psum[2][Pcur], a2);
                 }
             }
             if (lane == 0 && fails) atomicAdd(&sm.fail_pts, fails);
@@ -1307,7 +1368,7 @@ __device__ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, in
 #pragma unroll
             for (int j = 0; j < 3; j++) {
                 // the trials' gains: T_j = sum(D) - g_j (g_j <= sum(D))
-                const unsigned long long s = wave_sum(sm.psum[j][lane]);
+                const unsigned long long s = wave_sum(sm.ppw.psum[j][lane]);
                 if (lane == 0) sm.S[j] = sum0 - s;
             }
         }
@@ -1320,7 +1381,7 @@ __device__ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, in
                 best = j;
             }
         sum0 = sm.S[best];
-        if (tid < kParts) sm.pD[tid] -= sm.psum[best][tid];
+        if (tid < kParts) sm.ppw.pD[tid] -= sm.ppw.psum[best][tid];
         if (tid == 0) {
             sm.icc[kk][0] = best == 0 ? tx[0] : (best == 1 ? tx[1] : tx[2]);
             sm.icc[kk][1] = best == 0 ? ty[0] : (best == 1 ? ty[1] : ty[2]);
@@ -1417,6 +1478,7 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
             o->t_sel = 0;
             o->ll_pts = 0;
             o->split_cubes = o->split_pts = 0;
+            o->split_walks = o->split_partial = 0;
             o->t_sw = 0;
             o->drift_hist = 0;
             o->pad = 0;
@@ -1446,7 +1508,10 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
     uint64_t t_sel = 0, ll_pts = 0;
     // plain path: k-means++ + compactness passes; the cube path adds what its passes read
     unsigned long long bytes = use_cubes ? 0ull : 4ull * (unsigned long long)N * (unsigned long long)(K + 1);
-    if (tid == 0) sm.fail_pts = sm.split_cubes = sm.split_pts = 0;
+    if (tid == 0) {
+        sm.fail_pts = sm.split_cubes = sm.split_pts = 0;
+        sm.split_walks = sm.split_partial = 0;
+    }
 #define SSLOT(slot) (ss + (size_t)(slot) * (size_t)M)
 
     if (kPhase & 1) {
@@ -1787,7 +1852,7 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
             uint32_t *stg = sm.stage[wid];
             const uint32_t loff = lane_offset(lane);
             int head = 0, tail = 0;  // wave-uniform ring counters
-            uint32_t spl = 0;        // (trace) per lane: cubes split in place << kSplPtsBits | colours they decided
+            uint32_t spl = 0;        // (trace) per lane: colours its split cubes decided (<= 2^12 walks x 64 per sweep)
             auto label_stage = [&](int count) {
                 __builtin_amdgcn_wave_barrier();
                 if (lane < count) {
@@ -1823,10 +1888,54 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
                 if (lane == 0) b = atomicAdd(&sm.next_chunk, 64);
                 return b;  // (lane 0's; read with readfirstlane one chunk later)
             };
+            // the colours of the failing cubes fm (a ballot; lane = cube, mask mlo | mhi << 32, origin key
+            // okey) go to the ring: enumerated from the occupancy masks (no key loads), packed densely
+            // into the lanes and labelled 64 at a time.  LLFE_KM_UNROLL failing cubes per trip:
+            // independent readlane / mbcnt chains interleave; the ring (kStage) holds <= 127 pending +
+            // UNROLL x 64 new colours
+            auto push_cubes = [&](unsigned long long fm, const uint32_t mlo, const uint32_t mhi,
+                                  const uint32_t okey) __attribute__((always_inline)) {
+                // (per failing cube one readlane of its origin key instead of rebuilding it in scalar code)
+                auto push = [&](int src) {
+                    const unsigned long long m =
+                        ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane(mhi, src) << 32) |
+                        (uint32_t)__builtin_amdgcn_readlane(mlo, src);
+                    const uint32_t k = __builtin_amdgcn_readlane(okey, src);
+                    const uint32_t r =
+                        __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+                    stg[lane_sel(m, ((uint32_t)head + r) & (kStage - 1), kStage + lane)] = k | loff;
+                    head += __popcll(m);
+                };
+                while (fm) {
+#pragma unroll
+                    for (int u = 0; u < LLFE_KM_UNROLL; u++) {
+                        if (u > 0 && !fm) break;
+                        const int src = __builtin_ctzll(fm);
+                        fm = clear_bit(fm, src);
+                        push(src);
+                    }
+                    LABEL_FULL();
+                }
+            };
+            // Two-centre cubes of the cells path wait in the wave's pending list (sm.pend, a ring) until 64
+            // of them fill a walk: split_drain splits them, the colours inside their bands follow the
+            // other failing cubes' into the colour ring.  The sweep's end flushes what is left.
+            uint32_t *pl = sm.pend[wid];
+            int phead = 0, ptail = 0;            // wave-uniform list counters
+            uint32_t n_walks = 0, n_partial = 0;  // (trace) wave-uniform
+            auto drain = [&](int n) __attribute__((always_inline)) {
+                __builtin_amdgcn_wave_barrier();  // (the entries are this wave's own stores)
+                const uint4 r = split_drain(sm, ctab, pl, ptail, n);
+                ptail += n;
+                n_walks++;
+                n_partial += n < 64;
+                spl += r.w;
+                push_cubes(__ballot((r.x | r.y) != 0u), r.x, r.y, r.z);
+            };
             // (split_here: the cubes of failing cells, whose batches are dense in failing cubes; the
             // cubes-only sweep of a small table has one or two per batch and keeps the plain path)
-            auto cube_body = [&](const CubeEnt &e, const bool valid, auto split_here) __attribute__((always_inline)) {
-                constexpr bool kSplitHere = decltype(split_here)::value && kSplitMin <= 64;
+            auto cube_body = [&](const CubeEnt &e, const bool valid, const uint32_t cidx, auto split_here) __attribute__((always_inline)) {
+                constexpr bool kSplitHere = decltype(split_here)::value && kSplitOn;
                 bool pass = false, two = false;
                 int k = 0, jc = 0;
                 if (valid) {
@@ -1866,74 +1975,23 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
                 }
                 bool fail = valid && !pass;
                 uint32_t mlo = (uint32_t)e.mask, mhi = (uint32_t)(e.mask >> 32);
-                // Two-centre cubes (exactly one contender j): when the batch holds enough of them,
-                // each lane splits its own cube by the bisector of c_k and c_j (bisector_signs),
-                // adds the two sides' moments like a passing cube's, and only the colours inside the
-                // band go on to the ring below.
+                // Two-centre cubes (exactly one contender j) are listed for a later full walk instead of
+                // going to the ring: slot = pending + rank among the batch's two-centre lanes.
+                unsigned long long tb = 0;
                 if (kSplitHere) {
-                    const unsigned long long tb = __ballot(two);
-                    if (__popcll(tb) >= kSplitMin) {
-                        if (two) {
-                            const int ox = (int)((e.id >> 12) & 63u) * 4, oy = (int)((e.id >> 6) & 63u) * 4,
-                                      oz = (int)(e.id & 63u) * 4;
-                            int p, s1, s2, s3;
-                            {
-                                const float *ck = sm.c[k], *cj = sm.c[jc];
-                                const float ax = ck[0] - cj[0], ay = ck[1] - cj[1], az = ck[2] - cj[2];
-                                const float bx = (float)(2 * ox) - (cj[0] + ck[0]), by = (float)(2 * oy) - (cj[1] + ck[1]),
-                                            bz = (float)(2 * oz) - (cj[2] + ck[2]);
-                                const float f0 = __builtin_fmaf(az, bz, __builtin_fmaf(ay, by, ax * bx));
-                                constexpr float sc = (float)(1 << kBisFrac);
-                                const int gx = (int)__builtin_rintf(ax * (2.f * sc)), gy = (int)__builtin_rintf(ay * (2.f * sc)),
-                                          gz = (int)__builtin_rintf(az * (2.f * sc));
-                                p = kBisBand - ((int)__builtin_rintf(f0 * sc) + 3 * (gx + gy + gz));
-                                s1 = gz;
-                                s2 = gy - 3 * gz;
-                                s3 = gx - 3 * (gy + gz);
-                            }
-                            const uint4 sg = bisector_signs(p, s1, s2, s3);
-                            const MaskMoments a = mask_moments(mlo & sg.x, mhi & sg.y), b = mask_moments(mlo & sg.z, mhi & sg.w);
-                            atomicAdd(&sm.accA[k][tid], (unsigned long long)(a.n * (uint32_t)ox + a.sx) |
-                                                            ((unsigned long long)(a.n * (uint32_t)oy + a.sy) << 32));
-                            atomicAdd(&sm.accB[k][tid], (unsigned long long)(a.n * (uint32_t)oz + a.sz) | ((unsigned long long)a.n << 32));
-                            atomicAdd(&sm.accA[jc][tid], (unsigned long long)(b.n * (uint32_t)ox + b.sx) |
-                                                             ((unsigned long long)(b.n * (uint32_t)oy + b.sy) << 32));
-                            atomicAdd(&sm.accB[jc][tid], (unsigned long long)(b.n * (uint32_t)oz + b.sz) | ((unsigned long long)b.n << 32));
-                            mlo &= ~(sg.x | sg.z);
-                            mhi &= ~(sg.y | sg.w);
-                            fail = (mlo | mhi) != 0u;
-                            spl += (1u << kSplPtsBits) + a.n + b.n;
-                        }
+                    tb = __ballot(two);
+                    if (two) {
+                        const uint32_t r = __builtin_amdgcn_mbcnt_hi((uint32_t)(tb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)tb, 0u));
+                        pl[((uint32_t)phead + r) & (kPend - 1)] =
+                            cidx | ((uint32_t)k << kPendIdxBits) | ((uint32_t)jc << (kPendIdxBits + 3));
+                        fail = false;
                     }
+                    phead += __popcll(tb);
                 }
-                // cubes straddling a boundary: their colours (enumerated from the
-                // occupancy mask, no key loads) packed densely into the lanes and
-                // labelled 64 at a time
-                unsigned long long fm = __ballot(fail);
-                // per lane: the origin key of its cube (read back per failing cube with one
-                // readlane instead of rebuilding it in scalar code)
-                const uint32_t okey = cube_origin_key(e.id);
-                // LLFE_KM_UNROLL failing cubes per trip: independent readlane / mbcnt chains
-                // interleave; the ring (kStage) holds <= 127 pending + UNROLL x 64 new colours
-                auto push = [&](int src) {
-                    const unsigned long long m =
-                        ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane(mhi, src) << 32) |
-                        (uint32_t)__builtin_amdgcn_readlane(mlo, src);
-                    const uint32_t k = __builtin_amdgcn_readlane(okey, src);
-                    const uint32_t r =
-                        __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-                    stg[lane_sel(m, ((uint32_t)head + r) & (kStage - 1), kStage + lane)] = k | loff;
-                    head += __popcll(m);
-                };
-                while (fm) {
-#pragma unroll
-                    for (int u = 0; u < LLFE_KM_UNROLL; u++) {
-                        if (u > 0 && !fm) break;
-                        const int src = __builtin_ctzll(fm);
-                        fm = clear_bit(fm, src);
-                        push(src);
-                    }
-                    LABEL_FULL();
+                // cubes straddling a boundary between more than two centres: all their colours
+                push_cubes(__ballot(fail), mlo, mhi, cube_origin_key(e.id));
+                if (kSplitHere) {
+                    if (phead - ptail >= 64) drain(64);
                 }
             };
             // Cells first (CellEnt: the up to four cubes of a 4 x 8 x 8 box, consecutive in the
@@ -2008,8 +2066,12 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
                             ce.mask = 0;
                             ce.id = 0;
                             ce.sums = 0;
-                            if (v) ce = ctab[ql[b + lane]];
-                            cube_body(ce, v, std::true_type{});
+                            uint32_t ci = 0;
+                            if (v) {
+                                ci = (uint32_t)ql[b + lane];
+                                ce = ctab[ci];
+                            }
+                            cube_body(ce, v, ci, std::true_type{});
                         }
                         __builtin_amdgcn_wave_barrier();  // (the next batch rewrites the list)
                     }
@@ -2100,20 +2162,23 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
                     const int nb = __builtin_amdgcn_readfirstlane(ahead);
                     if (nb + lane < C) en = ctab[nb + lane];
                     if (nb < C) ahead = grab();
-                    cube_body(e, valid, std::false_type{});
+                    cube_body(e, valid, 0u, std::false_type{});
                     base = nb;
                 }
             }
+            if (kSplitOn && phead > ptail) drain(phead - ptail);  // (< 64 left: the wave's one partial walk)
             while (head - tail >= 64) label_stage(64);
             if (head > tail) label_stage(head - tail);
 #undef LABEL_FULL
             fails = (unsigned long long)head;
             if (lane == 0 && fails) atomicAdd(&sm.fail_pts, fails);
-            if (kSplitMin <= 64 && __ballot(spl != 0u)) {
-                const uint32_t nc = wave_sum(spl >> kSplPtsBits), np = wave_sum(spl & ((1u << kSplPtsBits) - 1u));
+            if (kSplitOn && n_walks) {
+                const uint32_t np = wave_sum(spl);
                 if (lane == 0) {
-                    atomicAdd(&sm.split_cubes, (unsigned long long)nc);
+                    atomicAdd(&sm.split_cubes, (unsigned long long)ptail);  // (every listed cube was walked)
                     atomicAdd(&sm.split_pts, (unsigned long long)np);
+                    atomicAdd(&sm.split_walks, n_walks);
+                    atomicAdd(&sm.split_partial, n_partial);
                 }
             }
         } else {
@@ -2411,6 +2476,8 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
             o->ll_pts = ll_pts;
             o->split_cubes = sm.split_cubes;
             o->split_pts = sm.split_pts;
+            o->split_walks = sm.split_walks;
+            o->split_partial = sm.split_partial;
             o->t_sw = t_sw;
             o->n_cubes = (uint32_t)C;
             o->drift_hist = drift_hist;

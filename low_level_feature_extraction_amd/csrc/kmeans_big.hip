@@ -469,6 +469,7 @@ __global__ __launch_bounds__(BT) void k_kmeans_big(const uint32_t *__restrict__ 
         o->t_sel = 0;
         o->ll_pts = 0;
         o->split_cubes = o->split_pts = 0;
+        o->split_walks = o->split_partial = 0;
         o->t_sw = 0;
         o->drift_hist = 0;
         for (int k = 0; k < K; k++) {

@@ -29,6 +29,9 @@ def main():
     sp_cubes, sp_pts = (a.T[17], a.T[18]) if a.shape[1] >= 19 else (z, z)
     # owned straddling cubes k-means++ summed in place, their colours (the line's last two columns)
     pps_cubes, pps_pts = (a.T[23], a.T[24]) if a.shape[1] >= 25 else (z, z)
+    # 64-lane walks that split those cubes, the partial ones among them (columns 25, 26; older builds walked
+    # inside a cube batch and did not count: zeros)
+    sp_walks, sp_part = (a.T[25], a.T[26]) if a.shape[1] >= 27 else (z, z)
     dh = a.T[19].astype(np.uint64) if a.shape[1] >= 20 else z.astype(np.uint64)
     ok = it > 1
     pp = (tpp - t0) / 100.0
@@ -46,6 +49,9 @@ def main():
               f" {np.mean(ll_pts[m] / (it[m] - 1) / U[m]):.3f} of the colours labelled one by one,"
               f" {np.mean(sp_pts[m] / (it[m] - 1) / U[m]):.3f} decided in {np.mean(sp_cubes[m] / (it[m] - 1)):.0f} split cubes"
               f" per iteration)  compact {cp[m].mean()/1e3:6.3f} ms")
+        if sp_walks[m].any():
+            print(f"      split walks per iteration {np.mean(sp_walks[m] / (it[m] - 1)):.1f} ({np.mean(sp_part[m] / (it[m] - 1)):.1f} of them partial),"
+                  f" live lanes per walk {sp_cubes[m].sum() / sp_walks[m].sum():.1f}")
         if ncub[m].any():
             print(f"      cubes/U {np.mean(ncub[m] / U[m]):.3f}  k-means++ colours read one by one / U"
                   f" {np.mean(pp_pts[m] / U[m]):.3f} (undecided cubes) + {np.mean(pp_sel[m] / U[m]):.3f} (selection);"
