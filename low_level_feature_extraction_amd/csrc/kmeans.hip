@@ -33,9 +33,9 @@
 // t_j is at least as close everywhere the box adds sum d(., c_k) - sum d(., t_j), in which the
 // sum |p|^2 terms cancel; an undecided cube's colours add max(0, H_t - max_m H_m) (H_c(p) =
 // 2 p.c - |c|^2), again without |p|^2 -- unless c_k owns the cube and its cells-path batch holds
-// enough such cubes: then the lane sums its own cube in place from the sign mask of the trial's
-// linear form (split_owned / gain_signs below).  All integers: every T_j, every prefix and every
-// choice is bit-identical to the plain sums.
+// enough such cubes: then the cube waits in its wave's list and a lane sums it whole, 64 cubes per
+// walk, from the sign mask of the trial's linear form (list_owned / pp_walk / gain_signs below).
+// All integers: every T_j, every prefix and every choice is bit-identical to the plain sums.
 #include "kmeans_common.h"
 
 #include <mutex>
@@ -230,7 +230,7 @@ struct KmSmem {
     int flag;
     int task;                            // work-queue item of the workgroup (persistent launches)
     int next_chunk;                      // next 64-cube chunk to hand out (cube sweeps)
-    unsigned long long fail_pts;  // keys read point by point in this Lloyd sweep
+    unsigned long long fail_pts;  // keys read point by point in the attempt's Lloyd sweeps (k-means++: its rounds')
     unsigned long long split_cubes, split_pts;  // (trace) cubes the attempt's sweeps split in place, colours they decided
     uint32_t split_walks, split_partial;        // (trace) ... in this many 64-lane walks, these of them not full
     // cube-based k-means++ (pp_cubes)
@@ -261,6 +261,8 @@ struct KmSmem {
     float thrL[3][kMaxK * kMaxK];        // Lloyd margin thresholds [cube / cell / super-cell][owner k][j]
     int cq[KW][256];                     // per-wave list of the cubes of a chunk's failing cells
     unsigned long long qtot;             // sum of |p|^2 over all colours (exact)
+    unsigned long long drift_hist;       // (trace) Lloyd iterations by largest centre move, 8 x u8 bins: thread 0's, kept
+                                         // here because as a register of the Lloyd loop it lived in scratch
 };
 
 // 1024 / KT workgroups per CU (160 KB of LDS): two of 512 threads, four of 256
@@ -274,6 +276,22 @@ static_assert(offsetof(KmSmem, accB) == sizeof(((KmSmem *)nullptr)->accA) &&
 static_assert(KW > 4 || sizeof(((KmSmem *)nullptr)->pend) <= sizeof(((KmSmem *)nullptr)->ppw),
               "pending-cube lists overflow the k-means++ state they alias");
 static_assert(kPend >= 63 + 64 && (kPend & (kPend - 1)) == 0, "pending-cube list too small");
+// (k-means++ sweeps) per-wave list of owned straddling cubes awaiting their walk, a ring like `pend` (drained at
+// 64: <= 63 pending + the 64 of one cube batch), and the walks' trace counters.  An entry is three words, one
+// array each: the cube's occupancy mask (low, high) and its id bits R << 12 | G << 6 | B | undecided trials
+// << 18 | owner k << 21 -- all the walk needs, so it does not gather the cube again (a dependent global load
+// per walk; measured, profiles/pp_compact/).  KmSmem::ppw is live in pp_cubes, so these take the tail of the
+// Lloyd accumulator accB instead: Lloyd clears accB before its first sweep, and inside pp_cubes only the
+// selection's step sums touch the accumulators, from the front of accA
+struct PPPend {
+    uint32_t list[KW][3][kPend];
+    uint32_t walks, lanes, mixed;  // (trace) gain_signs passes, their live lanes, drains over several partitions
+};
+static_assert(sizeof(PPPend) % 4 == 0 && 3 * KW * kSelSteps * sizeof(uint32_t) + sizeof(PPPend) <= 2 * sizeof(((KmSmem *)nullptr)->accA),
+              "k-means++ pending-cube lists overlap the selection's step sums");
+__device__ __forceinline__ PPPend &pp_pend(KmSmem &sm) {
+    return *reinterpret_cast<PPPend *>(reinterpret_cast<char *>(&sm.accB[0][0]) + sizeof(sm.accB) - sizeof(PPPend));
+}
 
 __device__ __forceinline__ Cent load_centres(const float (*c)[3]) {
     Cent r;
@@ -505,9 +523,9 @@ __device__ __forceinline__ uint4 split_drain(KmSmem &sm, const CubeEnt *__restri
 // gain_signs: x | y << 32 = the positions with G > 0, one lane per cube.  q = -G at position 63
 // (u = (3, 3, 3)); s1..s3 are the steps of G combined for the walk order as bisector_signs' are.
 // Every walked value is -G at a position of the cube, a difference of two squared distances between
-// colours: |q| <= 3 x 255^2 = 195 075 < 2^18, and |s| <= 2 x 255 x 7 = 3 570: no overflow.  A real
-// call: the 64 unrolled positions exist once, outside the sweep bodies.
-__device__ __noinline__ uint2 gain_signs(int q, int s1, int s2, int s3) {
+// colours: |q| <= 3 x 255^2 = 195 075 < 2^18, and |s| <= 2 x 255 x 7 = 3 570: no overflow.  Inlined
+// into pp_walk, its one caller.
+__device__ __forceinline__ uint2 gain_signs(int q, int s1, int s2, int s3) {
     uint32_t w[2] = {0u, 0u};
 #pragma unroll
     for (int bit = 63; bit >= 0; bit--) {
@@ -518,14 +536,64 @@ __device__ __noinline__ uint2 gain_signs(int q, int s1, int s2, int s3) {
     return make_uint2(w[0], w[1]);
 }
 
+// One 64-lane walk of the k-means++ sweep: lane < n takes entry first + lane of its wave's pending list
+// (PPPend::list) and rebuilds from it what box_vals knew when it listed the cube: the origin o and the
+// partition R from the id bits, the owner c_k (sm.icc[k]) and, for the first of the entry's undecided trials
+// t_j (packed colours tk0..tk2, wave-uniform), f = d(o, t) - d(o, c_k) and the steps 2 (t - c_k) of G.  The
+// trial's gain on the cube is exact over the positions where it is strictly closer than the owner
+// (gain_signs, mask_moments), and belongs to the cube's own partition R, which need not be the one the wave
+// is sweeping now: the lane adds it to sm.ppw.psum[j][R] itself (an LDS atomic without return; a wave sum per
+// partition present cost more -- most walks hold two or three).  A cube with a further undecided trial is
+// appended again at `head` with the walked trial's bit cleared, so every walk of a full list has 64 live
+// lanes (the ring holds <= 63 unread entries beside the n read here: the <= n new ones fit).  Returns
+// (wave-uniform) entries appended | (the n cubes lay in more than one partition) << 7.  All integers, so
+// neither lane nor order matters.  Inlined at its two sites in each of the four sweep instantiations (the
+// cells path's cube batches and the sweep-end flush): as a real call the walk existed once, but measured no
+// faster than walking in place, the inlined form 1 % above it (profiles/pp_compact/).
+__device__ __forceinline__ uint32_t pp_walk(KmSmem &sm, int first, int n, int head, uint32_t tk0, uint32_t tk1, uint32_t tk2) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    uint32_t(*pl)[kPend] = pp_pend(sm).list[wid];
+    uint32_t rest = 0u, mlo = 0u, mhi = 0u, ent = 0u;
+    int R = -1;
+    if (lane < n) {
+        const uint32_t slot = (uint32_t)(first + lane) & (kPend - 1);
+        mlo = pl[0][slot];
+        mhi = pl[1][slot];
+        ent = pl[2][slot];
+        const int k = (int)(ent >> (kPendIdxBits + 3));
+        const uint32_t und = (ent >> kPendIdxBits) & 7u;
+        const int j = __builtin_ctz(und);  // the entry's first undecided trial (und != 0)
+        rest = und & (und - 1u);
+        R = (int)((ent >> 12) & 63u);
+        const int ox = R * 4, oy = (int)((ent >> 6) & 63u) * 4, oz = (int)(ent & 63u) * 4;
+        const int kx = sm.icc[k][0], ky = sm.icc[k][1], kz = sm.icc[k][2];
+        const uint32_t tk = j == 0 ? tk0 : (j == 1 ? tk1 : tk2);
+        const int tjx = (int)(tk >> 16), tjy = (int)((tk >> 8) & 255u), tjz = (int)(tk & 255u);
+        const int f = d2i(ox, oy, oz, tjx, tjy, tjz) - d2i(ox, oy, oz, kx, ky, kz);
+        const int gx = 2 * (tjx - kx), gy = 2 * (tjy - ky), gz = 2 * (tjz - kz);
+        const uint2 pos = gain_signs(f - 3 * (gx + gy + gz), gz, gy - 3 * gz, gx - 3 * (gy + gz));
+        const MaskMoments a = mask_moments(mlo & pos.x, mhi & pos.y);
+        // 0 <= gain <= 64 x 195 075; every factor fits 24 bits
+        const uint32_t g = (uint32_t)(__mul24(gx, (int)a.sx) + __mul24(gy, (int)a.sy) + __mul24(gz, (int)a.sz) - __mul24((int)a.n, f));
+        if (g) atomicAdd(&(&sm.ppw.psum[0][0])[j * kParts + R], (unsigned long long)g);  // (psum[j][R])
+    }
+    const unsigned long long rb = __ballot(rest != 0u);
+    if (rest) {
+        const uint32_t slot = ((uint32_t)head + __builtin_amdgcn_mbcnt_hi((uint32_t)(rb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)rb, 0u))) & (kPend - 1);
+        pl[0][slot] = mlo;
+        pl[1][slot] = mhi;
+        pl[2][slot] = (ent & ~(7u << kPendIdxBits)) | (rest << kPendIdxBits);
+    }
+    const uint32_t mixed = __ballot(lane < n && R != __builtin_amdgcn_readfirstlane(R)) != 0ull;
+    return (uint32_t)__popcll(rb) | (mixed << 7);
+}
+
 // what box_vals knows about a failing cube that the split needs: the trials that are neither A nor B
-// on a cube its owner candidate owns (bit j; 0 when the cube is not owned), their f, the owner's
-// doubled coordinates
+// on a cube its owner candidate owns (bit j; 0 when the cube is not owned) and that owner's index.  Both
+// go into the cube's entry of the wave's pending list; the walk rebuilds f from them (pp_walk below)
 struct PPSplit {
     uint32_t und;
-    int f[3];
-    u16x2 krb;
-    int ky;
+    int k;
 };
 
 // Boundary colours are packed densely into the wave's lanes before they are labelled:
@@ -639,8 +707,9 @@ __device__ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, in
                          const CubeEnt *__restrict__ ctab, int C, const CellEnt *__restrict__ ltab, int L,
                          const SupEnt *__restrict__ stab, int S, const uint32_t *__restrict__ part_uq, const uint32_t *__restrict__ hist,
                          const uint64_t *__restrict__ mom, unsigned long long &bytes, uint32_t &pp_pts, uint32_t &pp_sel, uint64_t &t_sel,
-                         uint32_t &pp_split_cubes, uint32_t &pp_split_pts) {
+                         uint32_t &pp_split_cubes, uint32_t &pp_split_pts, uint3 &pp_walks) {
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    if (tid == 0) pp_pend(sm).walks = pp_pend(sm).lanes = pp_pend(sm).mixed = 0u;  // (the lists start empty: counters only)
     const uint32_t c0 = cvrng_next(rng) % (uint32_t)N;  // (every thread advances its rng copy)
     if (wid == 0) {
         const uint32_t a0 = key_layout(sm, part_uq, hist, c0);
@@ -1088,15 +1157,11 @@ __device__ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, in
                     const bool B = f + NBx[j * kMaxK + k] <= 0;  // t_j always at least as close
                     dec = dec & (A | (owned & B));
                     vv[j] = A ? 0u : (uint32_t)(sdot(trb[j], tg2[j]) - sk - __mul24(n, f));
-                    if (sp) {  // (cubes: what the split of an owned failing cube starts from)
-                        sp->f[j] = f;
-                        und |= (uint32_t)(owned & !A & !B) << j;
-                    }
+                    if (sp) und |= (uint32_t)(owned & !A & !B) << j;  // (cubes: what the split of an owned failing cube starts from)
                 }
                 if (sp) {
                     sp->und = und;
-                    sp->krb = krb;
-                    sp->ky = ky;
+                    sp->k = k;
                 }
                 v0 = vv[0];
                 v1 = vv[1];
@@ -1108,56 +1173,50 @@ __device__ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, in
                 const CubeGeo g = cube_geo(e);
                 box_vals(g.ox, g.oy, g.oz, g.n, g.sx, g.sy, g.sz, g.s2, Mkk, NA, NB, 3, 3, 3, v0, v1, v2, fail, sp);
             };
-            // Owned failing cubes (`fail`, false in idle lanes): when the batch holds at least kPPSplitMin
-            // of them each lane sums its own cube in place.  A decided trial adds what a decided cube's
-            // does (A: v = 0, B: the closed form v); an undecided one adds the exact gain over the
-            // positions where it is strictly closer than the owner (gain_signs).  Lanes with a second
-            // or third undecided trial repeat the pass; the others idle through it.  Such a lane
+            // Owned failing cubes of the cells path with an undecided trial wait in the wave's pending list
+            // (PPPend::list, a ring) until 64 of them fill a walk: list_owned below appends them, pp_drain has
+            // pp_walk walk the first n for one trial each; it books the gains itself, and a cube
+            // with a further undecided trial comes back as a new entry at the list's head.
+            int phead = 0, ptail = 0;                          // wave-uniform list counters
+            uint32_t n_walks = 0, n_lanes = 0, n_mixed = 0;    // (trace) wave-uniform
+            const uint32_t tk0 = (uint32_t)((tx[0] << 16) | (ty[0] << 8) | tz[0]), tk1 = (uint32_t)((tx[1] << 16) | (ty[1] << 8) | tz[1]),
+                           tk2 = (uint32_t)((tx[2] << 16) | (ty[2] << 8) | tz[2]);
+            auto pp_drain = [&](int n) __attribute__((always_inline)) {
+                __builtin_amdgcn_wave_barrier();  // (the entries are this wave's own stores)
+                const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)pp_walk(sm, ptail, n, phead, tk0, tk1, tk2));
+                __builtin_amdgcn_wave_barrier();
+                ptail += n;
+                phead += (int)(w & 127u);
+                n_walks++;
+                n_lanes += (uint32_t)n;  // (every entry has an undecided trial)
+                n_mixed += w >> 7;
+            };
+            // Owned failing cubes (`fail`, false in idle lanes) of a cells-path batch that holds at least
+            // kPPSplitMin of them: a decided trial adds here what a decided cube's does (A: v = 0, B: the closed
+            // form v, to the current partition, which is the cube's), the undecided ones go to the list with the
+            // cube's mask and id bits (slot = pending + rank among the batch's listed lanes).  Such a lane
             // leaves `fail` cleared, the rest go on to push_cubes.
-            auto split_owned = [&](const CubeEnt &e, const PPSplit &sp, uint32_t v0, uint32_t v1, uint32_t v2,
-                                   bool &fail) __attribute__((always_inline)) {
+            auto list_owned = [&](const CubeEnt &e, const PPSplit &sp, uint32_t v0, uint32_t v1, uint32_t v2,
+                                  bool &fail) __attribute__((always_inline)) {
                 if (kPPSplitMin > 64) return;
                 const bool so = fail && sp.und != 0u;
                 const unsigned long long sb = __ballot(so);
                 if (__popcll(sb) < kPPSplitMin) return;
                 spl_cubes += (uint32_t)__popcll(sb);
-                uint32_t und = 0u;
                 if (so) {
-                    und = sp.und;
-                    acc0 += (und & 1u) ? 0u : v0;
-                    acc1 += (und & 2u) ? 0u : v1;
-                    acc2 += (und & 4u) ? 0u : v2;
+                    acc0 += (sp.und & 1u) ? 0u : v0;
+                    acc1 += (sp.und & 2u) ? 0u : v1;
+                    acc2 += (sp.und & 4u) ? 0u : v2;
                     spl_pts += e.sums & 127u;
                     fail = false;
+                    const uint32_t slot = ((uint32_t)phead + __builtin_amdgcn_mbcnt_hi((uint32_t)(sb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)sb, 0u))) & (kPend - 1);
+                    uint32_t(*pl)[kPend] = pp_pend(sm).list[wid];
+                    pl[0][slot] = (uint32_t)e.mask;
+                    pl[1][slot] = (uint32_t)(e.mask >> 32);
+                    pl[2][slot] = (e.id & ((1u << kPendIdxBits) - 1u)) | (sp.und << kPendIdxBits) | ((uint32_t)sp.k << (kPendIdxBits + 3));
                 }
-                const uint32_t mlo = (uint32_t)e.mask, mhi = (uint32_t)(e.mask >> 32);
-                // the trials' doubled (B, R) as one word each (selected per lane below)
-                const uint32_t tw0 = __builtin_bit_cast(uint32_t, trb[0]), tw1 = __builtin_bit_cast(uint32_t, trb[1]),
-                               tw2 = __builtin_bit_cast(uint32_t, trb[2]);
-                const uint32_t kw = __builtin_bit_cast(uint32_t, sp.krb);
-                while (__ballot(und != 0u)) {
-                    if (und) {
-                        // the lane's first undecided trial j as three all-ones / zero words (bit masks,
-                        // not an index: an indexed choice turns the three trials' values into a
-                        // private array in scratch)
-                        const uint32_t m0 = 0u - (und & 1u), m1 = ~m0 & (0u - ((und >> 1) & 1u)), m2 = ~(m0 | m1);
-                        und &= und - 1u;
-                        const int f = (int)(((uint32_t)sp.f[0] & m0) | ((uint32_t)sp.f[1] & m1) | ((uint32_t)sp.f[2] & m2));
-                        const uint32_t tw = (tw0 & m0) | (tw1 & m1) | (tw2 & m2);
-                        const int tg = (int)(((uint32_t)tg2[0] & m0) | ((uint32_t)tg2[1] & m1) | ((uint32_t)tg2[2] & m2));
-                        // the steps of G per axis, 2 (t - c_k), from the doubled constants
-                        const int gx = (int)(tw >> 16) - (int)(kw >> 16), gy = tg - sp.ky,
-                                  gz = (int)(tw & 0xFFFFu) - (int)(kw & 0xFFFFu);
-                        const uint2 pos = gain_signs(f - 3 * (gx + gy + gz), gz, gy - 3 * gz, gx - 3 * (gy + gz));
-                        const MaskMoments a = mask_moments(mlo & pos.x, mhi & pos.y);
-                        // 0 <= gain <= 64 x 195 075; every factor fits 24 bits
-                        const uint32_t g = (uint32_t)(__mul24(gx, (int)a.sx) + __mul24(gy, (int)a.sy) + __mul24(gz, (int)a.sz) -
-                                                      __mul24((int)a.n, f));
-                        acc0 += g & m0;
-                        acc1 += g & m1;
-                        acc2 += g & m2;
-                    }
-                }
+                phead += __popcll(sb);
+                while (phead - ptail >= 64) pp_drain(64);  // (a walk may hand cubes back: their next trial)
             };
             // undecided cubes among the lanes of `fm`: their colours (enumerated from the
             // occupancy mask) packed densely into the lanes, summed 64 at a time
@@ -1250,7 +1309,7 @@ __device__ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, in
                                 acc1 += c1;
                                 acc2 += c2;
                             }
-                            split_owned(ce, sp, c0, c1, c2, cfail);
+                            list_owned(ce, sp, c0, c1, c2, cfail);
                             const unsigned long long fm = __ballot(cv && cfail);
                             if (fm) push_cubes(fm, ce);
                         }
@@ -1340,6 +1399,9 @@ __device__ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, in
             }
             }
             if (Pcur >= 0) {
+                // the list's <= 63 leftovers: one partial walk per wave and round, and up to two more for the
+                // leftovers' second and third trials
+                while (phead > ptail) pp_drain(min(phead - ptail, 64));
                 flush_pk();
                 const unsigned long long a0 = wave_sum(acc0), a1 = wave_sum(acc1), a2 = wave_sum(acc2);
                 if (lane == 0) {
@@ -1354,6 +1416,9 @@ __device__ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, in
                 if (lane == 0) {
                     atomicAdd(&sm.split_cubes, (unsigned long long)spl_cubes);
                     atomicAdd(&sm.split_pts, (unsigned long long)np);
+                    atomicAdd(&pp_pend(sm).walks, n_walks);
+                    atomicAdd(&pp_pend(sm).lanes, n_lanes);
+                    atomicAdd(&pp_pend(sm).mixed, n_mixed);
                 }
             }
         };
@@ -1401,6 +1466,7 @@ __device__ void pp_cubes(KmSmem &sm, const uint32_t *__restrict__ pts, int N, in
         pp_sel = (uint32_t)sm.sel_pts;
         pp_split_cubes = (uint32_t)sm.split_cubes;
         pp_split_pts = (uint32_t)sm.split_pts;
+        pp_walks = make_uint3(pp_pend(sm).walks, pp_pend(sm).lanes, pp_pend(sm).mixed);
         sm.fail_pts = sm.split_cubes = sm.split_pts = 0;
     }
     __syncthreads();
@@ -1474,6 +1540,7 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
             o->bytes = 0;
             o->pp_pts = 0;
             o->pp_split_cubes = o->pp_split_pts = 0;
+            o->pp_walks = o->pp_walk_lanes = o->pp_walk_mixed = 0;
             o->n_cubes = 0;
             o->t_sel = 0;
             o->ll_pts = 0;
@@ -1505,6 +1572,7 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
     const int C = use_cubes ? cubes.n_cubes[img] : 0;
     const CubeEnt *ctab = use_cubes ? cubes.cubes + (size_t)img * cubes.cube_stride : nullptr;
     uint32_t pp_pts = 0, pp_sel = 0, pp_split_cubes = 0, pp_split_pts = 0;
+    uint3 pp_walks = make_uint3(0u, 0u, 0u);  // (trace) k-means++ split walks, their live lanes, mixed drains
     uint64_t t_sel = 0, ll_pts = 0;
     // plain path: k-means++ + compactness passes; the cube path adds what its passes read
     unsigned long long bytes = use_cubes ? 0ull : 4ull * (unsigned long long)N * (unsigned long long)(K + 1);
@@ -1524,7 +1592,7 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
         pp_cubes(sm, pts, N, K, rng, ctab, C, cubes.cells + (size_t)img * cubes.cell_stride, cubes.n_cells[img],
                  cubes.sups ? cubes.sups + (size_t)img * cubes.sup_stride : nullptr, cubes.sups ? cubes.n_sups[img] : 0,
                  cubes.part_uq + (size_t)img * kParts, cubes.part_hist ? cubes.part_hist + (size_t)img * kParts : nullptr,
-                 cubes.moments + (size_t)img * kPartMoments * kParts, bytes, pp_pts, pp_sel, t_sel, pp_split_cubes, pp_split_pts);
+                 cubes.moments + (size_t)img * kPartMoments * kParts, bytes, pp_pts, pp_sel, t_sel, pp_split_cubes, pp_split_pts, pp_walks);
     } else {
     int cur = 0;
     {
@@ -1752,6 +1820,9 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
             o->pp_pts = pp_pts;
             o->pp_split_cubes = pp_split_cubes;
             o->pp_split_pts = pp_split_pts;
+            o->pp_walks = pp_walks.x;
+            o->pp_walk_lanes = pp_walks.y;
+            o->pp_walk_mixed = pp_walks.z;
             o->pad = (int32_t)pp_sel;
             o->t_sel = t_sel;
         }
@@ -1801,7 +1872,7 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
     int iter = 1;
     const double eps2 = 0.2 * 0.2;
     uint64_t t_sw = 0;  // (trace) time in the labelling sweeps
-    uint64_t drift_hist = 0;  // (trace)
+    if (tid == 0) sm.drift_hist = 0;  // (trace; thread 0 alone reads and writes it)
     for (;;) {
         const uint64_t tsw0 = wall_clock64();
         const CentP c = pack_centres(load_centres(sm.c));
@@ -2223,20 +2294,17 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
         }  // point sweep
         __syncthreads();
         t_sw += wall_clock64() - tsw0;
-        if (tid == 0) {
-            if (use_cubes) {
-                bytes += 16ull * (unsigned long long)C;  // boundary colours come from the masks
-                ll_pts += sm.fail_pts;
-                sm.fail_pts = 0;
-            } else {
-                bytes += 4ull * (unsigned long long)N;
-            }
-        }
+        // (the sweeps' byte and colour counts are taken once, after the loop: as running sums in thread 0 they
+        // lived in scratch, a load / store round trip at the head of every iteration end)
         // reduce 20 values (5 clusters x {x, y, z, count}) over the KT lanes: part p of
         // value v sums lanes p, p + 32, p + 64, ... so the 32 threads of a value read 32
         // consecutive 8-byte slots per step (lanes p * 16 .. p * 16 + 15 put 16 threads on
         // two LDS banks); integer sums, so any grouping gives the same totals
-        for (int q = tid; q < 640; q += KT) {
+        // (the thread id through an empty asm: from the loop-invariant `tid` the slot addresses below were
+        // hoisted out of the Lloyd loop into scratch and reloaded here, one of them inside this loop)
+        int tq = tid;
+        asm volatile("" : "+v"(tq));
+        for (int q = tq; q < 640; q += KT) {
             constexpr int LPP = KT / 32;  // lanes per part
             const int v = q >> 5, part = q & 31;
             const int k = v >> 2, comp = v & 3;
@@ -2264,11 +2332,16 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
         // (pass 1).
         for (int pass = 0;; pass++) {
             if (wid == 0) {
-                const int v = lane < 20 ? lane : 0, k = v >> 2, comp = v & 3;
+                // the lane id taken afresh in every iteration: from the loop-invariant `lane` this block's LDS
+                // addresses and shuffle indices were hoisted out of the Lloyd loop into scratch, and wave 0 ended
+                // each iteration on a chain of dependent reloads
+                int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+                asm volatile("" : "+v"(ln));
+                const int v = ln < 20 ? ln : 0, k = v >> 2, comp = v & 3;
                 unsigned long long val = 0;
                 bool go = true;
                 if (pass == 0) {
-                    if (lane < 20) {
+                    if (ln < 20) {
                         for (int part = 0; part < 32; part++) val += sm.red[part][v];
                         if (comp < 3) {
                             sm.sums[k][comp] = (long long)val;
@@ -2277,8 +2350,8 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
                             sm.counts[k] = (int)val;
                         }
                     }
-                    go = !__ballot(lane < 20 && comp == 3 && k < K && val == 0);
-                    if (lane == 0) {
+                    go = !__ballot(ln < 20 && comp == 3 && k < K && val == 0);
+                    if (ln == 0) {
                         sm.n_moved = 0;
                         sm.flag = go ? 0 : 2;  // 2: an empty cluster
                     }
@@ -2295,7 +2368,7 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
                     dist += __shfl(t2, 4 * k);
                     dist += __shfl(t2, 4 * k + 1);
                     dist += __shfl(t2, 4 * k + 2);
-                    if (lane < 20 && comp < 3 && k < K) sm.c[k][comp] = nv;
+                    if (ln < 20 && comp < 3 && k < K) sm.c[k][comp] = nv;
                     double max_shift = 0.0;
 #pragma unroll
                     for (int k1 = 0; k1 < kMaxK; k1++) {
@@ -2304,9 +2377,9 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
                     }
                     if (use_cubes) {  // the next sweep's thresholds from the new centres (this wave's own writes)
                         __builtin_amdgcn_wave_barrier();
-                        if (lane < kMaxK * kMaxK) thr_tables(lane);
+                        if (ln < kMaxK * kMaxK) thr_tables(ln);
                     }
-                    if (lane == 0) {
+                    if (ln == 0) {
                         sm.flag = (iter + 1 == 100 || max_shift <= eps2) ? 1 : 0;
                         sm.next_chunk = 0;
                         // (trace) iterations by their largest centre move, 8 u8 bins
@@ -2316,7 +2389,8 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
                                         (max_shift >= 4.0) + (max_shift >= 16.0) + (max_shift >= 64.0) +
                                         (max_shift >= 256.0);
                         const unsigned long long sh = 8ull * (unsigned)bin;
-                        if (((drift_hist >> sh) & 255ull) < 255ull) drift_hist += 1ull << sh;
+                        const unsigned long long dh = sm.drift_hist;
+                        if (((dh >> sh) & 255ull) < 255ull) sm.drift_hist = dh + (1ull << sh);
                     }
                 }
             }
@@ -2409,7 +2483,13 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
         if (sm.flag) break;
     }
 
-    if (tid == 0) o->t_lloyd = wall_clock64();
+    if (tid == 0) {
+        o->t_lloyd = wall_clock64();
+        // iter - 1 sweeps: each read the cube table (boundary colours come from the masks) or every key;
+        // sm.fail_pts has summed the colours they labelled one by one
+        bytes += (unsigned long long)(iter - 1) * (use_cubes ? 16ull * (unsigned long long)C : 4ull * (unsigned long long)N);
+        ll_pts = sm.fail_pts;
+    }
     // ------------------------------------------------ compactness with the last labels
     if (use_cubes) {
         // sum_k sum_{p in k} |p - c_k|^2 = sum_p |p|^2 - sum_k (2 c_k . S_k - n_k |c_k|^2)
@@ -2470,6 +2550,9 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
                 o->pp_pts = pp_pts;
                 o->pp_split_cubes = pp_split_cubes;
                 o->pp_split_pts = pp_split_pts;
+                o->pp_walks = pp_walks.x;
+                o->pp_walk_lanes = pp_walks.y;
+                o->pp_walk_mixed = pp_walks.z;
                 o->pad = (int32_t)pp_sel;
                 o->t_sel = t_sel;
             }
@@ -2480,7 +2563,7 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
             o->split_partial = sm.split_partial;
             o->t_sw = t_sw;
             o->n_cubes = (uint32_t)C;
-            o->drift_hist = drift_hist;
+            o->drift_hist = sm.drift_hist;
             o->t_end = wall_clock64();
             for (int k = 0; k < kMaxK; k++) {
                 for (int j = 0; j < 3; j++) o->centers[k][j] = k < K ? sm.c[k][j] : 0.f;

@@ -470,6 +470,7 @@ __global__ __launch_bounds__(BT) void k_kmeans_big(const uint32_t *__restrict__ 
         o->ll_pts = 0;
         o->split_cubes = o->split_pts = 0;
         o->split_walks = o->split_partial = 0;
+        o->pp_walks = o->pp_walk_lanes = o->pp_walk_mixed = 0;
         o->t_sw = 0;
         o->drift_hist = 0;
         for (int k = 0; k < K; k++) {

@@ -206,6 +206,8 @@ struct KmeansAttemptOut {
     uint64_t t_lstart;         // Lloyd launch: start of the attempt's workgroup
     uint32_t hw_id2, xcc_id2;  // ... and its placement
     uint32_t split_walks, split_partial;  // 64-lane walks that split those cubes (all sweeps); the ones not full
+    uint32_t pp_walks, pp_walk_lanes;     // 64-lane passes that walked k-means++'s split cubes; their live lanes summed
+    uint32_t pp_walk_mixed;               // ... and the list drains whose cubes lay in more than one partition
     float pp_centers[kMaxK][3];  // the k-means++ centres (cube-table path; llfe_kmeans_attempts)
 };
 

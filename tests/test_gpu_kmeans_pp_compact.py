@@ -1,0 +1,222 @@
+"""k-means++ split cubes walked 64 at a time from a per-wave list (kmeans.hip list_owned / pp_walk): an owned
+straddling cube of a cells-path batch with at least LLFE_KM_PP_SPLIT_MIN of them is no longer walked in its own
+batch; its mask, its id bits, its undecided trials and its owner wait in the wave's LDS list, a walk takes 64
+of them whenever 64 are pending, one trial each, and hands a cube with a further undecided trial back to the
+list; at the end of each round's sweep every wave walks what is left.  The gain goes to the cube's own
+red-quarter partition, which need not be the one the wave is sweeping when it walks.  A gain booked to the
+wrong partition changes a later round's selection, a lost or doubled entry a trial's total, so every case
+compares all 10 attempts of a small image, at two seeds, with the oracle's cv2.kmeans restatement in its
+exact-sum mode: k-means++ centres, iterations, float32 centres and counts equal, compactness within 1e-6
+relative.
+
+The last three columns of an attempt's LLFE_KM_TRACE line are pp_walks (64-lane passes of gain_signs),
+pp_walk_lanes (their live lanes summed, the second and third trials' passes included) and pp_walk_mixed (walks
+whose cubes lay in more than one partition).  Which cubes are split is unchanged, so with the NumPy model
+(tools/km_pp_compact_sim.py, which restates tools/km_pp_gain_sim.py's split rule and adds the lists), run on
+the exact colours and RNG stream of the case:
+
+    pp_walk_lanes == pp_split_cubes + und2 + 2 und3            (und_n: split cubes with n undecided trials)
+    ceil(pp_walk_lanes / 64) <= pp_walks <= pp_walk_lanes // 64 + KW x rounds + repeat passes
+
+A full walk has 64 live lanes, so there are at most pp_walk_lanes // 64 of them; the others are sweep-end
+walks, at most one per wave and round (KW = 8: one image is 10 attempts, which the 512-thread build takes;
+rounds = K - 1 sweeps) plus the repeat passes for what those left: each has a live lane with a second or third
+trial (at most und2 + 2 und3 in all) and there are at most two per first pass.  Which wave sweeps which run of
+chunks is the device's choice, so the walk count itself is compared with nothing else -- except that lists
+must pay: where the model's split batches hold fewer than 32 cubes on average, the case's walks are fewer than
+its split batches (each of which was at least one walk before).
+
+Cases: `rods`, `corners`, `extremes` (test_gpu_kmeans_pp_split.py's crafted images) and one 160 x 160 photo;
+`corners` has two regions at opposite ends of the red axis, so its walks mix partitions; `sparse`
+(test_gpu_kmeans_compact.py's five far blobs) has attempts whose every round lists fewer than 64 cubes in all,
+so each of their walks is a partial one whichever wave sweeps what; `ties` (cubes-only sweep) lists nothing;
+and eight photos through both build widths.
+"""
+import numpy as np
+import pytest
+
+from low_level_feature_extraction_amd import synth
+from tools import km_pp_compact_sim as csim
+
+from tests.test_gpu_kmeans_compact import _sparse
+from tests.test_gpu_kmeans_pp_split import _corners, _extremes, _rods, _ties
+
+pytestmark = [pytest.mark.gpu, pytest.mark.timeout(180)]
+
+K = 5
+ROUNDS = K - 1
+CELL_MIN = 8192  # kmeans.hip LLFE_KM_CELL_MIN
+SPLIT_MIN = 8    # kmeans.hip LLFE_KM_PP_SPLIT_MIN
+SEEDS = (2027, 31)
+KW_WIDE = 8      # waves of the 512-thread build (batches whose attempts all fit the GPU at once)
+# LLFE_KM_TRACE columns (llfe_api.cpp)
+COL_PP_PTS, COL_PP_SPLIT_CUBES, COL_PP_SPLIT_PTS, COL_PP_WALKS, COL_PP_WALK_LANES, COL_PP_WALK_MIXED = 11, 23, 24, 27, 28, 29
+
+# name -> (image, production noise (False: zero noise, the colours are exactly the image's), cells path)
+CASES = {
+    "rods": (_rods, False, True),
+    "corners": (_corners, False, True),
+    "extremes": (_extremes, False, True),
+    "sparse": (_sparse, False, True),
+    "photo160": (lambda: synth.synth_numpy(1, 160, 160, seed=2025), True, True),
+    "ties": (_ties, False, False),  # cubes-only sweep: no lists
+}
+
+
+def _read_trace(path):
+    return np.atleast_2d(np.loadtxt(path, dtype=np.int64))
+
+
+@pytest.fixture(scope="module")
+def images():
+    return {name: make() for name, (make, _, _) in CASES.items()}
+
+
+@pytest.fixture(scope="module")
+def runs(orc, images):
+    """name, seed -> (noise or None, unique keys, the oracle's attempts, the model's attempts); computed once"""
+    out = {}
+    for name, host in images.items():
+        h, w = host.shape[:2]
+        for seed in SEEDS:
+            noise = None if CASES[name][1] else np.zeros((h * w, 3), np.int8)
+            keys = orc.color_unique(host, orc.device_noise(h * w, seed, 0) if noise is None else noise)
+            st = orc.image_rng_state(seed, 0)
+            out[name, seed] = (noise, keys, orc.kmeans_attempts(keys, K, st, exact_sums=True), csim.attempts_compact(keys, K, st, 10, SPLIT_MIN))
+    return out
+
+
+@pytest.fixture(scope="module")
+def device(backend, images, runs, tmp_path_factory):
+    """name, seed -> (result, attempts, trace rows); every case runs on the device once"""
+    out = {}
+    mp = pytest.MonkeyPatch()
+    try:
+        for (name, seed), (noise, _, _, _) in runs.items():
+            trace = tmp_path_factory.mktemp("km") / f"{name}_{seed}.txt"
+            mp.setenv("LLFE_KM_TRACE", str(trace))
+            r = backend.process(images[name][None], ("colors",), seed=seed, index_base=0, noise=noise)[0]
+            out[name, seed] = (r, backend.kmeans_attempts(1)[0], _read_trace(trace))
+    finally:
+        mp.undo()
+    return out
+
+
+def _walk_bounds(cubes, lanes, und, kw):
+    """(lowest, highest) pass count for `cubes` listed cubes with `lanes` live lanes, und[n] of them with n
+    undecided trials, on kw waves"""
+    drains = lanes // 64 + kw * ROUNDS
+    return -(-lanes // 64), drains + min(2 * drains, int(und[2] + 2 * und[3]))
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+@pytest.mark.parametrize("name", list(CASES))
+def test_attempts_equal_exact_sum_oracle(images, runs, device, name, seed):
+    _, keys, ex, model = runs[name, seed]
+    r, att, t = device[name, seed]
+    assert r.n_unique == len(keys)
+    assert t.shape[0] == 10 and t.shape[1] > COL_PP_WALK_MIXED, t.shape
+    n_cubes = len(np.unique(((keys >> 18) & 63) << 12 | ((keys >> 10) & 63) << 6 | ((keys >> 2) & 63)))
+    assert (n_cubes >= CELL_MIN) == CASES[name][2], (name, n_cubes)
+    print(f"{name} seed {seed}: U={len(keys)} cubes={n_cubes}; per attempt split cubes / walks / live lanes / mixed drains:",
+          [[int(t[a, c]) for c in (COL_PP_SPLIT_CUBES, COL_PP_WALKS, COL_PP_WALK_LANES, COL_PP_WALK_MIXED)] for a in range(10)])
+    for a in range(10):
+        assert np.array_equal(model[a][0], ex["pp"][a].astype(np.int64)), ("model's k-means++", a)
+        assert np.array_equal(att[a]["pp_centers"][:K], ex["pp"][a]), (a, att[a]["pp_centers"], ex["pp"][a])
+        assert att[a]["iters"] == int(ex["iters"][a]), (a, att[a]["iters"], ex["iters"][a])
+        assert np.array_equal(att[a]["centers"][:K], ex["att_centers"][a]), a
+        assert np.array_equal(att[a]["counts"][:K], ex["att_counts"][a]), a
+        assert abs(att[a]["compactness"] - ex["att_compactness"][a]) <= 1e-6 * ex["att_compactness"][a], a
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+@pytest.mark.parametrize("name", [n for n in CASES if CASES[n][2]])
+def test_walk_counters(runs, device, name, seed):
+    model = runs[name, seed][3]
+    t = device[name, seed][2]
+    tot_walks = tot_batches = tot_cubes = 0
+    for a in range(10):
+        m = model[a][1]
+        cubes, walks, lanes = int(t[a, COL_PP_SPLIT_CUBES]), int(t[a, COL_PP_WALKS]), int(t[a, COL_PP_WALK_LANES])
+        u = m["und_split"]
+        assert cubes == m["split_cubes"] and int(t[a, COL_PP_SPLIT_PTS]) == m["split_pts"], (name, a)
+        assert lanes == cubes + int(u[2]) + 2 * int(u[3]) == m["lanes"], (name, a, lanes, cubes, u)
+        lo, hi = _walk_bounds(cubes, lanes, u, KW_WIDE)
+        print(f"{name} seed {seed} attempt {a}: cubes {cubes} lanes {lanes} walks {walks} in [{lo}, {hi}];"
+              f" model (round-robin, 8 waves) {m['walks'][8]}, split batches {m['batches_split']}")
+        assert lo <= walks <= hi, (name, a, walks, lo, hi)
+        assert int(t[a, COL_PP_WALK_MIXED]) <= walks, (name, a)
+        tot_walks, tot_batches, tot_cubes = tot_walks + walks, tot_batches + m["batches_split"], tot_cubes + cubes
+    assert tot_cubes > 0 and tot_walks > 0, name
+    if tot_cubes < 32 * tot_batches:  # sparse batches: the lists need fewer walks than one per split batch
+        assert tot_walks < tot_batches, (name, tot_walks, tot_batches)
+
+
+def test_corners_drains_mix_partitions(device):
+    """`corners` holds two regions at opposite ends of the red axis: some drain walks cubes of several partitions"""
+    for seed in SEEDS:
+        mixed = device["corners", seed][2][:, COL_PP_WALK_MIXED]
+        print(f"corners seed {seed}: drains over more than one partition per attempt {mixed.tolist()}")
+        assert (mixed > 0).any(), seed
+
+
+def test_sparse_attempts_with_partial_drains_only(runs, device):
+    """`sparse` has attempts in which every round lists fewer than 64 cubes in all (the model's round_cubes, which
+    do not depend on the waves): every drain of such an attempt is a sweep-end flush of a short list."""
+    seen = 0
+    for seed in SEEDS:
+        model, t = runs["sparse", seed][3], device["sparse", seed][2]
+        for a in range(10):
+            rc = model[a][1]["round_cubes"]
+            if sum(rc) > 0 and max(rc) < 64:
+                walks, lanes = int(t[a, COL_PP_WALKS]), int(t[a, COL_PP_WALK_LANES])
+                print(f"sparse seed {seed} attempt {a}: cubes per round {rc}, walks {walks}, live lanes {lanes}")
+                assert int(t[a, COL_PP_SPLIT_CUBES]) == sum(rc) and lanes == model[a][1]["lanes"], (seed, a)
+                # a round's flushes: at most one per wave and per listed cube, each at most three passes
+                assert sum(r > 0 for r in rc) <= walks <= 3 * sum(min(r, KW_WIDE) for r in rc), (seed, a, walks, rc)
+                seen += 1
+    assert seen >= 1
+
+
+def test_cubes_only_sweep_lists_nothing(runs, device):
+    for seed in SEEDS:
+        t = device["ties", seed][2]
+        assert not t[:, [COL_PP_SPLIT_CUBES, COL_PP_WALKS, COL_PP_WALK_LANES, COL_PP_WALK_MIXED]].any(), seed
+        assert all(m["split_cubes"] == 0 and m["lanes"] == 0 for _, m in runs["ties", seed][3]), seed
+
+
+def test_both_build_widths_list_and_agree(backend, tmp_path, monkeypatch):
+    """8 photos of 160 x 160 (cells path) as a batch of 8 (80 attempts: the 512-thread build, 8 lists) and as the
+    first 8 of a batch of 104 (1 040 attempts: the 256-thread build, 4 lists), same indices and seed: every
+    attempt's fields, its k-means++ counters and its live lanes are equal; the walk counts may differ and obey
+    the bounds of their width."""
+    big = np.stack([synth.synth_numpy(2 * i + 1, 160, 160, seed=2025) for i in range(104)])
+    runs_ = []
+    for tag, batch, kw in (("wide", big[:8], 8), ("narrow", big, 4)):
+        trace = tmp_path / f"km_trace_{tag}.txt"
+        monkeypatch.setenv("LLFE_KM_TRACE", str(trace))
+        res = backend.process(batch, ("colors",), seed=77, index_base=0)[:8]
+        att = backend.kmeans_attempts(len(batch))[:8]
+        t = _read_trace(trace)
+        assert t.shape[0] == 10 * len(batch), (tag, t.shape)
+        t = t[:80]
+        cubes, walks, lanes = t[:, COL_PP_SPLIT_CUBES], t[:, COL_PP_WALKS], t[:, COL_PP_WALK_LANES]
+        print(f"{tag}: k-means++ split cubes {int(cubes.sum())}, walks {int(walks.sum())}, live lanes {int(lanes.sum())}"
+              f" ({lanes.sum() / max(walks.sum(), 1):.1f} per walk), mixed drains {int(t[:, COL_PP_WALK_MIXED].sum())}")
+        assert cubes.sum() > 0 and walks.sum() > 0, tag
+        for a in range(80):
+            extra = int(lanes[a] - cubes[a])  # = und2 + 2 und3
+            drains = int(lanes[a]) // 64 + kw * ROUNDS
+            assert extra >= 0 and -(-int(lanes[a]) // 64) <= walks[a] <= drains + min(2 * drains, extra), (tag, a)
+        runs_.append((res, att, t[:, [COL_PP_PTS, COL_PP_SPLIT_CUBES, COL_PP_SPLIT_PTS, COL_PP_WALK_LANES]]))
+    (ra, aa, ta), (rb, ab, tb) = runs_
+    assert np.array_equal(ta, tb)
+    for i in range(8):
+        assert ra[i].n_unique == rb[i].n_unique, i
+        assert np.array_equal(np.asarray(ra[i].centers_rgb), np.asarray(rb[i].centers_rgb)), i
+        assert np.array_equal(np.asarray(ra[i].counts), np.asarray(rb[i].counts)), i
+        assert ra[i].compactness == rb[i].compactness, i
+        for a in range(10):
+            for f in ("pp_centers", "centers", "counts"):
+                assert np.array_equal(aa[i][a][f], ab[i][a][f]), (i, a, f)
+            assert aa[i][a]["iters"] == ab[i][a]["iters"] and aa[i][a]["compactness"] == ab[i][a]["compactness"], (i, a)

@@ -32,6 +32,9 @@ def main():
     # 64-lane walks that split those cubes, the partial ones among them (columns 25, 26; older builds walked
     # inside a cube batch and did not count: zeros)
     sp_walks, sp_part = (a.T[25], a.T[26]) if a.shape[1] >= 27 else (z, z)
+    # 64-lane walks of k-means++'s split cubes, their live lanes, the walks over more than one partition (columns
+    # 27..29; builds that walked inside the cube batch did not count: zeros)
+    ppw, ppw_lanes, ppw_mixed = (a.T[27], a.T[28], a.T[29]) if a.shape[1] >= 30 else (z, z, z)
     dh = a.T[19].astype(np.uint64) if a.shape[1] >= 20 else z.astype(np.uint64)
     ok = it > 1
     pp = (tpp - t0) / 100.0
@@ -58,6 +61,9 @@ def main():
                   f" selection time {t_sel[m].mean() / 1e3:.3f} ms; Lloyd sweeps {t_sw[m].mean() / 1e3:.3f} ms")
             print(f"      k-means++ split in place: {pps_cubes[m].mean():.0f} cubes, {np.mean(pps_pts[m] / U[m]):.3f} U of colours per attempt"
                   f" (sums over the class: {pps_cubes[m].sum()} cubes, {pps_pts[m].sum()} colours)")
+            if ppw[m].any():
+                print(f"      k-means++ split walks per attempt {ppw[m].mean():.1f} ({ppw_mixed[m].mean():.1f} of them over more than one partition),"
+                      f" live lanes per walk {ppw_lanes[m].sum() / ppw[m].sum():.1f}")
         if dh[m].any():
             bins = np.stack([((dh[m] >> np.uint64(8 * b)) & np.uint64(255)).astype(np.int64) for b in range(8)], 1)
             print("      iterations by largest centre move [<.25 <.5 <1 <2 <4 <8 <16 >=16]:",
