@@ -512,7 +512,7 @@ int llfe_jpeg_reconstruct(llfe_ctx *ctx, const uint8_t *coefs, int64_t slot_stri
                           int32_t n, int32_t h, int32_t w, uint8_t *out_bgr, llfe_stream stream);
 
 /* ---- the entropy half on the device too (opt-in): baseline sequential Huffman files with one
- * interleaved scan and no restart markers.  The host only parses the headers; the file's scan
+ * interleaved scan, without restart markers or (llfe_jpeg_parse_batch_flags) with them.  The host only parses the headers; the file's scan
  * bytes cross to the device instead of its coefficients, csrc/jpeg_huff.hip writes exactly the
  * coefficient slots llfe_jpeg_read_coefs_batch writes, and llfe_jpeg_reconstruct runs on them
  * unchanged.
@@ -522,7 +522,7 @@ int llfe_jpeg_reconstruct(llfe_ctx *ctx, const uint8_t *coefs, int64_t slot_stri
  *   table_offset   four decode tables (DC 0, DC 1, AC 0, AC 1) of LLFE_JPEG_HUFF_TABLE_BYTES:
  *                  u32 lim[18], i32 off[18], u8 vals[256] (csrc/jpeg_huff_core.h)
  *   scan_offset    the scan's entropy-coded bytes as they are in the file (stuffed FF 00 pairs
- *                  included), zero padded to a multiple of 16 plus 16
+ *                  and restart markers included), zero padded to a multiple of 16 plus 16
  * llfe_jpeg_scan (a host array, like llfe_jpeg_desc) says where, and carries the MCU geometry. */
 #define LLFE_JPEG_HUFF_TABLE_BYTES 400
 #define LLFE_JPEG_RECORD_HEADER 2048 /* bytes of a record in front of its scan bytes */
@@ -536,7 +536,7 @@ typedef struct {
     uint8_t blk_x[8], blk_y[8];   /*   its place inside the MCU in blocks, */
     uint8_t blk_dc[8], blk_ac[8]; /*   its DC and AC table (0 or 1) */
     uint8_t comp_hs[4], comp_vs[4]; /* per component: blocks per MCU across and down */
-    int32_t reserved;
+    int32_t restart_interval;     /* MCUs between restart markers (the file's DRI), 0..65535; 0: none */
 } llfe_jpeg_scan; /* 88 bytes */
 /* host only, no ctx: the host half.  Parses n blobs of one size on `threads` host threads into
  * staging (host, n x record_stride bytes; record_stride a multiple of 16, at least
@@ -550,16 +550,31 @@ typedef struct {
  * Anything else is LLFE_ERR_UNSUPPORTED (progressive, arithmetic, restart intervals,
  * multi-scan, EXIF orientation != 1, CMYK, other formats): nothing is written for it,
  * descs[i].n_comp and scans[i].blocks_in_mcu are 0, and it takes llfe_jpeg_read_coefs_batch
- * or llfe_decode_batch.  status[i] per image; returns the first non-OK status. */
+ * or llfe_decode_batch.  status[i] per image; returns the first non-OK status.  This is
+ * llfe_jpeg_parse_batch_flags with flags = 0: every record it stages has restart_interval 0. */
 int llfe_jpeg_parse_batch(const uint8_t *const *data, const uint64_t *sizes, int32_t n, int32_t height, int32_t width,
                           uint8_t *staging, int64_t record_stride, int64_t slot_stride, llfe_jpeg_desc *descs,
                           llfe_jpeg_scan *scans, int32_t *status, int32_t threads);
+/* The same with flags (any other bit is LLFE_ERR_INVALID).  LLFE_JPEG_PARSE_RESTARTS: files with
+ * a restart interval (a DRI of 1..65535, the value libjpeg's jpeg_read_header reports) are
+ * eligible as well.  Inside the scan of such a file an FF is followed by 00, by D0..D7, or by the
+ * terminating D9; FF FF fill bytes and every other marker stay LLFE_ERR_UNSUPPORTED.  The scan
+ * is staged raw, markers included, and scans[i].restart_interval holds the DRI.  The parser does
+ * not decode: whether the markers stand where the interval says is decided by
+ * llfe_jpeg_entropy_decode / llfe_jpeg_entropy_reference, which hand the image back if not.  A
+ * DRI of 0, or one no marker follows because it is not below the MCU count, is a restart-free
+ * scan. */
+#define LLFE_JPEG_PARSE_RESTARTS 1u
+int llfe_jpeg_parse_batch_flags(const uint8_t *const *data, const uint64_t *sizes, int32_t n, int32_t height,
+                                int32_t width, uint8_t *staging, int64_t record_stride, int64_t slot_stride,
+                                llfe_jpeg_desc *descs, llfe_jpeg_scan *scans, int32_t *status, int32_t threads,
+                                uint32_t flags);
 /* host only: the plain C++ twin of llfe_jpeg_entropy_decode over host memory (staging and
  * slots on the host), for tests and for debugging the kernels: the same subsequences, rounds,
  * verification, block scan, write pass and DC sums, run serially.  one_piece != 0: decode each
  * scan from its first bit to its last in one piece instead.  The same validation; status[i]:
  * LLFE_OK, or LLFE_ERR_UNSUPPORTED for an image that was not staged or whose scan shows an
- * anomaly. */
+ * anomaly, misplaced restart markers (below) included. */
 int llfe_jpeg_entropy_reference(const uint8_t *staging, int64_t staging_bytes, const llfe_jpeg_scan *scans,
                                 const llfe_jpeg_desc *descs, int32_t n, int32_t h, int32_t w, uint8_t *slots,
                                 int64_t slot_stride, int32_t *status, int32_t one_piece);
@@ -567,14 +582,17 @@ int llfe_jpeg_entropy_reference(const uint8_t *staging, int64_t staging_bytes, c
  * (device, n x slot_stride).  scans and descs are host arrays and are validated on the host
  * before anything is launched: every record, table and scan extent inside staging_bytes,
  * every descriptor inside its slot (as llfe_jpeg_reconstruct checks it), the MCU geometry
- * covering the block grids; a bad one is LLFE_ERR_INVALID with the slots untouched.  Images
+ * covering the block grids, restart_interval in 0..65535; a bad one is LLFE_ERR_INVALID with the slots untouched.  Images
  * with blocks_in_mcu == 0 are skipped.  The kernels read nothing outside what was validated
  * (the bit reader is bounded by scan_bytes) and every loop has a bound fixed on the host.
  * status_out (host, n): LLFE_OK for an image whose slot now holds its quantisation tables and
  * coefficients, LLFE_ERR_UNSUPPORTED for one that was skipped or whose scan showed an anomaly
  * (no such code, a coefficient index past 63, a DC category above 11 or an AC category above
  * 10, the scan not ending inside its last byte, leftover bits that are not 1-padding, a block
- * count other than the frame's, the verification of the subsequence states failing): its slot
+ * count other than the frame's, the verification of the subsequence states failing; with a
+ * restart interval Ri also: a marker met anywhere but at an MCU boundary behind 0..7 one-bits,
+ * the k-th marker (k = 0, 1, ...) not FF D0 + (k & 7) or not behind exactly (k + 1) * Ri MCUs,
+ * two adjacent markers, a marker behind the last MCU, a marker missing): its slot
  * may hold anything and the caller decodes it another way.  Runs on `stream` and returns when
  * it has finished. */
 int llfe_jpeg_entropy_decode(llfe_ctx *ctx, const uint8_t *staging, int64_t staging_bytes, const llfe_jpeg_scan *scans,

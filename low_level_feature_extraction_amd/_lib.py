@@ -168,13 +168,14 @@ class LlfeJpegScan(C.Structure):
         ("blk_ac", C.c_uint8 * 8),
         ("comp_hs", C.c_uint8 * 4),
         ("comp_vs", C.c_uint8 * 4),
-        ("reserved", C.c_int32),
+        ("restart_interval", C.c_int32),
     ]
 
 
 JPEG_GRAY, JPEG_444, JPEG_422, JPEG_420 = 1, 2, 3, 4  # LLFE_JPEG_*
 JPEG_HUFF_TABLE_BYTES, JPEG_RECORD_HEADER = 400, 2048  # LLFE_JPEG_HUFF_TABLE_BYTES, LLFE_JPEG_RECORD_HEADER
 JPEG_SUBSEQUENCE_BYTES = 128  # csrc/jpeg_huff_core.h kSub
+JPEG_PARSE_RESTARTS = 1  # LLFE_JPEG_PARSE_RESTARTS
 
 # every symbol declared in include/llfe.h, with its ctypes signature
 _vp, _i32, _i64, _u32, _u64 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_uint64
@@ -246,6 +247,8 @@ SIGNATURES = {
     "llfe_jpeg_reconstruct": (C.c_int, [_vp, _vp, _i64, C.POINTER(LlfeJpegDesc), _i32, _i32, _i32, _vp, _vp]),
     "llfe_jpeg_parse_batch": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _i64, _i64, C.POINTER(LlfeJpegDesc),
                                         C.POINTER(LlfeJpegScan), _vp, _i32]),
+    "llfe_jpeg_parse_batch_flags": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _i64, _i64, C.POINTER(LlfeJpegDesc),
+                                              C.POINTER(LlfeJpegScan), _vp, _i32, _u32]),
     "llfe_jpeg_entropy_reference": (C.c_int, [_vp, _i64, C.POINTER(LlfeJpegScan), C.POINTER(LlfeJpegDesc), _i32, _i32,
                                               _i32, _vp, _i64, _vp, _i32]),
     "llfe_jpeg_entropy_decode": (C.c_int, [_vp, _vp, _i64, C.POINTER(LlfeJpegScan), C.POINTER(LlfeJpegDesc), _i32, _i32,

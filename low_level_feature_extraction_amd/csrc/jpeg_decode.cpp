@@ -476,12 +476,14 @@ struct Walk {
     int nc = 0;
     uint8_t cid[3] = {0}, hv[3] = {0}, td[3] = {0}, ta[3] = {0};
     size_t scan_begin = 0, scan_end = 0;
+    unsigned ri = 0;  // the last DRI in front of the scan
 };
 
 // The marker walk: one SOF0 / SOF1, the DHTs, exactly one SOS with every component and the
 // whole spectrum, no restart interval, and the scan ending at an FF D9 that is the first marker
-// after it.  Everything else is for another decoder.
-int walk(const uint8_t *d, size_t n, Dht (&dht)[4], Walk &W) {
+// after it.  restarts: a restart interval is taken too, and the scan of a file that has one may
+// hold FF D0..D7 (where, is for the decoder to check).  Everything else is for another decoder.
+int walk(const uint8_t *d, size_t n, Dht (&dht)[4], Walk &W, bool restarts) {
     size_t p = 2;
     bool sof = false;
     for (;;) {
@@ -518,7 +520,9 @@ int walk(const uint8_t *d, size_t n, Dht (&dht)[4], Walk &W) {
         } else if (m >= 0xC2 && m <= 0xCF) {  // progressive, lossless, arithmetic, DAC
             return LLFE_ERR_UNSUPPORTED;
         } else if (m == 0xDD) {
-            if (sl != 2 || s[0] || s[1]) return LLFE_ERR_UNSUPPORTED;  // a restart interval
+            if (sl != 2) return LLFE_ERR_UNSUPPORTED;
+            W.ri = (unsigned)s[0] << 8 | s[1];
+            if (W.ri && !restarts) return LLFE_ERR_UNSUPPORTED;  // a restart interval
         } else if (m == 0xDA) {
             if (!sof || sl < 1 || s[0] != W.nc || sl != 4 + 2 * (size_t)W.nc) return LLFE_ERR_UNSUPPORTED;
             for (int c = 0; c < W.nc; c++) {
@@ -540,7 +544,11 @@ int walk(const uint8_t *d, size_t n, Dht (&dht)[4], Walk &W) {
                     q += 2;
                     continue;
                 }
-                if (d[q + 1] != 0xD9) return LLFE_ERR_UNSUPPORTED;  // RSTn, another scan, fill bytes
+                if (W.ri && d[q + 1] >= 0xD0 && d[q + 1] <= 0xD7) {
+                    q += 2;
+                    continue;
+                }
+                if (d[q + 1] != 0xD9) return LLFE_ERR_UNSUPPORTED;  // RSTn without a DRI, another scan, fill bytes
                 W.scan_end = q;
                 return W.scan_end > W.scan_begin ? LLFE_OK : LLFE_ERR_UNSUPPORTED;
             }
@@ -552,7 +560,7 @@ int walk(const uint8_t *d, size_t n, Dht (&dht)[4], Walk &W) {
 // parse one image and stage its record; every eligibility check comes before the first byte is
 // written
 int parse_one(const uint8_t *data, size_t size, int32_t h, int32_t w, uint8_t *rec, int64_t record_offset,
-              int64_t record_stride, int64_t slot_bytes, llfe_jpeg_desc *desc, llfe_jpeg_scan *scan) {
+              int64_t record_stride, int64_t slot_bytes, llfe_jpeg_desc *desc, llfe_jpeg_scan *scan, bool restarts) {
     const Api &A = api();
     if (!A.ok) return LLFE_ERR_UNSUPPORTED;
     if (size < 3 || data[0] != 0xFF || data[1] != 0xD8 || data[2] != 0xFF) return LLFE_ERR_UNSUPPORTED;
@@ -575,17 +583,18 @@ int parse_one(const uint8_t *data, size_t size, int32_t h, int32_t w, uint8_t *r
     const ComponentInfo *comp = (const ComponentInfo *)ci.comp_info;
     int sampling = 0;
     volatile int rc = classify(ci, comp, h, w, &sampling);
-    if (rc == LLFE_OK && (ci.progressive_mode || ci.arith_code || ci.restart_interval != 0 || err.mgr.num_warnings != 0))
+    if (rc == LLFE_OK && (ci.progressive_mode || ci.arith_code || (ci.restart_interval != 0 && !restarts) ||
+                          ci.restart_interval > 65535 || err.mgr.num_warnings != 0))
         rc = LLFE_ERR_UNSUPPORTED;
     llfe_jpeg_desc d;
     memset(&d, 0, sizeof d);
     if (rc == LLFE_OK) rc = geometry(comp, nc, sampling, h, w, slot_bytes, false, &d);
     Dht dht[4];
     Walk W;
-    if (rc == LLFE_OK) rc = walk(data, size, dht, W);
+    if (rc == LLFE_OK) rc = walk(data, size, dht, W, restarts);
     const QuantTbl *qt[3] = {nullptr, nullptr, nullptr};
     if (rc == LLFE_OK) {  // this walk and the library's agree on the frame
-        if (W.nc != nc) rc = LLFE_ERR_UNSUPPORTED;
+        if (W.nc != nc || W.ri != ci.restart_interval) rc = LLFE_ERR_UNSUPPORTED;
         for (int c = 0; c < nc && rc == LLFE_OK; c++) {
             const ComponentInfo &k = comp[c];
             if (W.cid[c] != k.component_id || W.hv[c] != (k.h_samp_factor << 4 | k.v_samp_factor) || k.quant_tbl_no < 0 ||
@@ -630,6 +639,7 @@ int parse_one(const uint8_t *data, size_t size, int32_t h, int32_t w, uint8_t *r
                 }
         }
         s.blocks_in_mcu = b;
+        s.restart_interval = (int32_t)W.ri;
         memset(rec, 0, LLFE_JPEG_RECORD_HEADER);
         for (int c = 0; c < nc; c++) memcpy(rec + s.quant_offset + 128 * c, qt[c]->quantval, 128);
         memcpy(rec + s.table_offset, tabs, sizeof tabs);
@@ -642,7 +652,9 @@ int parse_one(const uint8_t *data, size_t size, int32_t h, int32_t w, uint8_t *r
     return rc;
 }
 
-// One image of llfe_jpeg_entropy_reference: the phases of jpeg_huff.hip, serially.
+// One image of llfe_jpeg_entropy_reference: the phases of jpeg_huff.hip, serially.  RST: the
+// record has a restart interval.
+template <bool RST>
 int reference_one(const uint8_t *rec, const llfe_jpeg_scan &sc, const llfe_jpeg_desc &d, uint8_t *slot, bool one_piece) {
     using namespace llfe_huff;
     static const uint8_t nat[64] = {LLFE_JPEG_NATURAL_ORDER};
@@ -660,9 +672,10 @@ int reference_one(const uint8_t *rec, const llfe_jpeg_scan &sc, const llfe_jpeg_
     const Geometry g{&sc, &d, slot};
     std::vector<State> in((size_t)nsub), out((size_t)nsub), prev;
     std::vector<int> cnt((size_t)nsub, 0), first((size_t)nsub, 0);
+    std::vector<Marks> marks((size_t)nsub, Marks{0, 0, 0, 0});
     for (int i = 0; i < nsub; i++) {  // phase 2: every lane from its guess ...
-        in[i] = i ? State{sub_start(scan, len, i), 0} : start;
-        out[i] = decode_sub<false>(scan, len, tabs, sc, in[i], end_of(i), &cnt[i], nat, g, nullptr, 0, 0);
+        in[i] = i ? State{sub_start<RST>(scan, len, i), 0} : start;
+        out[i] = decode_sub<false, RST>(scan, len, tabs, sc, in[i], end_of(i), &cnt[i], nat, g, nullptr, 0, 0, &marks[i]);
     }
     for (int r = 0; r < nsub; r++) {  // ... then rounds from the predecessor's exit state
         prev = out;
@@ -670,26 +683,35 @@ int reference_one(const uint8_t *rec, const llfe_jpeg_scan &sc, const llfe_jpeg_
         for (int i = 1; i < nsub; i++)
             if (prev[i - 1].pos != kNone && !same(prev[i - 1], in[i])) {
                 in[i] = prev[i - 1];
-                out[i] = decode_sub<false>(scan, len, tabs, sc, in[i], end_of(i), &cnt[i], nat, g, nullptr, 0, 0);
+                out[i] = decode_sub<false, RST>(scan, len, tabs, sc, in[i], end_of(i), &cnt[i], nat, g, nullptr, 0, 0,
+                                                &marks[i]);
                 changed = true;
             }
         if (!changed) break;
     }
     int sum = 0;  // phases 3 and 4
+    int64_t k = 0;  // RST: the markers in front of lane i
     for (int i = 0; i < nsub; i++) {
         if (out[i].pos == kNone || !same(in[i], i ? out[i - 1] : start)) return LLFE_ERR_UNSUPPORTED;
         first[i] = sum;
+        const Marks &m = marks[(size_t)i];
+        if (RST && (m.bad || (m.n > 0 && ((int64_t)sum + m.first != (k + 1) * sc.restart_interval * sc.blocks_in_mcu ||
+                                          m.idx != (int)(k & 7)))))
+            return LLFE_ERR_UNSUPPORTED;
         sum += cnt[i];
+        k += m.n;
     }
     if (sum != total || out[nsub - 1].pos != (uint32_t)len * 8u || out[nsub - 1].bz != 0) return LLFE_ERR_UNSUPPORTED;
+    if (RST && k != (sc.mcus_w * sc.mcus_h - 1) / sc.restart_interval) return LLFE_ERR_UNSUPPORTED;
     std::vector<int16_t> dcd((size_t)total, 0);
     for (int i = 0; i < nsub; i++) {  // phase 5
         int n = 0;
-        decode_sub<true>(scan, len, tabs, sc, in[i], end_of(i), &n, nat, g, dcd.data(), first[i], total);
+        decode_sub<true, RST>(scan, len, tabs, sc, in[i], end_of(i), &n, nat, g, dcd.data(), first[i], total, nullptr);
     }
     int dc[3] = {0, 0, 0};  // phase 6
     for (int blk = 0; blk < total; blk++) {
         int c;
+        if (RST && blk % (sc.restart_interval * sc.blocks_in_mcu) == 0) dc[0] = dc[1] = dc[2] = 0;
         int16_t *dst = locate(g, blk, &c);
         dc[c] += dcd[(size_t)blk];
         if (dst) dst[0] = (int16_t)dc[c];
@@ -748,10 +770,11 @@ extern "C" int llfe_jpeg_read_coefs_batch(const uint8_t *const *data, const uint
     return LLFE_OK;
 }
 
-extern "C" int llfe_jpeg_parse_batch(const uint8_t *const *data, const uint64_t *sizes, int32_t n, int32_t height,
-                                     int32_t width, uint8_t *staging, int64_t record_stride, int64_t slot_stride,
-                                     llfe_jpeg_desc *descs, llfe_jpeg_scan *scans, int32_t *status, int32_t threads) {
-    if (n < 0 || (n && (!data || !sizes || !staging || !descs || !scans || !status)) || height <= 0 || width <= 0 ||
+extern "C" int llfe_jpeg_parse_batch_flags(const uint8_t *const *data, const uint64_t *sizes, int32_t n, int32_t height,
+                                           int32_t width, uint8_t *staging, int64_t record_stride, int64_t slot_stride,
+                                           llfe_jpeg_desc *descs, llfe_jpeg_scan *scans, int32_t *status, int32_t threads,
+                                           uint32_t flags) {
+    if ((flags & ~LLFE_JPEG_PARSE_RESTARTS) || n < 0 || (n && (!data || !sizes || !staging || !descs || !scans || !status)) || height <= 0 || width <= 0 ||
         height > 65535 || width > 65535 || slot_stride < 0 || record_stride < LLFE_JPEG_RECORD_HEADER ||
         (record_stride & 15))
         return LLFE_ERR_INVALID;
@@ -765,7 +788,8 @@ extern "C" int llfe_jpeg_parse_batch(const uint8_t *const *data, const uint64_t 
             try {
                 const int64_t off = (int64_t)i * record_stride;
                 rc = data[i] ? llfe_jpeg::parse_one(data[i], (size_t)sizes[i], height, width, staging + off, off,
-                                                    record_stride, slot_stride, &descs[i], &scans[i])
+                                                    record_stride, slot_stride, &descs[i], &scans[i],
+                                                    (flags & LLFE_JPEG_PARSE_RESTARTS) != 0)
                              : LLFE_ERR_INVALID;
             } catch (const std::bad_alloc &) {
                 rc = LLFE_ERR_OOM;
@@ -780,6 +804,13 @@ extern "C" int llfe_jpeg_parse_batch(const uint8_t *const *data, const uint64_t 
     for (int i = 0; i < n; i++)
         if (status[i]) return status[i];
     return LLFE_OK;
+}
+
+extern "C" int llfe_jpeg_parse_batch(const uint8_t *const *data, const uint64_t *sizes, int32_t n, int32_t height,
+                                     int32_t width, uint8_t *staging, int64_t record_stride, int64_t slot_stride,
+                                     llfe_jpeg_desc *descs, llfe_jpeg_scan *scans, int32_t *status, int32_t threads) {
+    return llfe_jpeg_parse_batch_flags(data, sizes, n, height, width, staging, record_stride, slot_stride, descs, scans,
+                                       status, threads, 0);
 }
 
 extern "C" int llfe_jpeg_entropy_reference(const uint8_t *staging, int64_t staging_bytes, const llfe_jpeg_scan *scans,
@@ -797,8 +828,9 @@ extern "C" int llfe_jpeg_entropy_reference(const uint8_t *staging, int64_t stagi
         for (int i = 0; i < n; i++)
             status[i] = scans[i].blocks_in_mcu == 0
                             ? LLFE_ERR_UNSUPPORTED
-                            : llfe_jpeg::reference_one(staging + scans[i].record_offset, scans[i], descs[i],
-                                                       slots + (size_t)i * (size_t)slot_stride, one_piece != 0);
+                            : (scans[i].restart_interval ? llfe_jpeg::reference_one<true> : llfe_jpeg::reference_one<false>)(
+                                  staging + scans[i].record_offset, scans[i], descs[i],
+                                  slots + (size_t)i * (size_t)slot_stride, one_piece != 0);
     } catch (const std::bad_alloc &) {
         return LLFE_ERR_OOM;
     }

@@ -33,6 +33,16 @@
 //                  included) to a side array in scan order.
 //   k_huff_dc      one workgroup per image: per-component prefix sums over the DC differences
 //                  of all blocks in scan order, scattered to the real blocks.
+// Restart intervals.  Every kernel behind k_huff_init exists twice, <RST = false> for the images
+// whose record has restart_interval 0 and <true> for the others; each instance skips the other's
+// images, and the host launches an instance only when the batch has images for it, so a batch
+// without restart intervals runs the launches and the code it always ran.  With RST the lanes
+// cross markers (jpeg_huff_core.h) and keep, next to the block count, the Marks of their last
+// decode; k_huff_verify scans the marker counts along with the block counts and accepts an
+// image only if no lane's Marks are bad, the first marker of every lane is the one its ordinal k
+// asks for (FF D0 + (k & 7), behind exactly (k + 1) * Ri * blocks_in_mcu blocks) and the markers
+// are (MCUs - 1) / Ri in all; the later markers of a lane are checked against its first one by
+// the decode itself.  k_huff_dc restarts its sums at every interval (a segmented scan).
 // Everything an image's lanes write lies in its own slot and its own rows of the workspace.
 // Every index derives from records and descriptors the host validated (validate_scans,
 // validate_jpeg_descs); every loop has a bound that follows from the scan length.
@@ -53,6 +63,7 @@ struct Ws {
     int *cnt, *first;  // n x max_sub
     State *bnd;        // 2 x n x max_wg: the last exit state of each workgroup, double-buffered
     int16_t *dcd;      // n x max_blocks
+    Marks *marks;      // n x max_sub (RST)
     int max_sub, max_wg, max_blocks;
 };
 
@@ -71,6 +82,7 @@ Ws carve(uint8_t *base, int n, int max_sub, int max_blocks, size_t *bytes) {
     w.first = (int *)(base + o), o += up16(lanes * sizeof(int));
     w.bnd = (State *)(base + o), o += up16(2 * (size_t)n * (size_t)w.max_wg * sizeof(State));
     w.dcd = (int16_t *)(base + o), o += up16((size_t)n * (size_t)max_blocks * sizeof(int16_t));
+    w.marks = (Marks *)(base + o), o += up16(lanes * sizeof(Marks));
     *bytes = o;
     return w;
 }
@@ -121,6 +133,7 @@ __global__ __launch_bounds__(HT) void k_huff_init(const uint8_t *__restrict__ st
     }
 }
 
+template <bool RST>
 __global__ __launch_bounds__(HT) void k_huff_sync(const uint8_t *__restrict__ staging,
                                                   const llfe_jpeg_scan *__restrict__ scans,
                                                   const llfe_jpeg_desc *__restrict__ descs, const int *__restrict__ status,
@@ -128,7 +141,7 @@ __global__ __launch_bounds__(HT) void k_huff_sync(const uint8_t *__restrict__ st
     __shared__ Shared S;
     __shared__ State lds_out[HT];
     const int img = blockIdx.y, g = blockIdx.x, t = threadIdx.x;
-    if (status[img] != 0) return;  // (whole workgroup)
+    if (status[img] != 0 || (scans[img].restart_interval != 0) != RST) return;  // (whole workgroup)
     const int len = scans[img].scan_bytes, nsub = subsequences(len);
     if (g * HT >= nsub) return;  // (whole workgroup)
     load_shared(S, staging, &scans[img], &descs[img]);
@@ -144,14 +157,16 @@ __global__ __launch_bounds__(HT) void k_huff_sync(const uint8_t *__restrict__ st
     const Geometry geo{&sc, &S.d, nullptr};
     State in = none, out = none;
     int cnt = 0;
+    Marks mk{0, 0, 0, 0};
     if (act) {
         if (pass == 0) {
-            in = i ? State{sub_start(scan, len, i), 0} : start;
-            out = decode_sub<false>(scan, len, tabs, sc, in, end, &cnt, nat, geo, nullptr, 0, 0);
+            in = i ? State{sub_start<RST>(scan, len, i), 0} : start;
+            out = decode_sub<false, RST>(scan, len, tabs, sc, in, end, &cnt, nat, geo, nullptr, 0, 0, &mk);
         } else {
             in = w.in[lane];
             out = w.out[lane];
             cnt = w.cnt[lane];
+            if (RST) mk = w.marks[lane];
         }
     }
     // the exit state in front of this workgroup: what its predecessor left in the last launch
@@ -164,7 +179,7 @@ __global__ __launch_bounds__(HT) void k_huff_sync(const uint8_t *__restrict__ st
         const bool redo = act && prev.pos != kNone && !same(prev, in);
         if (redo) {
             in = prev;
-            out = decode_sub<false>(scan, len, tabs, sc, in, end, &cnt, nat, geo, nullptr, 0, 0);
+            out = decode_sub<false, RST>(scan, len, tabs, sc, in, end, &cnt, nat, geo, nullptr, 0, 0, &mk);
         }
         if (!__syncthreads_or(redo)) break;
     }
@@ -172,55 +187,73 @@ __global__ __launch_bounds__(HT) void k_huff_sync(const uint8_t *__restrict__ st
         w.in[lane] = in;
         w.out[lane] = out;
         w.cnt[lane] = cnt;
+        if (RST) w.marks[lane] = mk;
         if (t == HT - 1 || i == nsub - 1) w.bnd[((int64_t)((pass + 1) & 1) * n + img) * w.max_wg + g] = out;
     }
 }
 
+template <bool RST>
 __global__ __launch_bounds__(HT) void k_huff_verify(const llfe_jpeg_scan *__restrict__ scans, int *__restrict__ status,
                                                     Ws w) {
     __shared__ int s_scan[HT];
+    __shared__ int s_mark[RST ? HT : 1];
     const int img = blockIdx.x, t = threadIdx.x;
-    if (status[img] != 0) return;  // (whole workgroup)
+    if (status[img] != 0 || (scans[img].restart_interval != 0) != RST) return;  // (whole workgroup)
     const llfe_jpeg_scan &sc = scans[img];
     const int len = sc.scan_bytes, nsub = subsequences(len);
     const int total = sc.mcus_w * sc.mcus_h * sc.blocks_in_mcu;
     const int64_t row = (int64_t)img * w.max_sub;
-    int bad = 0, carry = 0;
+    int bad = 0, carry = 0, mcarry = 0;  // mcarry: the markers in front of this round's lanes
     for (int base = 0; base < nsub; base += HT) {
         const int i = base + t;
         int c = 0;
+        Marks mk{0, 0, 0, 0};
         if (i < nsub) {
             const State o = w.out[row + i], e = w.in[row + i];
             const State prev = i ? w.out[row + i - 1] : State{0, 0};
             if (o.pos == kNone || !same(e, prev)) bad = 1;
             c = w.cnt[row + i];
+            if (RST) mk = w.marks[row + i];
         }
         s_scan[t] = c;
+        if (RST) s_mark[t] = mk.n;
         __syncthreads();
         for (int off = 1; off < HT; off <<= 1) {
             const int v = t >= off ? s_scan[t - off] : 0;
+            const int u = RST && t >= off ? s_mark[t - off] : 0;
             __syncthreads();
             s_scan[t] += v;
+            if (RST) s_mark[t] += u;
             __syncthreads();
         }
-        if (i < nsub) w.first[row + i] = carry + s_scan[t] - c;
+        const int first = carry + s_scan[t] - c;
+        if (i < nsub) w.first[row + i] = first;
+        if (RST && mk.n > 0) {  // this lane's first marker is the k-th of the scan
+            const int64_t k = (int64_t)mcarry + s_mark[t] - mk.n;
+            if ((int64_t)first + mk.first != (k + 1) * sc.restart_interval * sc.blocks_in_mcu || mk.idx != (int)(k & 7)) bad = 1;
+        }
+        if (RST && mk.bad) bad = 1;
         carry += s_scan[HT - 1];
+        if (RST) mcarry += s_mark[HT - 1];
         __syncthreads();
     }
     const int any_bad = __syncthreads_or(bad);
     if (t == 0) {
         const State last = w.out[row + nsub - 1];
-        if (any_bad || carry != total || last.pos != (uint32_t)len * 8u || last.bz != 0) status[img] = LLFE_ERR_UNSUPPORTED;
+        bool ok = !any_bad && carry == total && last.pos == (uint32_t)len * 8u && last.bz == 0;
+        if (RST && mcarry != (sc.mcus_w * sc.mcus_h - 1) / sc.restart_interval) ok = false;
+        if (!ok) status[img] = LLFE_ERR_UNSUPPORTED;
     }
 }
 
+template <bool RST>
 __global__ __launch_bounds__(HT) void k_huff_write(const uint8_t *__restrict__ staging,
                                                    const llfe_jpeg_scan *__restrict__ scans,
                                                    const llfe_jpeg_desc *__restrict__ descs, const int *__restrict__ status,
                                                    uint8_t *__restrict__ slots, int64_t slot_stride, Ws w) {
     __shared__ Shared S;
     const int img = blockIdx.y, g = blockIdx.x, t = threadIdx.x;
-    if (status[img] != 0) return;  // (whole workgroup)
+    if (status[img] != 0 || (scans[img].restart_interval != 0) != RST) return;  // (whole workgroup)
     const int len = scans[img].scan_bytes, nsub = subsequences(len);
     if (g * HT >= nsub) return;  // (whole workgroup)
     load_shared(S, staging, &scans[img], &descs[img]);
@@ -236,18 +269,20 @@ __global__ __launch_bounds__(HT) void k_huff_write(const uint8_t *__restrict__ s
     const int first = w.first[lane];
     if (first < 0 || first >= total) return;
     int cnt = 0;
-    decode_sub<true>(rec + sc.scan_offset, len, tabs, sc, w.in[lane], min(len, (i + 1) * kSub), &cnt, nat, geo,
-                     w.dcd + (int64_t)img * w.max_blocks, first, total);
+    decode_sub<true, RST>(rec + sc.scan_offset, len, tabs, sc, w.in[lane], min(len, (i + 1) * kSub), &cnt, nat, geo,
+                          w.dcd + (int64_t)img * w.max_blocks, first, total, nullptr);
 }
 
+template <bool RST>
 __global__ __launch_bounds__(HT) void k_huff_dc(const uint8_t *__restrict__ staging,
                                                 const llfe_jpeg_scan *__restrict__ scans,
                                                 const llfe_jpeg_desc *__restrict__ descs, const int *__restrict__ status,
                                                 uint8_t *__restrict__ slots, int64_t slot_stride, Ws w) {
     __shared__ int s_sum[3][HT];
+    __shared__ int s_cut[RST ? HT : 1];  // RST: a sum restarted in or in front of this lane's MCUs
     __shared__ Shared S;
     const int img = blockIdx.x, t = threadIdx.x;
-    if (status[img] != 0) return;  // (whole workgroup)
+    if (status[img] != 0 || (scans[img].restart_interval != 0) != RST) return;  // (whole workgroup)
     load_shared(S, staging, &scans[img], &descs[img]);
     const llfe_jpeg_scan &sc = S.sc;
     const Geometry geo{&sc, &S.d, slots + (int64_t)img * slot_stride};
@@ -255,9 +290,13 @@ __global__ __launch_bounds__(HT) void k_huff_dc(const uint8_t *__restrict__ stag
     const int bim = sc.blocks_in_mcu;
     const int64_t mcus = (int64_t)sc.mcus_w * sc.mcus_h;
     const int m0 = (int)(mcus * t / HT), m1 = (int)(mcus * (t + 1) / HT);  // this lane's MCUs
-    int sum0 = 0, sum1 = 0, sum2 = 0;
-    for (int m = m0; m < m1; m++)
+    // RST: the predictors are zero at every MCU m with m % Ri == 0, so a lane's sums are those
+    // behind the last such MCU of its range, and the scan across the lanes is a segmented one
+    const int ri = RST ? sc.restart_interval : 1;
+    int sum0 = 0, sum1 = 0, sum2 = 0, cut = 0;
+    for (int m = m0, left = RST ? m0 % ri : 0; m < m1; m++, left = left + 1 == ri ? 0 : left + 1)
         for (int b = 0; b < bim; b++) {
+            if (RST && left == 0 && b == 0) sum0 = sum1 = sum2 = 0, cut = 1;
             const int c = sc.blk_comp[b], v = dcd[m * bim + b];
             sum0 += c == 0 ? v : 0;
             sum1 += c == 1 ? v : 0;
@@ -266,17 +305,29 @@ __global__ __launch_bounds__(HT) void k_huff_dc(const uint8_t *__restrict__ stag
     s_sum[0][t] = sum0;
     s_sum[1][t] = sum1;
     s_sum[2][t] = sum2;
+    if (RST) s_cut[t] = cut;
     __syncthreads();
     for (int off = 1; off < HT; off <<= 1) {
         int v[3];
         for (int c = 0; c < 3; c++) v[c] = t >= off ? s_sum[c][t - off] : 0;
+        const int u = RST && t >= off ? s_cut[t - off] : 0;
+        const bool open = !RST || !s_cut[t];  // nothing restarted yet in what this lane has summed
         __syncthreads();
-        for (int c = 0; c < 3; c++) s_sum[c][t] += v[c];
+        if (open) {
+            for (int c = 0; c < 3; c++) s_sum[c][t] += v[c];
+            if (RST) s_cut[t] = u;
+        }
         __syncthreads();
     }
-    int run0 = s_sum[0][t] - sum0, run1 = s_sum[1][t] - sum1, run2 = s_sum[2][t] - sum2;  // exclusive
-    for (int m = m0; m < m1; m++)
+    int run0, run1, run2;  // exclusive
+    if (RST) {
+        run0 = t ? s_sum[0][t - 1] : 0, run1 = t ? s_sum[1][t - 1] : 0, run2 = t ? s_sum[2][t - 1] : 0;
+    } else {
+        run0 = s_sum[0][t] - sum0, run1 = s_sum[1][t] - sum1, run2 = s_sum[2][t] - sum2;
+    }
+    for (int m = m0, left = RST ? m0 % ri : 0; m < m1; m++, left = left + 1 == ri ? 0 : left + 1)
         for (int b = 0; b < bim; b++) {
+            if (RST && left == 0 && b == 0) run0 = run1 = run2 = 0;
             const int blk = m * bim + b;
             int c;
             int16_t *dst = locate(geo, blk, &c);
@@ -298,33 +349,41 @@ size_t jpeg_huff_workspace_bytes(int n, int max_sub, int max_blocks) {
 
 int jpeg_huff_passes(int max_sub) { return (max_sub + HT - 1) / HT; }
 
-hipError_t launch_jpeg_huff(int stage, int pass, const uint8_t *staging, const llfe_jpeg_scan *d_scans,
+template <bool RST>
+static void launch_stage(int stage, int pass, const uint8_t *staging, const llfe_jpeg_scan *d_scans,
+                         const llfe_jpeg_desc *d_descs, int n, uint8_t *slots, int64_t slot_stride, const Ws &w,
+                         int *d_status, hipStream_t s) {
+    const dim3 lanes((unsigned)w.max_wg, (unsigned)n);
+    switch (stage) {
+    case 1:
+        hipLaunchKernelGGL(k_huff_sync<RST>, lanes, dim3(HT), 0, s, staging, d_scans, d_descs, d_status, w, n, pass);
+        break;
+    case 2:
+        hipLaunchKernelGGL(k_huff_verify<RST>, dim3((unsigned)n), dim3(HT), 0, s, d_scans, d_status, w);
+        break;
+    case 3:
+        hipLaunchKernelGGL(k_huff_write<RST>, lanes, dim3(HT), 0, s, staging, d_scans, d_descs, d_status, slots, slot_stride, w);
+        break;
+    default:
+        hipLaunchKernelGGL(k_huff_dc<RST>, dim3((unsigned)n), dim3(HT), 0, s, staging, d_scans, d_descs, d_status, slots,
+                           slot_stride, w);
+        break;
+    }
+}
+
+hipError_t launch_jpeg_huff(int stage, int pass, int kinds, const uint8_t *staging, const llfe_jpeg_scan *d_scans,
                             const llfe_jpeg_desc *d_descs, int n, int max_sub, int max_blocks, int64_t max_coef_bytes,
                             uint8_t *slots, int64_t slot_stride, uint8_t *workspace, int *d_status, hipStream_t s) {
     if (n <= 0 || max_sub <= 0 || max_blocks <= 0) return hipSuccess;
     size_t bytes = 0;
     const Ws w = carve(workspace, n, max_sub, max_blocks, &bytes);
-    const dim3 lanes((unsigned)w.max_wg, (unsigned)n);
-    switch (stage) {
-    case 0: {
+    if (stage == 0) {
         const int64_t wgs = (max_coef_bytes / 16 + HT - 1) / HT;
         const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>(wgs, 64)), (unsigned)n);
         hipLaunchKernelGGL(k_huff_init, grid, dim3(HT), 0, s, staging, d_scans, d_descs, slots, slot_stride);
-        break;
-    }
-    case 1:
-        hipLaunchKernelGGL(k_huff_sync, lanes, dim3(HT), 0, s, staging, d_scans, d_descs, d_status, w, n, pass);
-        break;
-    case 2:
-        hipLaunchKernelGGL(k_huff_verify, dim3((unsigned)n), dim3(HT), 0, s, d_scans, d_status, w);
-        break;
-    case 3:
-        hipLaunchKernelGGL(k_huff_write, lanes, dim3(HT), 0, s, staging, d_scans, d_descs, d_status, slots, slot_stride, w);
-        break;
-    default:
-        hipLaunchKernelGGL(k_huff_dc, dim3((unsigned)n), dim3(HT), 0, s, staging, d_scans, d_descs, d_status, slots, slot_stride,
-                           w);
-        break;
+    } else {
+        if (kinds & 1) launch_stage<false>(stage, pass, staging, d_scans, d_descs, n, slots, slot_stride, w, d_status, s);
+        if (kinds & 2) launch_stage<true>(stage, pass, staging, d_scans, d_descs, n, slots, slot_stride, w, d_status, s);
     }
     return hipGetLastError();
 }

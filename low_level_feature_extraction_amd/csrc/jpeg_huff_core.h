@@ -12,6 +12,20 @@
 // next).  A subsequence is decoded from an entry state until the position reaches its end
 // byte; the exit state is the first symbol boundary at or past it.
 //
+// Restart intervals (records with restart_interval != 0; everything below marked RST, chosen
+// per image, so a scan without them runs the code it always ran).  The scan then also holds
+// markers FF D0..D7, byte-aligned, each behind an MCU boundary and 0..7 padding 1-bits, and the
+// decoder state behind one is known: block 0 of the MCU, DC next.  A position never lies
+// inside a marker.  The reader stops loading at a marker's FF (an FF followed by anything but
+// 00) and hands out zero bits from there, and its byte accounting stops at that FF, so no bit
+// of a marker or behind it is ever decoded as data.  A lane that stands in front of a marker
+// at a symbol boundary crosses it at once, also when it has already reached its end byte: the
+// position becomes the byte behind the marker and the state (0, 0), so a state is never on the
+// near side of a marker it could cross.  Crossing at an MCU boundary with only 1-bits left in
+// the byte is the regular case; a lane that gets there any other way (mid-block, or having
+// consumed bits past the data) crosses all the same, so that its exit state is the true one
+// whatever its entry state was, and its Marks say so (bad).
+//
 // Every read is bounded by the scan's staged length (bytes past it read as zero) and every
 // table index is masked, so a wrong entry state or a corrupt stream decodes to garbage or to
 // an anomaly, never to an access outside the record.
@@ -60,7 +74,10 @@ struct Reader {
     int rb;        // raw index of the top byte
     int rp;        // raw index of the next byte to load
     bool ff;       // the last byte loaded was FF: a 00 that follows is stuffing
+    int mk;        // RST: raw index of the FF of the marker the loads stopped at, kNoMark: none in sight
+    bool over;     // RST: bits past the last data byte in front of that marker were consumed
 };
+constexpr int kNoMark = 0x7fffffff;
 
 LLFE_HD void rd_init(Reader &r, const uint8_t *d, int len, uint32_t pos) {
     r.d = d;
@@ -71,13 +88,29 @@ LLFE_HD void rd_init(Reader &r, const uint8_t *d, int len, uint32_t pos) {
     r.rb = (int)(pos >> 3);
     r.rp = r.rb;
     r.ff = false;
+    r.mk = kNoMark;
+    r.over = false;
 }
 
-// top up to eight data bytes (at most sixteen raw bytes: one stuffed 00 per FF)
+// top up to eight data bytes (at most sixteen raw bytes: one stuffed 00 per FF).  RST: up to
+// the next marker, zeros from there
+template <bool RST>
 LLFE_HD void rd_fill(Reader &r) {
     for (int guard = 0; guard < 16 && r.nbytes < 8; guard++) {
         unsigned b = 0;
-        if (r.rp >= 0 && r.rp < r.len) {
+        if (RST) {
+            if (r.rp >= 0 && r.rp < r.len && r.rp < r.mk) {
+                b = r.d[r.rp];
+                if (b != 0xff) {
+                    r.rp++;
+                } else if (r.rp + 1 < r.len && r.d[r.rp + 1] != 0) {
+                    r.mk = r.rp;
+                    b = 0;
+                } else {
+                    r.rp += 2;
+                }
+            }
+        } else if (r.rp >= 0 && r.rp < r.len) {
             b = r.d[r.rp++];
             if (r.ff && b == 0) {
                 r.ff = false;
@@ -93,21 +126,36 @@ LLFE_HD void rd_fill(Reader &r) {
 // the k bits (1..32) that start `skip` bits after the current position; skip + k <= 57
 LLFE_HD uint32_t rd_peek(const Reader &r, int skip, int k) { return (uint32_t)((r.acc << (r.bo + skip)) >> (64 - k)); }
 
+// RST: the raw index stops at the marker in sight (the bytes from there are the reader's zeros,
+// not the file's)
+template <bool RST>
 LLFE_HD void rd_skip(Reader &r, int n) {
     r.bo += n;
-    while (r.bo >= 8 && r.nbytes > 0) {
+    while (r.bo >= 8 && r.nbytes > 0 && (!RST || r.rb < r.mk)) {
         r.rb += 1 + ((r.acc >> 56) == 0xff ? 1 : 0);
         r.acc <<= 8;
         r.nbytes--;
         r.bo -= 8;
     }
+    if (RST && r.rb >= r.mk && r.bo > 0) {
+        r.over = true;
+        r.bo = 0;
+    }
 }
 
 // the first position of subsequence i: its boundary byte, or the next one when the boundary
-// falls on the 00 of a stuffed pair
+// falls on the 00 of a stuffed pair.  RST: a boundary on either byte of a marker starts behind
+// the marker (where the lane in front of it ends up as well, having crossed it), and the guessed
+// state (0, 0) is then the true one
+template <bool RST>
 LLFE_HD uint32_t sub_start(const uint8_t *d, int len, int i) {
     int b = i * kSub;
-    if (b > 0 && b < len && d[b] == 0 && d[b - 1] == 0xff) b++;
+    if (RST) {
+        if (b > 0 && b < len && d[b - 1] == 0xff) b++;
+        else if (b + 1 < len && d[b] == 0xff && d[b + 1] != 0) b += 2;
+    } else if (b > 0 && b < len && d[b] == 0 && d[b - 1] == 0xff) {
+        b++;
+    }
     if (b > len) b = len;
     return (uint32_t)b * 8u;
 }
@@ -130,16 +178,29 @@ LLFE_HD int16_t *locate(const Geometry &g, int blk, int *comp) {
     return (int16_t *)(g.slot + g.d->comp[c].coef_offset + ((int64_t)row * g.d->comp[c].blocks_w + col) * 128);
 }
 
+// RST: what one decode_sub saw of restart markers, for the verification.  `bad`: a marker was
+// crossed other than at an MCU boundary behind 0..7 one-bits, is not FF D0..D7, or two markers
+// crossed by this one decode are not restart_interval MCUs apart with consecutive indices.
+struct Marks {
+    int32_t n;      // markers crossed
+    int32_t first;  // blocks completed in front of the first of them
+    int32_t idx;    // its index (Dn - D0)
+    int32_t bad;
+};
+
 // Decode from `in` until the position reaches byte `end` (<= len) or, with WRITE, block
 // `total` is reached.  *blocks counts the blocks completed.  With WRITE the coefficients go
 // to the slot in natural order (`nat`: zigzag index -> natural index) and every block's DC
 // difference, padding blocks included, to dcd[block]; `first` is the index of the block the
 // entry state is in.  Trailing 1-padding inside the scan's last byte ends the scan: the exit
 // position is then len * 8.  An anomaly (no such code, a coefficient index past 63, a DC
-// category above 11, an AC category above 10) returns pos = kNone.
-template <bool WRITE>
+// category above 11, an AC category above 10) returns pos = kNone.  RST: markers are crossed
+// as described at the top, *marks (may be null) says what was seen; a crossing advances two raw
+// bytes and takes one iteration, so the iteration bound holds.
+template <bool WRITE, bool RST>
 LLFE_HD State decode_sub(const uint8_t *scan, int len, const Tab *tabs, const llfe_jpeg_scan &sc, State in, int end,
-                         int *blocks, const uint8_t *nat, const Geometry &g, int16_t *dcd, int first, int total) {
+                         int *blocks, const uint8_t *nat, const Geometry &g, int16_t *dcd, int first, int total,
+                         Marks *marks) {
     Reader r;
     rd_init(r, scan, len, in.pos);
     int b = (int)(in.bz >> 8) & 7, z = (int)(in.bz & 63);
@@ -148,9 +209,34 @@ LLFE_HD State decode_sub(const uint8_t *scan, int len, const Tab *tabs, const ll
     int done = 0, blk = first, comp = 0;
     int16_t *dst = nullptr;
     if (WRITE && blk < total) dst = locate(g, blk, &comp);
+    Marks m{0, 0, 0, 0};
+    int m_done = 0, m_idx = 0;  // of the last marker crossed
+    if (RST && marks) *marks = m;
     const int cap = (end - r.rb) * 8 + 16;  // a symbol is at least one bit
-    for (int it = 0; it < cap && r.rb < end && (!WRITE || blk < total); it++) {
-        rd_fill(r);
+    for (int it = 0; it < cap && (RST || (r.rb < end && (!WRITE || blk < total))); it++) {
+        rd_fill<RST>(r);
+        if (RST) {
+            if (r.mk != kNoMark) {  // a marker is in sight: does the position stand in front of it?
+                const unsigned top = (unsigned)(r.acc >> 56), rest = 0xffu >> r.bo;
+                if (r.rb == r.mk || (r.bo > 0 && r.rb + 1 + (top == 0xff ? 1 : 0) == r.mk && (top & rest) == rest)) {
+                    const int idx = (int)scan[r.mk + 1] - 0xd0;  // (mk + 1 < len: rd_fill looked at it)
+                    if (b != 0 || z != 0 || r.over || idx < 0 || idx > 7) m.bad = 1;
+                    if (m.n == 0) {
+                        m.first = done;
+                        m.idx = idx & 7;
+                    } else if (done - m_done != sc.restart_interval * bim || (idx & 7) != ((m_idx + 1) & 7)) {
+                        m.bad = 1;
+                    }
+                    m_done = done;
+                    m_idx = idx & 7;
+                    m.n++;
+                    rd_init(r, scan, len, (uint32_t)(r.mk + 2) * 8u);
+                    b = z = 0;
+                    continue;
+                }
+            }
+            if (!(r.rb < end && (!WRITE || blk < total))) break;
+        }
         if (r.bo > 0 && r.rb >= len - 2) {  // only 1-padding left in the last data byte?
             const unsigned top = (unsigned)(r.acc >> 56), rest = 0xffu >> r.bo;
             if (r.rb + 1 + (top == 0xff ? 1 : 0) == len && (top & rest) == rest) {
@@ -171,7 +257,7 @@ LLFE_HD State decode_sub(const uint8_t *scan, int len, const Tab *tabs, const ll
             const int bits = (int)rd_peek(r, l, s);
             v = bits < (1 << (s - 1)) ? bits - (1 << s) + 1 : bits;
         }
-        rd_skip(r, l + s);
+        rd_skip<RST>(r, l + s);
         if (z == 0) {
             if (sym > 11) return State{kNone, 0};
             if (WRITE) dcd[blk] = (int16_t)v;
@@ -199,6 +285,7 @@ LLFE_HD State decode_sub(const uint8_t *scan, int len, const Tab *tabs, const ll
         }
     }
     *blocks = done;
+    if (RST && marks) *marks = m;
     return State{(uint32_t)r.rb * 8u + (uint32_t)r.bo, (uint32_t)b << 8 | (uint32_t)z};
 }
 
@@ -211,8 +298,8 @@ LLFE_HD State decode_sub(const uint8_t *scan, int len, const Tab *tabs, const ll
 LLFE_HD int subsequences(int scan_bytes) { return (scan_bytes + kSub - 1) / kSub; }
 
 // The host check in front of the kernels and of their twin: every extent a record names lies
-// inside the staging buffer, every selector inside its table, the MCU grid covers the block
-// grids of the (already validated) descriptors.  On success the largest subsequence count and
+// inside the staging buffer, every selector inside its table, the restart interval one a DRI
+// can hold, the MCU grid covers the block grids of the (already validated) descriptors.  On success the largest subsequence count and
 // block count (padding blocks included) of an image.
 inline bool validate_scans(const llfe_jpeg_scan *scans, const llfe_jpeg_desc *descs, int n, int64_t staging_bytes,
                            int *max_sub, int *max_blocks) {
@@ -230,6 +317,7 @@ inline bool validate_scans(const llfe_jpeg_scan *scans, const llfe_jpeg_desc *de
             !inside(s.scan_offset, (((int64_t)s.scan_bytes + 15) & ~(int64_t)15) + 16))
             return false;
         if (s.blocks_in_mcu < 1 || s.blocks_in_mcu > 6 || s.mcus_w < 1 || s.mcus_h < 1) return false;
+        if (s.restart_interval < 0 || s.restart_interval > 65535) return false;
         const int64_t blocks = (int64_t)s.mcus_w * s.mcus_h * s.blocks_in_mcu;
         if (blocks >= (1 << 30)) return false;
         for (int c = 0; c < d.n_comp; c++) {

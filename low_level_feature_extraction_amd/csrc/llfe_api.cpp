@@ -1943,11 +1943,14 @@ int llfe_jpeg_entropy_decode(llfe_ctx *ctx, const uint8_t *staging, int64_t stag
         return ctx->fail(LLFE_ERR_INVALID, "llfe_jpeg_entropy_decode: a descriptor points outside its slot or does not "
                                            "cover %dx%d", w, h);
     if (!llfe_huff::validate_scans(scans, descs, n, staging_bytes, &max_sub, &max_blocks))
-        return ctx->fail(LLFE_ERR_INVALID, "llfe_jpeg_entropy_decode: a scan record points outside the staging buffer or "
-                                           "its MCU geometry does not cover the block grids");
+        return ctx->fail(LLFE_ERR_INVALID, "llfe_jpeg_entropy_decode: a scan record points outside the staging buffer, "
+                                           "its MCU geometry does not cover the block grids or its restart interval is "
+                                           "not 0..65535");
     int64_t max_coef_bytes = 0;
+    int kinds = 0;  // bit 0: images without a restart interval, bit 1: with one
     for (int i = 0; i < n; i++) {
         status_out[i] = scans[i].blocks_in_mcu ? LLFE_OK : LLFE_ERR_UNSUPPORTED;
+        if (scans[i].blocks_in_mcu) kinds |= scans[i].restart_interval ? 2 : 1;
         for (int c = 0; c < descs[i].n_comp; c++)
             max_coef_bytes = std::max<int64_t>(max_coef_bytes, (int64_t)descs[i].comp[c].blocks_w * descs[i].comp[c].blocks_h * 128);
     }
@@ -1974,7 +1977,7 @@ int llfe_jpeg_entropy_decode(llfe_ctx *ctx, const uint8_t *staging, int64_t stag
     ctx->prof.cur_slot = Profiler::kStageSlot;
     const int passes = jpeg_huff_passes(max_sub);  // the cross-workgroup passes, fixed here from the scan lengths
     auto launch = [&](int stage, int pass) {
-        return launch_jpeg_huff(stage, pass, staging, ctx->d_jpeg_scan.p, ctx->d_jpeg_desc.p, n, max_sub, max_blocks,
+        return launch_jpeg_huff(stage, pass, kinds, staging, ctx->d_jpeg_scan.p, ctx->d_jpeg_desc.p, n, max_sub, max_blocks,
                                 max_coef_bytes, slots, slot_stride, ctx->d_jpeg_huff_ws.p, ctx->d_jpeg_status.p, s);
     };
     const int rc = [&]() -> int {

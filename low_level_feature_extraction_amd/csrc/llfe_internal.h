@@ -394,10 +394,11 @@ hipError_t launch_jpeg_reconstruct(const uint8_t *coefs, int64_t slot_stride, co
 // 0 = zero the coefficient areas (max_coef_bytes: the largest component of an image) and copy the
 // quantisation tables, 1 = a synchronisation pass (pass = 0 .. jpeg_huff_passes - 1),
 // 2 = verification and block scan (sets d_status of an image that fails), 3 = the write pass,
-// 4 = the DC sums.
+// 4 = the DC sums.  kinds: bit 0 = the batch has images without a restart interval, bit 1 = with
+// one; the stages behind 0 are launched once per kind present.
 size_t jpeg_huff_workspace_bytes(int n, int max_sub, int max_blocks);
 int jpeg_huff_passes(int max_sub);
-hipError_t launch_jpeg_huff(int stage, int pass, const uint8_t *staging, const llfe_jpeg_scan *d_scans,
+hipError_t launch_jpeg_huff(int stage, int pass, int kinds, const uint8_t *staging, const llfe_jpeg_scan *d_scans,
                             const llfe_jpeg_desc *d_descs, int n, int max_sub, int max_blocks, int64_t max_coef_bytes,
                             uint8_t *slots, int64_t slot_stride, uint8_t *workspace, int *d_status, hipStream_t s);
 

@@ -436,8 +436,9 @@ def reconstruct_staged(st: StagedCoefs, device=0, workers=None, out=None):
 # The entropy half on the device too (DESIGN.md §3 "JPEG entropy decode on the device"): the host
 # only parses the headers (llfe_jpeg_parse_batch), the file's scan bytes cross PCIe instead of
 # its coefficients, and llfe_jpeg_entropy_decode (csrc/jpeg_huff.hip) writes the coefficient
-# slots stage_coefs writes.  For baseline single-scan files without restart markers; every
-# other image, and every image whose scan shows an anomaly, takes the paths above.
+# slots stage_coefs writes.  For baseline single-scan files without restart markers, or
+# (restarts=True) with them; every other image, and every image whose scan shows an anomaly,
+# takes the paths above.
 class StagedBytes:
     """One batch after llfe_jpeg_parse_batch: ``records`` (n x record_stride uint8, pinned when
     a GPU is present), ``descs`` / ``scans`` (the llfe_jpeg_desc / llfe_jpeg_scan arrays),
@@ -486,13 +487,16 @@ def _bytes_staging(n, stride):
         return buf
 
 
-def stage_bytes(blobs, workers=None, slot_bytes=None) -> StagedBytes:
+def stage_bytes(blobs, workers=None, slot_bytes=None, restarts=False) -> StagedBytes:
     """The host half of decode_batch_device(entropy="device"): parse the headers of every
     eligible JPEG of a batch of equally sized images (llfe_jpeg_parse_batch: baseline Huffman,
     one interleaved scan, no restart markers, and what stage_coefs asks) and stage quantisation
     tables, decode tables and the scan's bytes in the next buffer of a ring of three.  Host
     only; no entropy decoding happens here.  The record stride is a power-of-two bucket of the
-    longest blob, so batches of like files reuse their pinned buffers."""
+    longest blob, so batches of like files reuse their pinned buffers.  ``restarts=True``
+    (llfe_jpeg_parse_batch_flags, LLFE_JPEG_PARSE_RESTARTS) also takes files with a restart
+    interval: their scans are staged with the markers in them and the records carry the
+    interval, which is all the device half needs to know."""
     import ctypes as C
 
     from . import _lib
@@ -517,8 +521,9 @@ def stage_bytes(blobs, workers=None, slot_bytes=None) -> StagedBytes:
     ptrs = (C.c_void_p * n)(*[C.cast(k, C.c_void_p) for k in keep])
     sizes = (C.c_uint64 * n)(*[len(b) for b in blobs])
     status = (C.c_int32 * n)()
-    _lib.lib().llfe_jpeg_parse_batch(ptrs, sizes, n, h, w, records.ctypes.data, stride, slot_bytes, descs, scans, status,
-                                     int(workers or default_decode_threads()))
+    _lib.lib().llfe_jpeg_parse_batch_flags(ptrs, sizes, n, h, w, records.ctypes.data, stride, slot_bytes, descs, scans,
+                                           status, int(workers or default_decode_threads()),
+                                           _lib.JPEG_PARSE_RESTARTS if restarts else 0)
     del keep
     return StagedBytes(blobs, h, w, records, descs, scans, list(status), slot_bytes, tensor)
 
@@ -602,7 +607,7 @@ def decode_staged_bytes(sb: StagedBytes, device=0, workers=None, out=None):
     return out
 
 
-def decode_batch_device(blobs, device=0, workers=None, out=None, entropy="host"):
+def decode_batch_device(blobs, device=0, workers=None, out=None, entropy="host", restarts=False):
     """decode_batch with the reconstruction on the GPU: equally sized images -> one
     (N, H, W, 3) BGR uint8 tensor on ``device``, the same bytes decode_batch returns.  Eligible
     JPEGs (8-bit greyscale or YCbCr 4:4:4 / 4:2:2 / 4:2:0, EXIF orientation 1, no decoder
@@ -614,9 +619,10 @@ def decode_batch_device(blobs, device=0, workers=None, out=None, entropy="host")
     ``entropy="device"`` moves the entropy decode of baseline single-scan JPEGs without restart
     markers to the device as well (csrc/jpeg_huff.hip): the file bytes cross PCIe, not the
     coefficients.  Images it does not take, and images whose scan the kernels find anomalous,
-    go through the ``entropy="host"`` path; the result is the same bytes in every case."""
+    go through the ``entropy="host"`` path; the result is the same bytes in every case.
+    ``restarts=True`` lets it take files with restart intervals too (stage_bytes)."""
     if entropy == "host":
         return reconstruct_staged(stage_coefs(blobs, workers), device, workers, out)
     if entropy != "device":
         raise ValueError('entropy must be "host" or "device"')
-    return decode_staged_bytes(stage_bytes(blobs, workers), device, workers, out)
+    return decode_staged_bytes(stage_bytes(blobs, workers, restarts=restarts), device, workers, out)

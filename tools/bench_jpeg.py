@@ -22,6 +22,9 @@ JPEG leg are not touched: this tool measures the opt-in path beside them.
            coefficients and of one batch of records.  The bar B had to clear over A is applied
            to C over B: every C leg above every B leg, medians further apart than three times
            B's min-max range.
+           --restart-rows N encodes the feed with a restart marker every N MCU rows; leg C then
+           stages with restarts=True (without it such files are refused by stage_bytes and C
+           runs at B's speed plus a header parse).  Figures: profiles/jpeg_restart/.
 One JSON line per mode on stdout.
 """
 from __future__ import annotations
@@ -41,7 +44,7 @@ import numpy as np  # noqa: E402
 
 
 def _encode(args):
-    i, h, w, seed = args
+    i, h, w, seed, restart_rows = args
     import io
 
     from PIL import Image
@@ -49,15 +52,16 @@ def _encode(args):
     from low_level_feature_extraction_amd import synth
 
     b = io.BytesIO()
-    Image.fromarray(synth.synth_numpy(i, h, w, seed=seed)[:, :, ::-1]).save(b, "JPEG", quality=85)
+    Image.fromarray(synth.synth_numpy(i, h, w, seed=seed)[:, :, ::-1]).save(
+        b, "JPEG", quality=85, **({"restart_marker_rows": restart_rows} if restart_rows else {}))
     return b.getvalue()
 
 
-def _blobs(n, h, w, seed, distinct=8):
+def _blobs(n, h, w, seed, distinct=8, restart_rows=0):
     from concurrent.futures import ThreadPoolExecutor
 
     with ThreadPoolExecutor(max_workers=distinct) as ex:
-        d = list(ex.map(_encode, [(i, h, w, seed) for i in range(distinct)]))
+        d = list(ex.map(_encode, [(i, h, w, seed, restart_rows) for i in range(distinct)]))
     return [d[i % distinct] for i in range(n)]
 
 
@@ -110,7 +114,8 @@ def gpu(args):
     feats = tuple(args.features.split(","))
     be = Backend.get(0)
     threads = decode.default_decode_threads()
-    blobs = _blobs(B, h, w, args.seed)
+    blobs = _blobs(B, h, w, args.seed, restart_rows=args.restart_rows)
+    restarts = args.restart_rows > 0
     pinned = [torch.empty((B, h, w, 3), dtype=torch.uint8).pin_memory() for _ in range(3)]
     bufs = [p.numpy() for p in pinned]
     outs = [torch.empty((B, h, w, 3), dtype=torch.uint8, device="cuda:0") for _ in range(3)]
@@ -128,7 +133,7 @@ def gpu(args):
             if kind == "A":
                 return decode.decode_batch(blobs, bufs[k % 3], threads)
             if kind == "C":
-                return decode.stage_bytes(blobs, threads, slot_bytes=slot_bytes)
+                return decode.stage_bytes(blobs, threads, slot_bytes=slot_bytes, restarts=restarts)
             return decode.stage_coefs(blobs, threads, slot_bytes=slot_bytes)
 
         with ThreadPoolExecutor(max_workers=1) as prod:
@@ -153,7 +158,7 @@ def gpu(args):
             return B * steps / (time.perf_counter() - t0)
 
     with torch.cuda.stream(side):
-        dev = decode.decode_batch_device(blobs[:4], workers=threads, entropy="device")
+        dev = decode.decode_batch_device(blobs[:4], workers=threads, entropy="device", restarts=restarts)
     assert np.array_equal(dev.cpu().numpy(), decode.decode_batch(blobs[:4], workers=threads))
     leg("A"), leg("B"), leg("C")  # warm all three: pinned rings, workspaces, thread pools
     va, vb, vc = [], [], []
@@ -169,7 +174,7 @@ def gpu(args):
     st = decode.stage_coefs(blobs, threads, slot_bytes=slot_bytes)
     prod_b = time.perf_counter() - t
     t = time.perf_counter()
-    sb = decode.stage_bytes(blobs, threads, slot_bytes=slot_bytes)
+    sb = decode.stage_bytes(blobs, threads, slot_bytes=slot_bytes, restarts=restarts)
     prod_c = time.perf_counter() - t
     assert sb.status == [0] * B
     # H2D of one batch of coefficients, and the kernels alone
@@ -215,6 +220,7 @@ def gpu(args):
     bar_c = min(vc) > max(vb) and (c["median"] - b["median"]) > 3 * (b["max"] - b["min"])
     print(json.dumps({
         "mode": "gpu", "unit": "images/s", "batch": B, "image": f"{w}x{h} quality-85 4:2:0 synth", "steps_per_leg": steps,
+        "restart_rows": args.restart_rows, "restart_interval_mcus": sb.scans[0].restart_interval,
         "decode_threads": threads, "features": list(feats), "A_decode_batch": a, "B_coefficients": b,
         "C_device_entropy": c,
         "A_legs": [round(v, 1) for v in va], "B_legs": [round(v, 1) for v in vb], "C_legs": [round(v, 1) for v in vc],
@@ -241,6 +247,8 @@ def main():
     ap.add_argument("--legs", type=int, default=4, help="legs of each producer, alternating (--gpu)")
     ap.add_argument("--runs", type=int, default=5, help="alternating runs (--host)")
     ap.add_argument("--host-images", type=int, default=16, help="images per thread and run (--host)")
+    ap.add_argument("--restart-rows", type=int, default=0,
+                    help="encode the feed with a restart marker every N MCU rows; leg C stages with restarts=True (--gpu)")
     ap.add_argument("--features", default="colors,shapes,shadows")
     ap.add_argument("--seed", type=int, default=2025)
     args = ap.parse_args()

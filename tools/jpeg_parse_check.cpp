@@ -6,7 +6,8 @@
 // decodes it, by subsequences and in one piece, into an exactly sized heap slot -- so a write
 // past the record or the slot, or a read of the bit reader past the staged scan, is a sanitizer
 // report -- and compares the slot with the one llfe_jpeg_read_coefs_batch extracts.
-// Prints one line per file; exit status 0 when every call returned a documented status and
+// With --restarts in front of the files, parses with LLFE_JPEG_PARSE_RESTARTS
+// (tests/test_jpeg_restart_sanitized.py).  Prints one line per file; exit status 0 when every call returned a documented status and
 // every decoded slot equals the extracted one.
 #include <algorithm>
 #include <cstdio>
@@ -50,7 +51,9 @@ static bool same_extents(const llfe_jpeg_desc &d, const uint8_t *a, const uint8_
 
 int main(int argc, char **argv) {
     int bad = 0;
-    for (int a = 1; a < argc; a++) {
+    const bool restarts = argc > 1 && !strcmp(argv[1], "--restarts");
+    const uint32_t flags = restarts ? LLFE_JPEG_PARSE_RESTARTS : 0u;
+    for (int a = restarts ? 2 : 1; a < argc; a++) {
         const std::vector<uint8_t> f = slurp(argv[a]);
         int32_t w = 0, h = 0;
         int nc = 0;
@@ -64,7 +67,7 @@ int main(int argc, char **argv) {
         int32_t st = 1;
         const uint8_t *p = f.data();
         const uint64_t sz = f.size();
-        const int rc = llfe_jpeg_parse_batch(&p, &sz, 1, h, w, rec.p, stride, slot_bytes, &d, &s, &st, 1);
+        const int rc = llfe_jpeg_parse_batch_flags(&p, &sz, 1, h, w, rec.p, stride, slot_bytes, &d, &s, &st, 1, flags);
         if (rc != st || !documented(st) || (st != LLFE_OK && (d.n_comp != 0 || s.blocks_in_mcu != 0))) bad++;
         int st_sub = LLFE_ERR_UNSUPPORTED, st_one = LLFE_ERR_UNSUPPORTED, st_host = 1, equal = -1;
         if (st == LLFE_OK) {
@@ -84,7 +87,7 @@ int main(int argc, char **argv) {
             llfe_jpeg_desc d2;
             llfe_jpeg_scan s2;
             int32_t st2 = 1;
-            llfe_jpeg_parse_batch(&p, &sz, 1, h, w, tight.p, stride - 32, slot_bytes, &d2, &s2, &st2, 1);
+            llfe_jpeg_parse_batch_flags(&p, &sz, 1, h, w, tight.p, stride - 32, slot_bytes, &d2, &s2, &st2, 1, flags);
             if (!documented(st2)) bad++;
         }
         printf("%s: %dx%d parse %d scan %d bytes decode %d / %d host %d equal %d\n", argv[a], w, h, st,
