@@ -599,6 +599,65 @@ int llfe_jpeg_entropy_decode(llfe_ctx *ctx, const uint8_t *staging, int64_t stag
                              const llfe_jpeg_desc *descs, int32_t n, int32_t h, int32_t w, uint8_t *slots,
                              int64_t slot_stride, int32_t *status_out, llfe_stream stream);
 
+/* ---- PNG decode on the device (opt-in; llfe_decode_batch is unchanged): 8-bit RGB / RGBA,
+ * not interlaced.  The host only walks the chunks; the file's deflate stream crosses to the
+ * device instead of its pixels, and csrc/png_inflate.hip inflates, checks the Adler-32, undoes
+ * the row filters and writes the BGR batch, bit for bit what llfe_decode_batch writes.
+ *
+ * A batch is staged as one record per image in a buffer of one record stride: the IDAT
+ * payloads concatenated (zero-length and 1-byte chunks included) without the two zlib header
+ * bytes and the four Adler-32 bytes, zero padded to a multiple of 16, then 16 zero bytes, then
+ * the stored Adler-32 (u32) and 12 zero bytes.  llfe_png_desc (a host array) says where. */
+typedef struct {
+    int64_t record_offset; /* of the image's record in the staging buffer, 16-byte aligned */
+    int64_t raw_bytes;     /* height * (row_bytes + 1): what the stream must inflate to */
+    int32_t deflate_bytes; /* bytes of the deflate stream; 0: nothing staged */
+    int32_t bpp;           /* bytes per pixel: 3 (RGB) or 4 (RGBA) */
+    int32_t row_bytes;     /* width * bpp */
+    uint32_t adler;        /* the Adler-32 the file stores */
+} llfe_png_desc; /* 32 bytes */
+/* host only, no ctx: the host half.  Walks the chunks of n blobs of one size on `threads` host
+ * threads (critical-chunk CRCs checked, LLFE_MAX_PIXELS applied, as llfe_decode_batch does) and
+ * stages the eligible ones into staging (host, n x record_stride bytes; record_stride a multiple
+ * of 16, the longest blob rounded up to 16 plus 32 holds any) and descs[n].  Eligible: colour
+ * type 2 or 6 at 8 bits, not interlaced, of the batch's size, a zlib header with CM = 8,
+ * CINFO <= 7, no FDICT and a valid FCHECK, raw_bytes below 2^31 and plausible for the IDAT
+ * bytes, the record fitting record_stride.  Everything else (grey, palette, 16-bit, sub-byte,
+ * interlaced, JPEG, other formats, another size) keeps a zeroed descriptor and is
+ * LLFE_ERR_UNSUPPORTED; a corrupt container is LLFE_ERR_INVALID as in llfe_decode_batch.
+ * Decode those with llfe_decode_batch.  status[i] per image; returns the first non-OK status. */
+int llfe_png_parse_batch(const uint8_t *const *data, const uint64_t *sizes, int32_t n, int32_t height, int32_t width,
+                         uint8_t *staging, int64_t record_stride, llfe_png_desc *descs, int32_t *status,
+                         int32_t threads);
+/* host only: the plain C++ twin of llfe_png_decode_device over host memory, built from the same
+ * decoding core (csrc/png_inflate_core.h), for tests and for debugging the kernels.  raw (n x
+ * raw_stride) receives the inflated filtered rows, out_bgr (n x h x w x 3) the pixels.  The same
+ * validation; status[i]: LLFE_OK, or LLFE_ERR_UNSUPPORTED for an image that was not staged or
+ * whose stream shows an anomaly (below). */
+int llfe_png_decode_reference(const uint8_t *staging, int64_t staging_bytes, const llfe_png_desc *descs, int32_t n,
+                              int32_t h, int32_t w, uint8_t *raw, int64_t raw_stride, uint8_t *out_bgr,
+                              int32_t *status);
+/* the device half: staging (device, staging_bytes, 16-byte aligned, as parsed above) -> raw
+ * (device, n x raw_stride, 16-byte aligned, raw_stride a multiple of 16 and at least raw_bytes:
+ * the inflated filtered rows) and out_bgr (device, n x h x w x 3).  descs is a host array and is
+ * validated on the host before anything is launched: every record inside staging_bytes, the
+ * geometry h x w at 3 or 4 bytes per pixel; a bad one is LLFE_ERR_INVALID with nothing written
+ * (so is n above 65535).
+ * Images with deflate_bytes == 0 are skipped and left as they are in out_bgr.  status (host, n):
+ * LLFE_OK for an image whose pixels are in out_bgr, LLFE_ERR_UNSUPPORTED for one that was
+ * skipped or whose stream showed an anomaly: reserved block type 3, a stored block whose NLEN
+ * is not ~LEN, a set of code lengths that is over-subscribed or incomplete (other than a
+ * single code of length 1, or no distance code), a dynamic header zlib refuses, no such code,
+ * length symbols 286 / 287 or distance codes 30 / 31, a distance beyond the bytes produced so
+ * far, output that would pass raw_bytes, input exhausted before the final block's end, the
+ * final block ending before raw_bytes, a filter byte above 4, an Adler-32 mismatch.  Its raw
+ * and pixels may hold anything and the caller decodes it with llfe_decode_batch.  The kernels
+ * read nothing outside the validated records and every loop is bounded by the record.  Runs
+ * on `stream` and returns when it has finished. */
+int llfe_png_decode_device(llfe_ctx *ctx, const uint8_t *staging_dev, int64_t staging_bytes,
+                           const llfe_png_desc *descs, int32_t n, int32_t h, int32_t w, uint8_t *raw_dev,
+                           int64_t raw_stride, uint8_t *out_bgr_dev, int32_t *status, llfe_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

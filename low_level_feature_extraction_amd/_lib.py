@@ -172,6 +172,17 @@ class LlfeJpegScan(C.Structure):
     ]
 
 
+class LlfePngDesc(C.Structure):
+    _fields_ = [
+        ("record_offset", C.c_int64),
+        ("raw_bytes", C.c_int64),
+        ("deflate_bytes", C.c_int32),
+        ("bpp", C.c_int32),
+        ("row_bytes", C.c_int32),
+        ("adler", C.c_uint32),
+    ]
+
+
 JPEG_GRAY, JPEG_444, JPEG_422, JPEG_420 = 1, 2, 3, 4  # LLFE_JPEG_*
 JPEG_HUFF_TABLE_BYTES, JPEG_RECORD_HEADER = 400, 2048  # LLFE_JPEG_HUFF_TABLE_BYTES, LLFE_JPEG_RECORD_HEADER
 JPEG_SUBSEQUENCE_BYTES = 128  # csrc/jpeg_huff_core.h kSub
@@ -253,6 +264,10 @@ SIGNATURES = {
                                               _i32, _vp, _i64, _vp, _i32]),
     "llfe_jpeg_entropy_decode": (C.c_int, [_vp, _vp, _i64, C.POINTER(LlfeJpegScan), C.POINTER(LlfeJpegDesc), _i32, _i32,
                                            _i32, _vp, _i64, _vp, _vp]),
+    "llfe_png_parse_batch": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _i64, C.POINTER(LlfePngDesc), _vp, _i32]),
+    "llfe_png_decode_reference": (C.c_int, [_vp, _i64, C.POINTER(LlfePngDesc), _i32, _i32, _i32, _vp, _i64, _vp, _vp]),
+    "llfe_png_decode_device": (C.c_int, [_vp, _vp, _i64, C.POINTER(LlfePngDesc), _i32, _i32, _i32, _vp, _i64, _vp, _vp,
+                                         _vp]),
 }
 
 _lib = None

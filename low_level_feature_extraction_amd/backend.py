@@ -575,6 +575,37 @@ class Backend:
                    slots.data_ptr(), stride, status, self._stream(slots))
         return list(status)
 
+    def png_decode(self, records, descs, h: int, w: int, out, raw=None) -> list:
+        """PNG decode on the device (llfe_png_decode_device): ``records`` an n x record_stride
+        uint8 device tensor of staged deflate streams, ``descs`` the n llfe_png_desc records
+        (decode.stage_png), ``out`` the n x h x w x 3 BGR uint8 device tensor, on the current
+        stream.  ``raw`` (n x raw_stride uint8 on the device, raw_stride a multiple of 16 that
+        holds h * (w * 4 + 1) bytes; allocated here when None) receives the inflated filtered
+        rows.  -> the per-image status list: 0 for an image whose pixels are in ``out``,
+        LLFE_ERR_UNSUPPORTED for one that was not staged or whose stream showed an anomaly (its
+        place in ``out`` is undefined: decode it another way).  A descriptor that points outside
+        its record raises LlfeError (LLFE_ERR_INVALID) before any launch."""
+        torch = _torch()
+        if not (_is_torch(records) and records.is_cuda and records.dtype == torch.uint8 and records.dim() == 2 and
+                records.is_contiguous()):
+            raise ValueError("png_decode: records must be a contiguous n x record_stride uint8 device tensor")
+        n = records.shape[0]
+        if len(descs) != n:
+            raise ValueError(f"png_decode: {len(descs)} descriptors for {n} records")
+        if not (_is_torch(out) and tuple(out.shape) == (n, h, w, 3) and out.dtype == torch.uint8 and out.is_contiguous()
+                and out.device == records.device):
+            raise ValueError(f"png_decode: out must be a contiguous {(n, h, w, 3)} uint8 tensor on {records.device}")
+        if raw is None:
+            need = max([d.raw_bytes for d in descs], default=0)
+            raw = torch.empty((n, max(16, (need + 15) & ~15)), dtype=torch.uint8, device=records.device)
+        if not (_is_torch(raw) and raw.dim() == 2 and raw.shape[0] == n and raw.dtype == torch.uint8 and
+                raw.is_contiguous() and raw.device == records.device):
+            raise ValueError(f"png_decode: raw must be a contiguous {n} x raw_stride uint8 tensor on {records.device}")
+        status = (C.c_int32 * n)()
+        self._call("llfe_png_decode_device", records.data_ptr(), records.numel(), descs, n, int(h), int(w),
+                   raw.data_ptr(), raw.shape[1], out.data_ptr(), status, self._stream(records))
+        return list(status)
+
     def font_detect(self, images, binary=None, regions=False) -> list:
         """FontDetector.detect_font's pixel work on the GPU (llfe_font_detect): per image
         the external contours of the font binary (or of ``binary``, n x h x w, nonzero =

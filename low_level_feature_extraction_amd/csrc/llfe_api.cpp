@@ -32,6 +32,7 @@
 #include "contours.h"
 #include "jpeg_huff_core.h"
 #include "llfe_internal.h"
+#include "png_inflate_core.h"
 
 using namespace llfe;
 
@@ -484,6 +485,9 @@ struct llfe_ctx {
     HostBuf<int32_t> h_jpeg_status;
     DevBuf<int32_t> d_jpeg_status;
     DevBuf<uint8_t> d_jpeg_huff_ws;
+    // llfe_png_decode_device: the validated descriptors (the status buffers above are shared)
+    HostBuf<llfe_png_desc> h_png_desc;
+    DevBuf<llfe_png_desc> d_png_desc;
     Work *km_last = nullptr;  // workspace of the last k-means launch (llfe_kmeans_attempts)
     // LLFE_FEATURE_FONTS: per slot the records and counters of the chunk's font pass, whether
     // that pass ran its contours on the GPU (else finish_chunk takes the host path) and the
@@ -1993,6 +1997,62 @@ int llfe_jpeg_entropy_decode(llfe_ctx *ctx, const uint8_t *staging, int64_t stag
     HIPCHK(ctx, hipMemcpyAsync(ctx->h_jpeg_status.p, ctx->d_jpeg_status.p, sizeof(int32_t) * (size_t)n,
                                hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipStreamSynchronize(s));  // (the pinned records and the workspace are free again)
+    ctx->prof.collect(Profiler::kStageSlot);
+    std::memcpy(status_out, ctx->h_jpeg_status.p, sizeof(int32_t) * (size_t)n);
+    return LLFE_OK;
+}
+
+int llfe_png_decode_device(llfe_ctx *ctx, const uint8_t *staging, int64_t staging_bytes, const llfe_png_desc *descs,
+                           int32_t n, int32_t h, int32_t w, uint8_t *raw, int64_t raw_stride, uint8_t *out_bgr,
+                           int32_t *status_out, llfe_stream stream) {
+    if (!ctx) return LLFE_ERR_INVALID;
+    if (!valid_dims(n, h, w) || n > 65535 || (n && (!staging || !descs || !raw || !out_bgr || !status_out)) ||
+        raw_stride <= 0 || (raw_stride & 15) || ((uintptr_t)raw & 15) || staging_bytes < 0 || ((uintptr_t)staging & 15))
+        return ctx->fail(LLFE_ERR_INVALID, "llfe_png_decode_device: bad arguments (n=%d h=%d w=%d raw_stride=%lld)", n, h,
+                         w, (long long)raw_stride);
+    // nothing is launched on a descriptor the host check has not passed
+    if (!llfe_png::validate_png_descs(descs, n, h, w, staging_bytes, raw_stride))
+        return ctx->fail(LLFE_ERR_INVALID, "llfe_png_decode_device: a descriptor points outside the staging buffer or "
+                                           "its geometry is not %dx%d at 3 or 4 bytes per pixel", w, h);
+    int staged = 0;
+    double in_bytes = 0, raw_bytes = 0;
+    for (int i = 0; i < n; i++) {
+        status_out[i] = descs[i].deflate_bytes ? LLFE_OK : LLFE_ERR_UNSUPPORTED;
+        if (descs[i].deflate_bytes) {
+            staged++;
+            in_bytes += descs[i].deflate_bytes;
+            raw_bytes += (double)descs[i].raw_bytes;
+        }
+    }
+    if (staged == 0) return LLFE_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(ctx, ctx->h_png_desc.ensure((size_t)n));
+    HIPCHK(ctx, ctx->d_png_desc.ensure((size_t)n));
+    HIPCHK(ctx, ctx->h_jpeg_status.ensure((size_t)n));
+    HIPCHK(ctx, ctx->d_jpeg_status.ensure((size_t)n));
+    std::memcpy(ctx->h_png_desc.p, descs, sizeof(llfe_png_desc) * (size_t)n);
+    std::memcpy(ctx->h_jpeg_status.p, status_out, sizeof(int32_t) * (size_t)n);
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_png_desc.p, ctx->h_png_desc.p, sizeof(llfe_png_desc) * (size_t)n,
+                               hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_jpeg_status.p, ctx->h_jpeg_status.p, sizeof(int32_t) * (size_t)n,
+                               hipMemcpyHostToDevice, s));
+    const int prev_slot = ctx->prof.cur_slot;
+    ctx->prof.cur_slot = Profiler::kStageSlot;
+    auto launch = [&](int stage) {
+        return launch_png_decode(stage, staging, ctx->d_png_desc.p, n, h, w, raw, raw_stride, out_bgr, ctx->d_jpeg_status.p,
+                                 s);
+    };
+    const int rc = [&]() -> int {
+        TIMED(ctx, s, "k_png_inflate", in_bytes + raw_bytes, launch(0));
+        TIMED(ctx, s, "k_png_unfilter_bgr", raw_bytes + (double)staged * h * w * 3, launch(1));
+        return LLFE_OK;
+    }();
+    ctx->prof.cur_slot = prev_slot;
+    if (rc != LLFE_OK) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_jpeg_status.p, ctx->d_jpeg_status.p, sizeof(int32_t) * (size_t)n,
+                               hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));  // (the pinned descriptors are free again)
     ctx->prof.collect(Profiler::kStageSlot);
     std::memcpy(status_out, ctx->h_jpeg_status.p, sizeof(int32_t) * (size_t)n);
     return LLFE_OK;

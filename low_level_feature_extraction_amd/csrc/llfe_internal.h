@@ -402,4 +402,12 @@ hipError_t launch_jpeg_huff(int stage, int pass, int kinds, const uint8_t *stagi
                             const llfe_jpeg_desc *d_descs, int n, int max_sub, int max_blocks, int64_t max_coef_bytes,
                             uint8_t *slots, int64_t slot_stride, uint8_t *workspace, int *d_status, hipStream_t s);
 
+// llfe_png_decode_device (png_inflate.hip).  The descriptors are validated on the host first
+// (png_inflate_core.h validate_png_descs); d_descs is that array on the device, d_status n ints,
+// non-zero for the images to skip.  Stages, in this order on one stream: 0 = inflate into raw
+// (n x raw_stride) with the Adler-32 check, 1 = unfilter raw into out (n x h x w x 3); either
+// sets d_status of an image that shows an anomaly.
+hipError_t launch_png_decode(int stage, const uint8_t *staging, const llfe_png_desc *d_descs, int n, int h, int w,
+                             uint8_t *raw, int64_t raw_stride, uint8_t *out, int *d_status, hipStream_t s);
+
 }  // namespace llfe

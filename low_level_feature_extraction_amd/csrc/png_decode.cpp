@@ -15,6 +15,9 @@
 // pixel per step), then the row is converted straight into the NHWC batch (RGB -> BGR by
 // SSSE3 shuffles where the CPU has them).
 // A batch fans out over std::threads, one image per task.
+//
+// At the end of the file: the host half of the opt-in device decode (llfe_png_parse_batch: the
+// same chunk walk, the deflate stream staged instead of inflated) and the kernels' host twin.
 #include <dlfcn.h>
 #include <emmintrin.h>
 #include <tmmintrin.h>
@@ -31,6 +34,7 @@
 #include <vector>
 
 #include "llfe.h"
+#include "png_inflate_core.h"
 
 namespace {
 
@@ -625,4 +629,135 @@ extern "C" int llfe_decode_png_batch(const uint8_t *const *data, const uint64_t 
 extern "C" int llfe_decode_batch(const uint8_t *const *data, const uint64_t *sizes, int32_t n, int32_t height,
                                  int32_t width, uint8_t *out_bgr, int32_t *status, int32_t threads) {
     return decode_fanout(data, sizes, n, height, width, out_bgr, status, threads, decode_any);
+}
+
+// ---------------------------------------------------------------- PNG decode on the device
+// The host half (llfe_png_parse_batch) and the host twin of the kernels
+// (llfe_png_decode_reference), over the decoding core the kernels compile
+// (png_inflate_core.h; DESIGN.md §3 "PNG decode on the device").
+namespace {
+
+// the chunk walk of decode_one and its checks; an eligible image's deflate stream into rec
+int stage_one(const uint8_t *data, size_t size, int32_t h, int32_t w, uint8_t *rec, int64_t cap, llfe_png_desc *desc) {
+    if (!is_png(data, size)) return LLFE_ERR_UNSUPPORTED;
+    Png png;
+    const int rc = parse(data, size, png, false);
+    if (rc) return rc;
+    if ((int64_t)png.h != h || (int64_t)png.w != w) return LLFE_ERR_UNSUPPORTED;
+    if ((uint64_t)png.w * png.h > max_pixels()) return LLFE_ERR_INVALID;
+    if (png.depth != 8 || (png.ctype != 2 && png.ctype != 6)) return LLFE_ERR_UNSUPPORTED;
+    const int bpp = png.channels();
+    const uint64_t rowb = (uint64_t)png.w * bpp, raw_n = (rowb + 1) * png.h;
+    uint64_t idat_n = 0;
+    for (auto &c : png.idat) idat_n += c.second;
+    if (raw_n / 1032 > idat_n + 64) return LLFE_ERR_INVALID;
+    if (raw_n > 0x7fffffffu || idat_n < 7 || idat_n > 0x7fffffffu - 64) return LLFE_ERR_UNSUPPORTED;
+    const uint64_t deflate_n = idat_n - 6;
+    if ((int64_t)(((deflate_n + 15) & ~(uint64_t)15) + 32) > cap) return LLFE_ERR_UNSUPPORTED;
+    // byte g of the concatenated payloads
+    uint8_t head[2], tail[4];
+    uint64_t g = 0;
+    for (auto &c : png.idat) {
+        for (uint64_t k = 0; k < c.second && g + k < 2; k++) head[g + k] = c.first[k];
+        for (uint64_t k = c.second; k > 0 && g + k - 1 >= idat_n - 4; k--) tail[g + k - 1 - (idat_n - 4)] = c.first[k - 1];
+        // the part of this chunk inside [2, idat_n - 4)
+        const uint64_t lo = std::max<uint64_t>(g, 2), hi = std::min<uint64_t>(g + c.second, idat_n - 4);
+        if (lo < hi) memcpy(rec + (lo - 2), c.first + (lo - g), (size_t)(hi - lo));
+        g += c.second;
+    }
+    const unsigned cmf = head[0], flg = head[1];
+    if ((cmf & 15) != 8 || (cmf >> 4) > 7 || (flg & 32) || ((cmf << 8 | flg) % 31) != 0) return LLFE_ERR_UNSUPPORTED;
+    const uint64_t pad = (deflate_n + 15) & ~(uint64_t)15;
+    memset(rec + deflate_n, 0, (size_t)(pad - deflate_n) + 32);
+    const uint32_t adler = be32(tail);
+    memcpy(rec + pad + 16, &adler, 4);
+    desc->raw_bytes = (int64_t)raw_n;
+    desc->deflate_bytes = (int32_t)deflate_n;
+    desc->bpp = bpp;
+    desc->row_bytes = (int32_t)rowb;
+    desc->adler = adler;
+    return LLFE_OK;
+}
+
+// the twin of one image: inflate into raw, Adler-32, unfilter into BGR
+int reference_one(const uint8_t *rec, const llfe_png_desc &d, int h, int w, uint8_t *raw, uint8_t *out) {
+    using namespace llfe_png;
+    Tables T;
+    Reader r;
+    rd_init(r, rec, (uint32_t)d.deflate_bytes);
+    FlatSink s{raw, 0};
+    const uint32_t raw_n = (uint32_t)d.raw_bytes;
+    int rc = inflate(r, T, s, raw_n);
+    if (rc == kOk && adler32(raw, raw_n) != d.adler) rc = kEAdler;
+    if (rc != kOk) return rc;
+    const size_t stride = (size_t)d.row_bytes + 1;
+    for (int y = 0; y < h; y++)
+        if (raw[y * stride] > 4) rc = kEFilter;
+    if (rc != kOk) return rc;
+    for (int y = 0; y < h; y++) {
+        const uint8_t *src = raw + y * stride + 1;
+        const int f = raw[y * stride];
+        uint8_t *o = out + (size_t)y * w * 3;
+        const uint8_t *up = y ? o - (size_t)w * 3 : nullptr;
+        uint32_t a = 0, c = 0;
+        for (int x = 0; x < w; x++) {
+            const uint8_t *p = src + (size_t)x * d.bpp;
+            const uint32_t b = up ? (uint32_t)up[3 * x] | (uint32_t)up[3 * x + 1] << 8 | (uint32_t)up[3 * x + 2] << 16 : 0;
+            a = llfe_png::unfilter_px(f, (uint32_t)p[2] | (uint32_t)p[1] << 8 | (uint32_t)p[0] << 16, a, b, c);
+            st24(o + 3 * x, a);
+            c = b;
+        }
+    }
+    return kOk;
+}
+
+}  // namespace
+
+extern "C" int llfe_png_parse_batch(const uint8_t *const *data, const uint64_t *sizes, int32_t n, int32_t height,
+                                    int32_t width, uint8_t *staging, int64_t record_stride, llfe_png_desc *descs,
+                                    int32_t *status, int32_t threads) {
+    if (n < 0 || (n && (!data || !sizes || !staging || !descs || !status)) || height <= 0 || width <= 0 ||
+        record_stride < 48 || (record_stride & 15))
+        return LLFE_ERR_INVALID;
+    const int nt = std::max(1, std::min<int>(threads > 0 ? threads : 1, n));
+    std::atomic<int> next{0};
+    auto work = [&]() {
+        for (int i; (i = next.fetch_add(1)) < n;) {
+            llfe_png_desc d{};
+            d.record_offset = (int64_t)i * record_stride;
+            int rc;
+            try {
+                rc = data[i] ? stage_one(data[i], (size_t)sizes[i], height, width, staging + d.record_offset, record_stride, &d)
+                             : LLFE_ERR_INVALID;
+            } catch (const std::bad_alloc &) {
+                rc = LLFE_ERR_OOM;
+            }
+            if (rc) d = llfe_png_desc{};
+            descs[i] = d;
+            status[i] = rc;
+        }
+    };
+    std::vector<std::thread> th;
+    for (int t = 1; t < nt; t++) th.emplace_back(work);
+    work();
+    for (auto &t : th) t.join();
+    for (int i = 0; i < n; i++)
+        if (status[i]) return status[i];
+    return LLFE_OK;
+}
+
+extern "C" int llfe_png_decode_reference(const uint8_t *staging, int64_t staging_bytes, const llfe_png_desc *descs,
+                                         int32_t n, int32_t h, int32_t w, uint8_t *raw, int64_t raw_stride,
+                                         uint8_t *out_bgr, int32_t *status) {
+    if (n < 0 || h <= 0 || w <= 0 || (n && (!staging || !descs || !raw || !out_bgr || !status)) || staging_bytes < 0 ||
+        raw_stride <= 0 || !llfe_png::validate_png_descs(descs, n, h, w, staging_bytes, raw_stride))
+        return LLFE_ERR_INVALID;
+    for (int i = 0; i < n; i++) {
+        status[i] = LLFE_ERR_UNSUPPORTED;
+        if (descs[i].deflate_bytes == 0) continue;
+        if (reference_one(staging + descs[i].record_offset, descs[i], h, w, raw + (size_t)i * raw_stride,
+                          out_bgr + (size_t)i * h * w * 3) == llfe_png::kOk)
+            status[i] = LLFE_OK;
+    }
+    return LLFE_OK;
 }

@@ -13,7 +13,9 @@ above ``MAX_PIXELS`` (cv2's CV_IO_MAX_IMAGE_PIXELS, 2^30) fail like cv2.imdecode
 
 ``decode_batch_device`` (opt-in, at the end of this module) returns the same batch in device
 memory: for JPEG the host stops after the entropy half and csrc/jpeg_recon.hip reconstructs;
-with ``entropy="device"`` baseline files are entropy-decoded on the device too (csrc/jpeg_huff.hip).
+with ``entropy="device"`` baseline files are entropy-decoded on the device too (csrc/jpeg_huff.hip);
+with ``png="device"`` 8-bit RGB / RGBA PNGs are inflated, unfiltered and converted there
+(csrc/png_inflate.hip).
 """
 from __future__ import annotations
 
@@ -487,7 +489,7 @@ def _bytes_staging(n, stride):
         return buf
 
 
-def stage_bytes(blobs, workers=None, slot_bytes=None, restarts=False) -> StagedBytes:
+def stage_bytes(blobs, workers=None, slot_bytes=None, restarts=False, size=None) -> StagedBytes:
     """The host half of decode_batch_device(entropy="device"): parse the headers of every
     eligible JPEG of a batch of equally sized images (llfe_jpeg_parse_batch: baseline Huffman,
     one interleaved scan, no restart markers, and what stage_coefs asks) and stage quantisation
@@ -496,7 +498,7 @@ def stage_bytes(blobs, workers=None, slot_bytes=None, restarts=False) -> StagedB
     longest blob, so batches of like files reuse their pinned buffers.  ``restarts=True``
     (llfe_jpeg_parse_batch_flags, LLFE_JPEG_PARSE_RESTARTS) also takes files with a restart
     interval: their scans are staged with the markers in them and the records carry the
-    interval, which is all the device half needs to know."""
+    interval, which is all the device half needs to know.  ``size`` as in stage_coefs."""
     import ctypes as C
 
     from . import _lib
@@ -504,7 +506,7 @@ def stage_bytes(blobs, workers=None, slot_bytes=None, restarts=False) -> StagedB
     blobs = [bytes(b) for b in blobs]
     if not blobs:
         raise DecodeError("empty batch")
-    hw = _image_size(blobs[0])
+    hw = size or _image_size(blobs[0])
     if hw is None:
         hw = decode_bgr(blobs[0]).shape[:2]
     h, w = hw
@@ -607,7 +609,173 @@ def decode_staged_bytes(sb: StagedBytes, device=0, workers=None, out=None):
     return out
 
 
-def decode_batch_device(blobs, device=0, workers=None, out=None, entropy="host", restarts=False):
+# ------------------------------------------------------------------ PNG decode on the device
+# PNG the same way (DESIGN.md §3 "PNG decode on the device"): the host only walks the chunks
+# (llfe_png_parse_batch), the file's deflate stream crosses PCIe instead of its pixels, and
+# llfe_png_decode_device (csrc/png_inflate.hip) inflates, unfilters and converts.  For 8-bit RGB /
+# RGBA files that are not interlaced; every other image, and every image whose stream shows an
+# anomaly, goes through the host decoders as in decode_batch.
+class StagedPng:
+    """One batch after llfe_png_parse_batch: ``records`` (n x record_stride uint8, pinned when a
+    GPU is present), ``descs`` (the llfe_png_desc array), ``status`` per image, the blobs and the
+    batch geometry."""
+
+    def __init__(self, blobs, h, w, records, descs, status, tensor=None):
+        self.blobs, self.h, self.w = blobs, h, w
+        self.records, self.descs, self.status, self.tensor = records, descs, status, tensor
+
+    @property
+    def used_bytes(self) -> int:
+        """Bytes from the start of a record that any image of the batch occupies."""
+        return max([((d.deflate_bytes + 15) & ~15) + 32 for d in self.descs if d.deflate_bytes], default=0)
+
+    @property
+    def raw_stride(self) -> int:
+        """Bytes per image of inflated rows (a multiple of 16) that hold any image of the batch."""
+        return max(16, (max([d.raw_bytes for d in self.descs], default=0) + 15) & ~15)
+
+
+_PNG_STAGE = {}
+
+
+def _png_staging(n, stride):
+    """_bytes_staging for the records of stage_png (a ring of _STAGE_RING per (count, stride))."""
+    from . import _lib
+
+    with _STAGE_LOCK:
+        ring = _PNG_STAGE.setdefault((n, stride), {"next": 0, "bufs": []})
+        if len(_PNG_STAGE) > 4:
+            for k in [k for k in _PNG_STAGE if k != (n, stride)]:
+                del _PNG_STAGE[k]
+        if len(ring["bufs"]) < _STAGE_RING:
+            tensor = None
+            try:
+                import torch
+
+                if torch.cuda.is_available():
+                    tensor = torch.empty((n, stride), dtype=torch.uint8, pin_memory=True)
+            except ImportError:  # pragma: no cover - C-only deployments
+                pass
+            arr = tensor.numpy() if tensor is not None else np.empty((n, stride), np.uint8)
+            ring["bufs"].append((arr, (_lib.LlfePngDesc * n)(), tensor))
+        buf = ring["bufs"][ring["next"] % _STAGE_RING]
+        ring["next"] += 1
+        return buf
+
+
+def stage_png(blobs, workers=None, size=None) -> StagedPng:
+    """The host half of decode_batch_device(png="device"): walk the chunks of every eligible PNG
+    of a batch of equally sized images (llfe_png_parse_batch: 8-bit RGB or RGBA, not interlaced)
+    and stage its deflate stream in the next buffer of a ring of three.  Host only; nothing is
+    inflated here.  The record stride is a bucket of the longest blob (a power of two up to
+    1 MiB, 1 MiB steps above), so batches of like files reuse their pinned buffers.  ``size`` (h, w) names the batch's image size
+    instead of reading it from the first blob (a part of a batch staged on its own)."""
+    import ctypes as C
+
+    from . import _lib
+
+    blobs = [bytes(b) for b in blobs]
+    if not blobs:
+        raise DecodeError("empty batch")
+    hw = size or _image_size(blobs[0])
+    if hw is None:
+        hw = decode_bgr(blobs[0]).shape[:2]
+    h, w = hw
+    n = len(blobs)
+    longest = max(len(b) for b in blobs)
+    stride = max(4096, 1 << (longest + 64).bit_length())
+    if stride > 1 << 20:  # (above 1 MiB a power of two wastes pinned memory: 1 MiB steps)
+        stride = (longest + 64 + (1 << 20) - 1) >> 20 << 20
+    records, descs, tensor = _png_staging(n, stride)
+    keep = [C.c_char_p(b) for b in blobs]
+    ptrs = (C.c_void_p * n)(*[C.cast(k, C.c_void_p) for k in keep])
+    sizes = (C.c_uint64 * n)(*[len(b) for b in blobs])
+    status = (C.c_int32 * n)()
+    _lib.lib().llfe_png_parse_batch(ptrs, sizes, n, h, w, records.ctypes.data, stride, descs, status,
+                                    int(workers or default_decode_threads()))
+    del keep
+    return StagedPng(blobs, h, w, records, descs, list(status), tensor)
+
+
+def png_reference(sp: StagedPng):
+    """llfe_png_decode_reference, the host twin of csrc/png_inflate.hip, over a StagedPng:
+    -> (n x raw_stride uint8 inflated rows, n x h x w x 3 BGR, status list).  Both arrays start
+    as zeros.  For tests and for debugging the kernels."""
+    import ctypes as C
+
+    from . import _lib
+
+    n = len(sp.blobs)
+    raw = np.zeros((n, sp.raw_stride), np.uint8)
+    out = np.zeros((n, sp.h, sp.w, 3), np.uint8)
+    status = (C.c_int32 * n)()
+    rc = _lib.lib().llfe_png_decode_reference(sp.records.ctypes.data, sp.records.size, sp.descs, n, sp.h, sp.w,
+                                              raw.ctypes.data, raw.shape[1], out.ctypes.data, status)
+    if rc != 0:
+        raise ValueError(f"llfe_png_decode_reference: {rc}")
+    return raw, out, list(status)
+
+
+def png_decode_staged(sp: StagedPng, device=0, out=None, raw=None):
+    """The device half without the fallback: one H2D of the used part of each staged record, then
+    llfe_png_decode_device on the current stream into ``out`` (allocated when None; the places of
+    the images with a non-zero status are undefined).  -> (out, the device's status list)."""
+    import torch
+
+    from .backend import Backend
+
+    n, h, w = len(sp.blobs), sp.h, sp.w
+    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
+        used = sp.used_bytes
+        host = sp.tensor if sp.tensor is not None else torch.from_numpy(sp.records)
+        d_rec = torch.empty((n, sp.records.shape[1]), dtype=torch.uint8, device=dev)
+        for i, rc in enumerate(sp.status):  # (a record fills what its file is long, not the bucket)
+            if rc == 0:
+                d_rec[i, :used].copy_(host[i, :used], non_blocking=True)
+        if raw is None:
+            raw = torch.empty((n, sp.raw_stride), dtype=torch.uint8, device=dev)
+        status = Backend.get(dev.index).png_decode(d_rec, sp.descs, h, w, out, raw)
+    return out, status
+
+
+def decode_staged_png(sp: StagedPng, device=0, workers=None, out=None):
+    """The device half of decode_batch_device(png="device"): the staged records across, the
+    kernels, and for every image with a non-zero parse or device status decode_batch's own
+    treatment (the native host decoders, Pillow for what they leave), so errors read as
+    decode_batch's.  -> (N, H, W, 3) uint8 tensor on the device."""
+    import torch
+
+    n, h, w = len(sp.blobs), sp.h, sp.w
+    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+    if out is None:
+        out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
+    if tuple(out.shape) != (n, h, w, 3) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"out must be a contiguous {(n, h, w, 3)} uint8 tensor on {dev}")
+    status = list(sp.status)
+    if any(rc == 0 for rc in sp.status):
+        status = png_decode_staged(sp, dev, out)[1]
+    todo = [i for i, rc in enumerate(status) if rc != 0]
+    if todo:
+        fill = torch.from_numpy(_host_fill(sp, todo, workers)).to(dev)
+        out[torch.tensor(todo, device=dev)] = fill
+    return out
+
+
+def _is_png(b) -> bool:
+    return b[:8] == _PNG_SIG
+
+
+def _renumber(e, index):
+    """A DecodeError of a part of a batch, naming the image by its place in the whole batch."""
+    head, sep, tail = str(e).partition(":")
+    k = head[len("image "):]
+    return DecodeError(f"image {index[int(k)]}:{tail}" if sep and head.startswith("image ") and k.isdigit() else str(e))
+
+
+def decode_batch_device(blobs, device=0, workers=None, out=None, entropy="host", restarts=False, png="host"):
     """decode_batch with the reconstruction on the GPU: equally sized images -> one
     (N, H, W, 3) BGR uint8 tensor on ``device``, the same bytes decode_batch returns.  Eligible
     JPEGs (8-bit greyscale or YCbCr 4:4:4 / 4:2:2 / 4:2:0, EXIF orientation 1, no decoder
@@ -620,9 +788,68 @@ def decode_batch_device(blobs, device=0, workers=None, out=None, entropy="host",
     markers to the device as well (csrc/jpeg_huff.hip): the file bytes cross PCIe, not the
     coefficients.  Images it does not take, and images whose scan the kernels find anomalous,
     go through the ``entropy="host"`` path; the result is the same bytes in every case.
-    ``restarts=True`` lets it take files with restart intervals too (stage_bytes)."""
+    ``restarts=True`` lets it take files with restart intervals too (stage_bytes).
+
+    ``png="device"`` sends the PNGs of the batch down a device path of their own (stage_png /
+    decode_staged_png: csrc/png_inflate.hip inflates, unfilters and converts 8-bit RGB / RGBA
+    files), the other images down the path ``entropy`` names, all into the one tensor; with
+    ``png="host"`` PNGs go through the host decoders as before."""
+    if entropy not in ("host", "device"):
+        raise ValueError('entropy must be "host" or "device"')
+    if png not in ("host", "device"):
+        raise ValueError('png must be "host" or "device"')
+    if png == "device":
+        blobs = [bytes(b) for b in blobs]
+        pngs = [i for i, b in enumerate(blobs) if _is_png(b)]
+        if pngs:
+            return _decode_split(blobs, pngs, device, workers, out, entropy, restarts)
     if entropy == "host":
         return reconstruct_staged(stage_coefs(blobs, workers), device, workers, out)
-    if entropy != "device":
-        raise ValueError('entropy must be "host" or "device"')
     return decode_staged_bytes(stage_bytes(blobs, workers, restarts=restarts), device, workers, out)
+
+
+def _decode_split(blobs, pngs, device, workers, out, entropy, restarts):
+    """decode_batch_device(png="device") of a batch that holds PNGs (at the places `pngs`): the
+    batch split by signature, each part down its path with the batch's size, the results
+    gathered into one tensor.  Of the parts' errors the one naming the first image is raised,
+    as decode_batch would."""
+    import torch
+
+    hw = _image_size(blobs[0])
+    if hw is None:
+        hw = decode_bgr(blobs[0]).shape[:2]
+    h, w = hw
+    n = len(blobs)
+    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+    if out is None:
+        out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
+    if tuple(out.shape) != (n, h, w, 3) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"out must be a contiguous {(n, h, w, 3)} uint8 tensor on {dev}")
+
+    def png_part(sub, o):
+        return decode_staged_png(stage_png(sub, workers, size=(h, w)), dev, workers, o)
+
+    def other_part(sub, o):
+        if entropy == "host":
+            return reconstruct_staged(stage_coefs(sub, workers, size=(h, w)), dev, workers, o)
+        return decode_staged_bytes(stage_bytes(sub, workers, restarts=restarts, size=(h, w)), dev, workers, o)
+
+    if len(pngs) == n:
+        return png_part(blobs, out)
+    is_png = set(pngs)
+    errs = []
+    for index, part in ((pngs, png_part), ([i for i in range(n) if i not in is_png], other_part)):
+        sub = torch.empty((len(index), h, w, 3), dtype=torch.uint8, device=dev)
+        try:
+            part([blobs[i] for i in index], sub)
+        except DecodeError as e:
+            errs.append(_renumber(e, index))
+            continue
+        out[torch.tensor(index, device=dev)] = sub
+    if errs:
+        def place(e):
+            k = str(e).partition(":")[0][len("image "):]
+            return int(k) if k.isdigit() else -1
+
+        raise min(errs, key=place)
+    return out
