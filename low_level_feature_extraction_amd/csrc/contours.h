@@ -1,4 +1,4 @@
-// Host-side contour structures shared by contours.cpp and llfe_api.cpp.
+// Host-side contour structures shared by contours.cpp and the host API units (llfe_ctx.h).
 #pragma once
 #include <cstdint>
 #include <vector>

@@ -1,0 +1,182 @@
+// C ABI of libllfe.so (include/llfe.h): image decode on the device -- JPEG reconstruction,
+// JPEG entropy decode and PNG inflate / unfilter, each on the caller's stream.  Every entry
+// point validates on the host, uploads its records through pinned buffers, runs its launches
+// under the stage profiler tag and waits for the stream.
+#include "jpeg_huff_core.h"
+#include "llfe_ctx.h"
+#include "png_inflate_core.h"
+
+using namespace llfe_host;
+
+namespace {
+
+// room for n records in a pinned buffer and its device twin
+template <typename T>
+hipError_t ensure_records(HostBuf<T> &h, DevBuf<T> &d, int n) {
+    const hipError_t e = h.ensure((size_t)n);
+    return e != hipSuccess ? e : d.ensure((size_t)n);
+}
+
+// n validated records: copied into the pinned buffer and uploaded from there on s
+template <typename T>
+hipError_t upload_records(HostBuf<T> &h, DevBuf<T> &d, const T *src, int n, hipStream_t s) {
+    std::memcpy(h.p, src, sizeof(T) * (size_t)n);
+    return hipMemcpyAsync(d.p, h.p, sizeof(T) * (size_t)n, hipMemcpyHostToDevice, s);
+}
+
+// the end of a decode: the per-image status back, the stream waited for (the pinned records
+// and the workspace are free again), the launches' profiler records collected
+int download_status(llfe_ctx *ctx, int32_t *status_out, int n, hipStream_t s) {
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_dec_status.p, ctx->d_dec_status.p, sizeof(int32_t) * (size_t)n,
+                               hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    ctx->prof.collect(Profiler::kStageSlot);
+    std::memcpy(status_out, ctx->h_dec_status.p, sizeof(int32_t) * (size_t)n);
+    return LLFE_OK;
+}
+
+// The plane workspace is bounded: images go through it in chunks on the one stream (a chunk's
+// colour kernel is ordered before the next chunk's IDCT).  256 MiB is 86 1080p 4:2:0 images
+// (1.5 plane bytes per pixel), 4 M blocks of IDCT per launch.
+constexpr int64_t kJpegPlaneBudget = (int64_t)256 << 20;
+
+}  // namespace
+
+extern "C" {
+
+int llfe_jpeg_reconstruct(llfe_ctx *ctx, const uint8_t *coefs, int64_t slot_stride, const llfe_jpeg_desc *descs,
+                          int32_t n, int32_t h, int32_t w, uint8_t *out_bgr, llfe_stream stream) {
+    if (!ctx) return LLFE_ERR_INVALID;
+    if (!valid_dims(n, h, w) || h > 65535 || w > 65535 || (n && (!coefs || !descs || !out_bgr)) || slot_stride <= 0 ||
+        (slot_stride & 15) || ((uintptr_t)coefs & 15))
+        return ctx->fail(LLFE_ERR_INVALID, "llfe_jpeg_reconstruct: bad arguments (n=%d h=%d w=%d slot_stride=%lld)", n, h,
+                         w, (long long)slot_stride);
+    int64_t plane_stride = 0;
+    int max_blocks = 0;
+    // nothing is launched on a descriptor the host check has not passed
+    if (!validate_jpeg_descs(descs, n, h, w, slot_stride, &plane_stride, &max_blocks))
+        return ctx->fail(LLFE_ERR_INVALID, "llfe_jpeg_reconstruct: a descriptor points outside its slot or does not "
+                                           "cover %dx%d", w, h);
+    if (n == 0 || max_blocks == 0) return LLFE_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    int64_t budget = kJpegPlaneBudget;
+    if (const char *e = getenv("LLFE_JPEG_PLANE_BYTES"); e && atoll(e) > 0) budget = atoll(e);  // (tests: many chunks)
+    const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(n, budget / plane_stride));
+    HIPCHK(ctx, ensure_records(ctx->h_jpeg_desc, ctx->d_jpeg_desc, n));
+    HIPCHK(ctx, ctx->d_jpeg_planes.ensure((size_t)chunk * (size_t)plane_stride));
+    HIPCHK(ctx, upload_records(ctx->h_jpeg_desc, ctx->d_jpeg_desc, descs, n, s));
+    for (int i0 = 0; i0 < n; i0 += chunk) {
+        StageSlotScope tag(ctx->prof);
+        const int m = std::min(chunk, n - i0);
+        const uint8_t *cf = coefs + (size_t)i0 * (size_t)slot_stride;
+        uint8_t *o = out_bgr + (size_t)i0 * (size_t)h * w * 3;
+        const llfe_jpeg_desc *dd = ctx->d_jpeg_desc.p + i0;
+        // coefficients in (2 B each, at most 3 per pixel), planes out; planes in, BGR out
+        TIMED(ctx, s, "k_jpeg_idct", (double)m * plane_stride * 3,
+              launch_jpeg_reconstruct(cf, slot_stride, dd, m, h, w, max_blocks, ctx->d_jpeg_planes.p, plane_stride, o, s,
+                                      0));
+        TIMED(ctx, s, "k_jpeg_color", (double)m * (plane_stride + (double)h * w * 3),
+              launch_jpeg_reconstruct(cf, slot_stride, dd, m, h, w, max_blocks, ctx->d_jpeg_planes.p, plane_stride, o, s,
+                                      1));
+    }
+    HIPCHK(ctx, hipStreamSynchronize(s));  // (the pinned descriptors and the planes are free again)
+    ctx->prof.collect(Profiler::kStageSlot);
+    return LLFE_OK;
+}
+
+int llfe_jpeg_entropy_decode(llfe_ctx *ctx, const uint8_t *staging, int64_t staging_bytes, const llfe_jpeg_scan *scans,
+                             const llfe_jpeg_desc *descs, int32_t n, int32_t h, int32_t w, uint8_t *slots,
+                             int64_t slot_stride, int32_t *status_out, llfe_stream stream) {
+    if (!ctx) return LLFE_ERR_INVALID;
+    if (!valid_dims(n, h, w) || h > 65535 || w > 65535 || n > 65535 ||
+        (n && (!staging || !scans || !descs || !slots || !status_out)) || slot_stride <= 0 || (slot_stride & 15) ||
+        ((uintptr_t)slots & 15) || staging_bytes < 0 || ((uintptr_t)staging & 15))
+        return ctx->fail(LLFE_ERR_INVALID, "llfe_jpeg_entropy_decode: bad arguments (n=%d h=%d w=%d slot_stride=%lld)", n,
+                         h, w, (long long)slot_stride);
+    int64_t plane_stride = 0;
+    int recon_blocks = 0, max_sub = 0, max_blocks = 0;
+    // nothing is launched on a descriptor or a record the host check has not passed
+    if (!validate_jpeg_descs(descs, n, h, w, slot_stride, &plane_stride, &recon_blocks))
+        return ctx->fail(LLFE_ERR_INVALID, "llfe_jpeg_entropy_decode: a descriptor points outside its slot or does not "
+                                           "cover %dx%d", w, h);
+    if (!llfe_huff::validate_scans(scans, descs, n, staging_bytes, &max_sub, &max_blocks))
+        return ctx->fail(LLFE_ERR_INVALID, "llfe_jpeg_entropy_decode: a scan record points outside the staging buffer, "
+                                           "its MCU geometry does not cover the block grids or its restart interval is "
+                                           "not 0..65535");
+    int64_t max_coef_bytes = 0;
+    int kinds = 0;  // bit 0: images without a restart interval, bit 1: with one
+    for (int i = 0; i < n; i++) {
+        status_out[i] = scans[i].blocks_in_mcu ? LLFE_OK : LLFE_ERR_UNSUPPORTED;
+        if (scans[i].blocks_in_mcu) kinds |= scans[i].restart_interval ? 2 : 1;
+        for (int c = 0; c < descs[i].n_comp; c++)
+            max_coef_bytes = std::max<int64_t>(max_coef_bytes, (int64_t)descs[i].comp[c].blocks_w * descs[i].comp[c].blocks_h * 128);
+    }
+    if (n == 0 || max_sub == 0) return LLFE_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(ctx, ensure_records(ctx->h_jpeg_desc, ctx->d_jpeg_desc, n));
+    HIPCHK(ctx, ensure_records(ctx->h_jpeg_scan, ctx->d_jpeg_scan, n));
+    HIPCHK(ctx, ensure_records(ctx->h_dec_status, ctx->d_dec_status, n));
+    HIPCHK(ctx, ctx->d_jpeg_huff_ws.ensure(jpeg_huff_workspace_bytes(n, max_sub, max_blocks)));
+    HIPCHK(ctx, upload_records(ctx->h_jpeg_desc, ctx->d_jpeg_desc, descs, n, s));
+    HIPCHK(ctx, upload_records(ctx->h_jpeg_scan, ctx->d_jpeg_scan, scans, n, s));
+    HIPCHK(ctx, upload_records(ctx->h_dec_status, ctx->d_dec_status, (const int32_t *)status_out, n, s));
+    const int passes = jpeg_huff_passes(max_sub);  // the cross-workgroup passes, fixed here from the scan lengths
+    auto launch = [&](int stage, int pass) {
+        return launch_jpeg_huff(stage, pass, kinds, staging, ctx->d_jpeg_scan.p, ctx->d_jpeg_desc.p, n, max_sub, max_blocks,
+                                max_coef_bytes, slots, slot_stride, ctx->d_jpeg_huff_ws.p, ctx->d_dec_status.p, s);
+    };
+    {
+        StageSlotScope tag(ctx->prof);
+        TIMED(ctx, s, "k_huff_init", (double)n * max_coef_bytes, launch(0, 0));
+        for (int p = 0; p < passes; p++) TIMED(ctx, s, "k_huff_sync", (double)staging_bytes, launch(1, p));
+        TIMED(ctx, s, "k_huff_verify", (double)n * max_sub * 20, launch(2, 0));
+        TIMED(ctx, s, "k_huff_write", (double)staging_bytes + (double)n * max_blocks * 2, launch(3, 0));
+        TIMED(ctx, s, "k_huff_dc", (double)n * max_blocks * 6, launch(4, 0));
+    }
+    return download_status(ctx, status_out, n, s);
+}
+
+int llfe_png_decode_device(llfe_ctx *ctx, const uint8_t *staging, int64_t staging_bytes, const llfe_png_desc *descs,
+                           int32_t n, int32_t h, int32_t w, uint8_t *raw, int64_t raw_stride, uint8_t *out_bgr,
+                           int32_t *status_out, llfe_stream stream) {
+    if (!ctx) return LLFE_ERR_INVALID;
+    if (!valid_dims(n, h, w) || n > 65535 || (n && (!staging || !descs || !raw || !out_bgr || !status_out)) ||
+        raw_stride <= 0 || (raw_stride & 15) || ((uintptr_t)raw & 15) || staging_bytes < 0 || ((uintptr_t)staging & 15))
+        return ctx->fail(LLFE_ERR_INVALID, "llfe_png_decode_device: bad arguments (n=%d h=%d w=%d raw_stride=%lld)", n, h,
+                         w, (long long)raw_stride);
+    // nothing is launched on a descriptor the host check has not passed
+    if (!llfe_png::validate_png_descs(descs, n, h, w, staging_bytes, raw_stride))
+        return ctx->fail(LLFE_ERR_INVALID, "llfe_png_decode_device: a descriptor points outside the staging buffer or "
+                                           "its geometry is not %dx%d at 3 or 4 bytes per pixel", w, h);
+    int staged = 0;
+    double in_bytes = 0, raw_bytes = 0;
+    for (int i = 0; i < n; i++) {
+        status_out[i] = descs[i].deflate_bytes ? LLFE_OK : LLFE_ERR_UNSUPPORTED;
+        if (descs[i].deflate_bytes) {
+            staged++;
+            in_bytes += descs[i].deflate_bytes;
+            raw_bytes += (double)descs[i].raw_bytes;
+        }
+    }
+    if (staged == 0) return LLFE_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(ctx, ensure_records(ctx->h_png_desc, ctx->d_png_desc, n));
+    HIPCHK(ctx, ensure_records(ctx->h_dec_status, ctx->d_dec_status, n));
+    HIPCHK(ctx, upload_records(ctx->h_png_desc, ctx->d_png_desc, descs, n, s));
+    HIPCHK(ctx, upload_records(ctx->h_dec_status, ctx->d_dec_status, (const int32_t *)status_out, n, s));
+    auto launch = [&](int stage) {
+        return launch_png_decode(stage, staging, ctx->d_png_desc.p, n, h, w, raw, raw_stride, out_bgr, ctx->d_dec_status.p,
+                                 s);
+    };
+    {
+        StageSlotScope tag(ctx->prof);
+        TIMED(ctx, s, "k_png_inflate", in_bytes + raw_bytes, launch(0));
+        TIMED(ctx, s, "k_png_unfilter_bgr", raw_bytes + (double)staged * h * w * 3, launch(1));
+    }
+    return download_status(ctx, status_out, n, s);
+}
+
+}  // extern "C"

@@ -15,7 +15,7 @@ namespace llfe {
 constexpr int kTileW = 64;
 constexpr int kTileH = 32;
 
-// getGaussianKernel(11, 0, CV_32F) (gauss_kernel_f32(11) in llfe_api.cpp, checked equal at
+// getGaussianKernel(11, 0, CV_32F) (gauss_kernel_f32(11) in llfe_context.cpp, checked equal at
 // llfe_create): the row-streaming stencil takes these as constants
 #define LLFE_GAUSS11_F32                                                                                     \
     0x1.20c256p-7f, 0x1.bcb86ap-6f, 0x1.0ab50ap-4f, 0x1.f2464cp-4f, 0x1.6a7e1ep-3f, 0x1.9ac20ap-3f,          \

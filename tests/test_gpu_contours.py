@@ -177,7 +177,7 @@ def test_batch_gpu_contour_mode_capacity_regrowth(backend, orc):
 def test_unsupported_gpu_contour_chunk_falls_back_to_host(orc, monkeypatch):
     """A chunk the GPU tracer flags as unsupported (kCtBadTrace / kCtTooWide /
     kCtDpOverflow) is traced on the host pool instead of failing the batch
-    (llfe_api.cpp gpu_shapes_of_chunk); contour mode LLFE_CONTOURS_GPU_FORCE_FALLBACK takes
+    (llfe_pipeline.cpp gpu_shapes_of_chunk); contour mode LLFE_CONTOURS_GPU_FORCE_FALLBACK takes
     that path."""
     from low_level_feature_extraction_amd import synth
     from low_level_feature_extraction_amd.backend import Backend

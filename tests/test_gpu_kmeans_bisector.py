@@ -21,7 +21,7 @@ pytestmark = [pytest.mark.gpu, pytest.mark.timeout(120)]
 K = 5
 CELL_MIN = 8192  # kmeans.hip LLFE_KM_CELL_MIN
 SEEDS = (2027, 31)
-COL_LL_PTS, COL_SPLIT_CUBES, COL_SPLIT_PTS = 15, 17, 18  # LLFE_KM_TRACE columns (llfe_api.cpp)
+COL_LL_PTS, COL_SPLIT_CUBES, COL_SPLIT_PTS = 15, 17, 18  # LLFE_KM_TRACE columns (llfe_pipeline.cpp)
 
 
 def _blobs(edge, keep, side):

@@ -37,7 +37,7 @@ pytestmark = [pytest.mark.gpu, pytest.mark.timeout(180)]
 K = 5
 CELL_MIN = 8192  # kmeans.hip LLFE_KM_CELL_MIN
 SEEDS = (2027, 31)
-# LLFE_KM_TRACE columns (llfe_api.cpp)
+# LLFE_KM_TRACE columns (llfe_pipeline.cpp)
 COL_ITERS, COL_LL_PTS, COL_SPLIT_CUBES, COL_SPLIT_PTS, COL_WALKS, COL_PARTIAL = 3, 15, 17, 18, 25, 26
 KW_WIDE, KW_NARROW = 8, 4
 

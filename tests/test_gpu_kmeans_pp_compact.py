@@ -49,7 +49,7 @@ CELL_MIN = 8192  # kmeans.hip LLFE_KM_CELL_MIN
 SPLIT_MIN = 8    # kmeans.hip LLFE_KM_PP_SPLIT_MIN
 SEEDS = (2027, 31)
 KW_WIDE = 8      # waves of the 512-thread build (batches whose attempts all fit the GPU at once)
-# LLFE_KM_TRACE columns (llfe_api.cpp)
+# LLFE_KM_TRACE columns (llfe_pipeline.cpp)
 COL_PP_PTS, COL_PP_SPLIT_CUBES, COL_PP_SPLIT_PTS, COL_PP_WALKS, COL_PP_WALK_LANES, COL_PP_WALK_MIXED = 11, 23, 24, 27, 28, 29
 
 # name -> (image, production noise (False: zero noise, the colours are exactly the image's), cells path)

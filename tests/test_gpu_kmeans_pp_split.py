@@ -37,7 +37,7 @@ K = 5
 CELL_MIN = 8192  # kmeans.hip LLFE_KM_CELL_MIN
 SPLIT_MIN = 8    # kmeans.hip LLFE_KM_PP_SPLIT_MIN
 SEEDS = (2027, 31)
-COL_PP_PTS, COL_PP_SPLIT_CUBES, COL_PP_SPLIT_PTS = 11, 23, 24  # LLFE_KM_TRACE columns (llfe_api.cpp)
+COL_PP_PTS, COL_PP_SPLIT_CUBES, COL_PP_SPLIT_PTS = 11, 23, 24  # LLFE_KM_TRACE columns (llfe_pipeline.cpp)
 
 
 def _blobs(edge, keep, side):

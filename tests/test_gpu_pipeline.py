@@ -7,6 +7,7 @@
 * Pillow thumbnail (reduce pre-pass + LANCZOS) bit-exact against the golden fixtures
   and Pillow itself.
 """
+import dataclasses
 import io
 import os
 
@@ -89,6 +90,45 @@ def _same(a, b):
         assert ra.n_unique == rb.n_unique and ra.compactness == rb.compactness
         assert ra.shapes == rb.shapes and (ra.shadow_sum, ra.shadow_count) == (rb.shadow_sum, rb.shadow_count)
     assert len(a) == len(b)
+
+
+def _records_equal(a, b):
+    """Every field of two lists of ImageFeatures, arrays by value."""
+    assert len(a) == len(b)
+    for i, (ra, rb) in enumerate(zip(a, b)):
+        for f in dataclasses.fields(ra):
+            va, vb = getattr(ra, f.name), getattr(rb, f.name)
+            if isinstance(va, np.ndarray):
+                assert isinstance(vb, np.ndarray) and va.dtype == vb.dtype and np.array_equal(va, vb), (i, f.name)
+            else:
+                assert va == vb, (i, f.name)
+
+
+@pytest.mark.parametrize("mode", ["host", "gpu"])
+def test_sync_multi_chunk_matches_whole_batch(backend, monkeypatch, mode):
+    """llfe_process_batch over five device passes (one image each: the host result buffers
+    alternate while the device workspace stays the same) gives the records of one pass, on
+    every field and with all four features, in either contour mode, from a host array and
+    from a device tensor."""
+    import torch
+
+    feats = ("colors", "shapes", "shadows", "fonts")
+    x = _batch(5, 48, 80, seed=13)
+    x[3] = 200  # a flat image: no shape, no font region, one colour
+    xd = torch.from_numpy(x).cuda()
+    prev = backend.contour_mode()
+    backend.set_contour_mode(mode)
+    try:
+        whole = backend.process(x, feats, seed=11, index_base=40)
+        _records_equal(backend.process(xd, feats, seed=11, index_base=40), whole)
+        monkeypatch.setenv("LLFE_WORKSPACE_GB", "0.001")
+        assert backend.batch_capacity(48, 80) == 1
+        for src in (x, xd):
+            _records_equal(backend.process(src, feats, seed=11, index_base=40), whole)
+    finally:
+        backend.set_contour_mode(prev)
+    assert any(r.shapes for r in whole) and not whole[3].shapes
+    assert all(r.font is not None for r in whole)
 
 
 def test_submit_collect_matches_process(backend):

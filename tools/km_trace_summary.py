@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Summarise an LLFE_KM_TRACE file (one line per k-means attempt, see llfe_api.cpp):
+"""Summarise an LLFE_KM_TRACE file (one line per k-means attempt, see kmeans_stage in llfe_pipeline.cpp):
 per-phase times for the "photo" (U > 300k) and "ui" classes, Lloyd time per iteration,
 Lloyd bytes per iteration relative to a plain sweep, and the kernel span / CU balance.
 
