@@ -375,7 +375,8 @@ int llfe_palette_rules(const uint8_t *centers_rgb, const int32_t *counts, int32_
  * reference: cv2.kmeans only returns the best attempt (color_extractor.py:194). */
 int llfe_kmeans_attempts(llfe_ctx *ctx, int32_t n, llfe_kmeans_attempt *out);
 /* Pillow Image.resize(size, LANCZOS, box) on u8 HWC (image_processor.py:221-224).
- * box may be NULL (whole image). src/dst device. */
+ * box = (x0, y0, x1, y1) in source pixels, or NULL (whole image); its values are taken at
+ * float32 precision, as Pillow takes them. src/dst device. */
 int llfe_resize_lanczos_pil(llfe_ctx *ctx, const uint8_t *src, int32_t h, int32_t w, int32_t ch, uint8_t *dst,
                             int32_t out_h, int32_t out_w, const double *box, llfe_stream stream);
 /* Pillow Image.reduce((fx, fy)) box averaging of a device u8 HWC image; dst holds

@@ -11,7 +11,7 @@ namespace {
 // Pillow precompute_coeffs (LANCZOS, support 3) -> 22-bit fixed point
 int pil_coeffs(int in_size, double in0, double in1, int out_size, std::vector<int32_t> &bounds,
                std::vector<int32_t> &kk) {
-    double scale = (in1 - in0) / out_size;
+    double scale = (double)((float)in1 - (float)in0) / out_size;  // Pillow subtracts its float arguments as floats
     double filterscale = scale < 1.0 ? 1.0 : scale;
     double support = 3.0 * filterscale;
     int ksize = (int)std::ceil(support) * 2 + 1;
@@ -54,7 +54,11 @@ int pil_coeffs(int in_size, double in0, double in1, int out_size, std::vector<in
 // Image.resize(size, LANCZOS, box) of n same-size packed device images
 int resize_lanczos_n(llfe_ctx *ctx, const uint8_t *src, int n, int32_t h, int32_t w, int32_t ch, uint8_t *dst,
                      int32_t out_h, int32_t out_w, const double *box, hipStream_t s) {
-    double bx0 = box ? box[0] : 0, by0 = box ? box[1] : 0, bx1 = box ? box[2] : w, by1 = box ? box[3] : h;
+    // Pillow hands the box of Image.resize to its C code as four 32-bit floats: w / 3 arrives there
+    // rounded to float32, and the coefficients follow from that value
+    auto f32 = [](double v) { return (double)(float)v; };
+    double bx0 = box ? f32(box[0]) : 0, by0 = box ? f32(box[1]) : 0, bx1 = box ? f32(box[2]) : w,
+           by1 = box ? f32(box[3]) : h;
     bool need_h = out_w != w || bx0 != 0 || bx1 != out_w;
     bool need_v = out_h != h || by0 != 0 || by1 != out_h;
     std::vector<int32_t> bh, kh, bv, kv;

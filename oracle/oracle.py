@@ -430,7 +430,8 @@ def pil_resize_lanczos(img, out_w, out_h, box=None):
     out = np.empty((out_h, out_w, ch), np.uint8)
     b = None
     if box is not None:
-        b = np.asarray(box, np.float64)
+        # Image.resize hands the box to Pillow's C code as four 32-bit floats
+        b = np.ascontiguousarray(np.asarray(box, np.float32).astype(np.float64))
     lib().orc_pil_resize_lanczos(_p(img), h, w, ch, _p(out), out_h, out_w, None if b is None else _p(b))
     return out
 

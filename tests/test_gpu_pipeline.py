@@ -5,7 +5,8 @@
   matching, compactness within 1e-3 relative) in NumPy-noise parity mode.
 * seeds are per global image index: results do not depend on batching / sharding.
 * Pillow thumbnail (reduce pre-pass + LANCZOS) bit-exact against the golden fixtures
-  and Pillow itself.
+  and Pillow itself (workload sizes; tests/test_gpu_resize_cases.py runs the small
+  directed cases of tests/resize_cases.py: boxes, every arm, the float32 thumbnail box).
 """
 import dataclasses
 import io

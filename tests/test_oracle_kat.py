@@ -379,118 +379,9 @@ def test_preprocess_and_seed_helpers(orc):
 # utils.py:118-143 (validate_and_preprocess_image): AREA / LANCZOS4 / LINEAR downscales.
 # A second restatement in NumPy (float32 scalars for OpenCV's float steps, int64 for its
 # fixed point) checked bit-exactly against llfe_oracle.c, plus hand-derived answers.
-def _np_area_tab(ssize, dsize, scale):
-    tab = []
-    for dx in range(dsize):
-        f1 = dx * scale
-        f2 = f1 + scale
-        cell = min(scale, ssize - f1)
-        s1, s2 = math.ceil(f1), math.floor(f2)
-        s2 = min(s2, ssize - 1)
-        s1 = min(s1, s2)
-        if s1 - f1 > 1e-3:
-            tab.append((dx, s1 - 1, np.float32((s1 - f1) / cell)))
-        for s in range(s1, s2):
-            tab.append((dx, s, np.float32(1.0 / cell)))
-        if f2 - s2 > 1e-3:
-            tab.append((dx, s2, np.float32(min(min(f2 - s2, 1.0), cell) / cell)))
-    return tab
-
-
-def _np_lanczos4(x):
-    x = np.float32(x)
-    s45 = 0.70710678118654752440084436210485
-    cs = [(1, 0), (-s45, -s45), (0, 1), (s45, -s45), (-1, 0), (s45, s45), (0, -1), (-s45, s45)]
-    y0 = -float(np.float32(x + np.float32(3))) * math.pi * 0.25
-    s0, c0 = math.sin(y0), math.cos(y0)
-    c = []
-    tot = np.float32(0)
-    for i in range(8):
-        yi = np.float32(np.float32(x + np.float32(3)) - np.float32(i))
-        if abs(yi) >= np.float32(1e-6):
-            y = -float(yi) * math.pi * 0.25
-            v = np.float32((cs[i][0] * s0 + cs[i][1] * c0) / (y * y))
-        else:
-            v = np.float32(1e30)
-        c.append(v)
-        tot = np.float32(tot + v)
-    inv = np.float32(np.float32(1) / tot)
-    return [np.float32(v * inv) for v in c]
-
-
-def _s16(v):
-    return int(np.clip(np.rint(np.float32(v)), -32768, 32767))
-
-
-def _np_cv_resize(img, ow, oh, interp):
-    h, w, cn = img.shape
-    sx_, sy_ = w / ow, h / oh  # = 1 / ((double)dsize / ssize) up to the last ulp; recomputed below
-    inv_x, inv_y = ow / w, oh / h
-    scale_x, scale_y = 1.0 / inv_x, 1.0 / inv_y
-    ix, iy = int(round(scale_x)), int(round(scale_y))
-    fast = abs(scale_x - ix) < 2.220446049250313e-16 and abs(scale_y - iy) < 2.220446049250313e-16
-    if interp == "linear" and fast and ix == 2 and iy == 2:
-        interp = "area"
-    if interp == "area":
-        if fast:
-            out = np.zeros((oh, ow, cn), np.uint8)
-            for dy in range(oh):
-                for dx in range(ow):
-                    blk = img[dy * iy:(dy + 1) * iy, dx * ix:(dx + 1) * ix].astype(np.int64)
-                    s = blk.sum(axis=(0, 1))
-                    if ix == 2 and iy == 2:
-                        out[dy, dx] = (s + 2) >> 2
-                    else:
-                        out[dy, dx] = np.clip(np.rint(s.astype(np.float32) * np.float32(1.0 / np.float32(ix * iy))),
-                                              0, 255)
-            return out
-        S = img.astype(np.float32)
-        buf = np.zeros((h, ow, cn), np.float32)
-        for dx, sx, a in _np_area_tab(w, ow, scale_x):
-            buf[:, dx] = buf[:, dx] + S[:, sx] * a
-        acc = np.zeros((oh, ow, cn), np.float32)
-        for dy, sy, b in _np_area_tab(h, oh, scale_y):
-            acc[dy] = acc[dy] + b * buf[sy]
-        return np.clip(np.rint(acc), 0, 255).astype(np.uint8)
-    ks = 8 if interp == "lanczos4" else 2
-
-    def coeffs(d, scale, n):
-        f = np.float32((d + 0.5) * scale - 0.5)
-        s = math.floor(f)
-        f = np.float32(f - np.float32(s))
-        if ks == 2 and s >= n - 1:
-            s, f = n - 1, np.float32(0)
-        c = _np_lanczos4(f) if ks == 8 else [np.float32(1) - f, f]
-        return s, [_s16(np.float32(v * np.float32(2048))) for v in c]
-
-    xs = [coeffs(dx, scale_x, w) for dx in range(ow)]
-    ys = [coeffs(dy, scale_y, h) for dy in range(oh)]
-    I = img.astype(np.int64)
-    # horizontal pass for every source row: (h, ow, cn)
-    hor = np.zeros((h, ow, cn), np.int64)
-    for dx, (sx, a) in enumerate(xs):
-        for j in range(ks):
-            col = min(max(sx - (ks // 2 - 1) + j, 0), w - 1)
-            hor[:, dx] += I[:, col] * a[j]
-    width = ow * cn
-    x_vec = 0
-    while x_vec <= width - 16:
-        x_vec += 16
-    while x_vec < width - 8:
-        x_vec += 8
-    out = np.zeros((oh, ow * cn), np.int64)
-    for dy, (sy, b) in enumerate(ys):
-        rows = [hor[min(max(sy - (ks // 2 - 1) + k, 0), h - 1)].reshape(-1) for k in range(ks)]
-        if ks == 8:
-            v = sum(r * bk for r, bk in zip(rows, b))
-            out[dy] = (v + (1 << 21)) >> 22
-        else:
-            scal = (rows[0] * b[0] + rows[1] * b[1] + (1 << 21)) >> 22
-            t = ((np.clip(rows[0] >> 4, -32768, 32767) * b[0]) >> 16) + ((np.clip(rows[1] >> 4, -32768, 32767) * b[1]) >> 16)
-            vec = (np.clip(t, -32768, 32767) + 2) >> 2
-            idx = np.arange(width)
-            out[dy] = np.where(idx < x_vec, vec, scal)
-    return np.clip(out, 0, 255).astype(np.uint8).reshape(oh, ow, cn)
+# The restatement lives in tests/resize_cases.py, which also runs it on upscales
+# (tests/test_resize_case_inputs.py).
+from tests.resize_cases import np_cv_resize as _np_cv_resize, np_lanczos4 as _np_lanczos4  # noqa: E402
 
 
 RESIZE_CASES = [  # (h, w, oh, ow): exact 2x, 3x, fractional, tall, wide, odd
