@@ -73,6 +73,84 @@ def _is_torch(x) -> bool:
     return isinstance(x, torch.Tensor)
 
 
+def _default_device(device: int | None = None) -> int:
+    if device is None:
+        device = int(os.environ.get("LLFE_DEVICE", os.environ.get("LOCAL_RANK", "0")))
+    return device
+
+
+_DESC_DTYPE = None  # np.dtype(L.LlfeImageDesc), made at the first use
+
+
+def _image_descs(images, device: int):
+    """The llfe_image_desc records of a list of H x W x 3 uint8 images, numpy arrays (host) or
+    torch tensors (host or the GPU ``device``), for process_images and submit_images:
+    -> (numpy structured array with data / height / width / row_stride / on_device filled, keep-alive
+    list, heights, widths, the first device tensor or None).  An image is read in place when its
+    pixels are packed and its rows do not overlap (rows may be strided), and otherwise gets one
+    packed copy.  A device tensor on another GPU than ``device`` raises ValueError: its pointer
+    means nothing to this context."""
+    global _DESC_DTYPE
+    if _DESC_DTYPE is None:
+        _DESC_DTYPE = np.dtype(L.LlfeImageDesc)
+    keep, ptr, hh, ww, st, dev = [], [], [], [], [], []
+    u8 = first = None
+    for i, im in enumerate(images):
+        if _is_torch(im):
+            # (few attribute calls per image: at serving rates this loop holds the GIL once per
+            # request; a contiguous tensor needs no look at its strides)
+            if u8 is None:
+                u8 = _torch().uint8
+            shp = im.shape
+            if len(shp) != 3 or shp[2] != 3 or im.dtype != u8:
+                raise ValueError(f"image {i}: expected H x W x 3 uint8, got {tuple(shp)} {im.dtype}")
+            t, stride = im, 3 * shp[1]
+            if not t.is_contiguous():
+                if t.stride(2) != 1 or t.stride(1) != 3 or t.stride(0) < stride:
+                    t = t.contiguous()  # pixels not packed, or rows overlap (stride 0): one copy
+                else:
+                    stride = t.stride(0)
+            on_dev = 1 if t.is_cuda else 0
+            if on_dev:
+                if t.device.index != device:
+                    raise ValueError(f"image {i}: tensor on cuda:{t.device.index}, context on cuda:{device}")
+                if first is None:
+                    first = t
+            ptr.append(t.data_ptr())
+        else:
+            t = np.asarray(im)
+            if t.dtype != np.uint8 or t.ndim != 3 or t.shape[2] != 3:
+                raise ValueError(f"image {i}: expected H x W x 3 uint8, got {t.shape} {t.dtype}")
+            shp = t.shape
+            if t.strides[2] != 1 or t.strides[1] != 3 or t.strides[0] < 3 * shp[1]:
+                t = np.ascontiguousarray(t)
+            ptr.append(t.ctypes.data)
+            stride, on_dev = t.strides[0], 0
+        dev.append(on_dev)
+        st.append(stride)
+        hh.append(shp[0])
+        ww.append(shp[1])
+        keep.append(t)
+    descs = np.zeros(len(keep), _DESC_DTYPE)
+    descs["data"], descs["height"], descs["width"] = ptr, hh, ww
+    descs["row_stride"], descs["on_device"] = st, dev
+    return descs, keep, hh, ww, first
+
+
+def _dev_u8_2d(name: str, t, shape: str = "2-d"):
+    if not (_is_torch(t) and t.is_cuda and t.dtype == _torch().uint8 and t.dim() == 2 and t.is_contiguous()):
+        raise ValueError(f"{name} must be a contiguous {shape} uint8 device tensor")
+
+
+def _shape_dict(s) -> dict:
+    return {"type": L.SHAPE_TYPES[s.type], "x": int(s.x), "y": int(s.y), "width": int(s.width),
+            "height": int(s.height), "border_radius": float(s.border_radius), "area": float(s.area)}
+
+
+def _font_dict(r) -> dict:
+    return {k: int(getattr(r, k)) for k in _FONT_FIELDS}
+
+
 def font_bits_tiling(h: int, w: int):
     """(strip width, segment height) of k_font_bits for an h x w image (llfe_font_bits_tiling)."""
     sw, sh = C.c_int32(0), C.c_int32(0)
@@ -94,9 +172,7 @@ class Backend:
     _ilock = threading.Lock()
 
     def __init__(self, device: int | None = None):
-        if device is None:
-            device = int(os.environ.get("LLFE_DEVICE", os.environ.get("LOCAL_RANK", "0")))
-        self.device = device
+        self.device = device = _default_device(device)
         # PyTorch-ROCm ships its own HIP runtime (torch/lib/libamdhip64.so) beside the
         # /opt/rocm one libllfe links: torch's must initialise first, or its later
         # lazy init finds "no HIP GPUs" once libllfe holds the device
@@ -114,11 +190,11 @@ class Backend:
             raise L.LlfeError(rc, f"llfe_init(device={device}) failed (no HIP device available?)")
         self.ctx = ctx
         self._lock = threading.RLock()  # (re-entered by submit -> _call)
+        self._inflight = {}  # ticket -> what collect needs; keeps the batch's inputs alive
 
     @classmethod
     def get(cls, device: int | None = None) -> "Backend":
-        if device is None:
-            device = int(os.environ.get("LLFE_DEVICE", os.environ.get("LOCAL_RANK", "0")))
+        device = _default_device(device)
         key = (device, threading.get_ident())
         with cls._ilock:
             b = cls._instances.get(key)
@@ -206,6 +282,25 @@ class Backend:
             return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
         return C.c_void_p(0)
 
+    def _with_shapes(self, n, mask, ticket, call):
+        """(results, shapes, font records) of one batch call for n images: ``call(results, shapes,
+        capacity, needed)`` -> rc runs again with the shape array grown to ``needed`` when it
+        returns LLFE_ERR_CAPACITY, and the font records of ``ticket`` (or L.LAST_CALL) are
+        fetched under the same lock hold, so no other call comes between."""
+        results = (L.LlfeImageResult * max(n, 1))()
+        cap = max(64 * n, 64)
+        needed = C.c_int64(0)
+        with self._lock:
+            while True:
+                shapes = (L.LlfeShape * cap)()
+                rc = call(results, shapes, cap, C.byref(needed))
+                if rc == L.LLFE_ERR_CAPACITY and needed.value > cap:
+                    cap = int(needed.value)
+                    continue
+                self._chk(rc)
+                break
+            return results, shapes, self._font_records(ticket, n, mask)
+
     @staticmethod
     def _batch_view(images):
         """-> (pointer, n, h, w, on_device, keepalive)"""
@@ -246,21 +341,10 @@ class Backend:
         mask = feature_mask(features)
         b = L.LlfeBatch(C.c_void_p(ptr), n, h, w, on_dev, C.c_void_p(nptr) if nptr else None, n_on_dev,
                         int(n_colors), index_base)
-        results = (L.LlfeImageResult * max(n, 1))()
-        cap = max(64 * n, 64)
-        needed = C.c_int64(0)
         stream = self._stream(keep)
-        with self._lock:
-            while True:
-                shapes = (L.LlfeShape * cap)()
-                rc = self._lib.llfe_process_batch(self.ctx, C.byref(b), mask, C.c_uint64(seed & (2**64 - 1)), results,
-                                                  shapes, cap, C.byref(needed), stream)
-                if rc == L.LLFE_ERR_CAPACITY and needed.value > cap:
-                    cap = int(needed.value)
-                    continue
-                self._chk(rc)
-                break
-            fonts = self._font_records(L.LAST_CALL, n, mask)
+        results, shapes, fonts = self._with_shapes(n, mask, L.LAST_CALL, lambda res, sh, cap, need: (
+            self._lib.llfe_process_batch(self.ctx, C.byref(b), mask, C.c_uint64(seed & (2**64 - 1)), res, sh, cap,
+                                         need, stream)))
         out = self._convert(results, shapes, n, mask, w, h, fonts)
         del keep, nkeep
         return out
@@ -276,51 +360,21 @@ class Backend:
         its preprocessed size, or None.  Returns ImageFeatures in input order."""
         n = len(images)
         mode = PRE_MODES.get(preprocessing, 0)
-        descs = (L.LlfeImageDesc * max(n, 1))()
-        keep, sizes = [], []
-        for i, im in enumerate(images):
-            if _is_torch(im):
-                t = im
-                if t.dtype != _torch().uint8 or t.dim() != 3 or t.shape[2] != 3:
-                    raise ValueError(f"image {i}: expected H x W x 3 uint8, got {tuple(t.shape)} {t.dtype}")
-                if t.stride(2) != 1 or t.stride(1) != 3 or t.stride(0) < 3 * t.shape[1]:
-                    t = t.contiguous()  # pixels not packed, or rows overlap (stride 0): one copy
-                ptr, h, w, stride, dev = t.data_ptr(), t.shape[0], t.shape[1], t.stride(0), int(t.is_cuda)
-            else:
-                t = np.asarray(im)
-                if t.dtype != np.uint8 or t.ndim != 3 or t.shape[2] != 3:
-                    raise ValueError(f"image {i}: expected H x W x 3 uint8, got {t.shape} {t.dtype}")
-                if t.strides[2] != 1 or t.strides[1] != 3 or t.strides[0] < 3 * t.shape[1]:
-                    t = np.ascontiguousarray(t)
-                ptr, h, w, stride, dev = t.ctypes.data, t.shape[0], t.shape[1], t.strides[0], 0
-            keep.append(t)
-            descs[i].data, descs[i].height, descs[i].width = ptr, h, w
-            descs[i].row_stride, descs[i].on_device = stride, dev
-            plan = preprocess_size(w, h, preprocessing)
-            oh, ow = (plan[1], plan[0]) if plan else (h, w)
-            sizes.append((ow, oh))
-            if noise is not None:
-                nptr, n_on_dev, nk = self._noise_view(noise[i], 1, oh, ow)
-                keep.append(nk)
-                descs[i].noise, descs[i].noise_on_device = nptr, n_on_dev
+        descs, keep, hs, ws, first = _image_descs(images, self.device)
+        for i in range(n):
+            plan = preprocess_size(ws[i], hs[i], preprocessing)
+            if plan:
+                ws[i], hs[i] = plan[0], plan[1]
+        if noise is not None:
+            nz = [self._noise_view(noise[i], 1, hs[i], ws[i]) for i in range(n)]
+            descs["noise"], descs["noise_on_device"] = [v[0] or 0 for v in nz], [v[1] for v in nz]
+            keep.append(nz)
         mask = feature_mask(features)
-        results = (L.LlfeImageResult * max(n, 1))()
-        cap = max(64 * n, 64)
-        needed = C.c_int64(0)
-        stream = self._stream(next((t for t in keep if _is_torch(t) and t.is_cuda), None))
-        with self._lock:
-            while True:
-                shapes = (L.LlfeShape * cap)()
-                rc = self._lib.llfe_process_images(self.ctx, descs, n, mask, mode, int(n_colors),
-                                                   C.c_uint64(seed & (2**64 - 1)), index_base, results, shapes, cap,
-                                                   C.byref(needed), stream)
-                if rc == L.LLFE_ERR_CAPACITY and needed.value > cap:
-                    cap = int(needed.value)
-                    continue
-                self._chk(rc)
-                break
-            fonts = self._font_records(L.LAST_CALL, n, mask)
-        out = self._convert(results, shapes, n, mask, [sz[0] for sz in sizes], [sz[1] for sz in sizes], fonts)
+        stream = self._stream(first)
+        results, shapes, fonts = self._with_shapes(n, mask, L.LAST_CALL, lambda res, sh, cap, need: (
+            self._lib.llfe_process_images(self.ctx, descs.ctypes.data, n, mask, mode, int(n_colors),
+                                          C.c_uint64(seed & (2**64 - 1)), index_base, res, sh, cap, need, stream)))
+        out = self._convert(results, shapes, n, mask, ws, hs, fonts)
         del keep
         return out
 
@@ -388,12 +442,8 @@ class Backend:
         ticket = C.c_int64(0)
         self._call("llfe_submit_batch", C.byref(b), mask, C.c_uint64(seed & (2**64 - 1)), self._stream(keep),
                    C.byref(ticket))
-        if not hasattr(self, "_inflight"):
-            self._inflight = {}
         self._inflight[ticket.value] = (n, h, w, mask, keep, nkeep, b)  # inputs stay alive
         return ticket.value
-
-    _DESC_DTYPE = None
 
     def batch_capacity(self, h: int, w: int) -> int:
         """Images of h x w one ``submit`` / ``submit_images`` launch takes."""
@@ -409,70 +459,21 @@ class Backend:
         n = len(images)
         if n < 1:
             raise ValueError("submit_images needs at least one image")
-        if Backend._DESC_DTYPE is None:
-            Backend._DESC_DTYPE = np.dtype(L.LlfeImageDesc)
-        descs = np.zeros(n, Backend._DESC_DTYPE)
-        keep = []
-        ptr, hh, ww, st, dev = [], [], [], [], []
-        u8 = None
-        for i, im in enumerate(images):
-            if _is_torch(im):
-                # (few attribute calls per image: at serving rates this loop holds the GIL
-                # once per request; a strided tensor is packed by one copy)
-                if u8 is None:
-                    u8 = _torch().uint8
-                shp = im.shape
-                if len(shp) != 3 or shp[2] != 3 or im.dtype != u8:
-                    raise ValueError(f"image {i}: expected H x W x 3 uint8, got {tuple(shp)} {im.dtype}")
-                t = im if im.is_contiguous() else im.contiguous()
-                ptr.append(t.data_ptr())
-                st.append(3 * shp[1])
-                dev.append(1 if t.is_cuda else 0)
-                hh.append(shp[0])
-                ww.append(shp[1])
-                keep.append(t)
-            else:
-                t = np.asarray(im)
-                if t.dtype != np.uint8 or t.ndim != 3 or t.shape[2] != 3:
-                    raise ValueError(f"image {i}: expected H x W x 3 uint8, got {t.shape} {t.dtype}")
-                if t.strides[2] != 1 or t.strides[1] != 3 or t.strides[0] < 3 * t.shape[1]:
-                    t = np.ascontiguousarray(t)
-                ptr.append(t.ctypes.data)
-                st.append(t.strides[0])
-                dev.append(0)
-                hh.append(t.shape[0])
-                ww.append(t.shape[1])
-                keep.append(t)
-        descs["data"], descs["height"], descs["width"] = ptr, hh, ww
-        descs["row_stride"], descs["on_device"] = st, dev
+        descs, keep, hh, ww, first = _image_descs(images, self.device)
         idx = np.ascontiguousarray(np.arange(n) if indices is None else indices, dtype=np.int64)
         if idx.shape != (n,):
             raise ValueError("indices must hold one global index per image")
         mask = feature_mask(features)
         ticket = C.c_int64(0)
-        stream = self._stream(next((t for t in keep if _is_torch(t) and t.is_cuda), None))
         self._call("llfe_submit_images", descs.ctypes.data, n, mask, int(n_colors), C.c_uint64(seed & (2**64 - 1)),
-                   idx.ctypes.data, stream, C.byref(ticket))
-        if not hasattr(self, "_inflight"):
-            self._inflight = {}
+                   idx.ctypes.data, self._stream(first), C.byref(ticket))
         self._inflight[ticket.value] = (n, hh, ww, mask, keep, idx, descs)
         return ticket.value
 
     def collect(self, ticket: int) -> list:
         n, h, w, mask, keep, nkeep, b = self._inflight[ticket]
-        results = (L.LlfeImageResult * max(n, 1))()
-        cap = max(64 * n, 64)
-        needed = C.c_int64(0)
-        with self._lock:
-            while True:
-                shapes = (L.LlfeShape * cap)()
-                rc = self._lib.llfe_collect_batch(self.ctx, C.c_int64(ticket), results, shapes, cap, C.byref(needed))
-                if rc == L.LLFE_ERR_CAPACITY and needed.value > cap:
-                    cap = int(needed.value)
-                    continue
-                self._chk(rc)
-                break
-            fonts = self._font_records(ticket, n, mask)
+        results, shapes, fonts = self._with_shapes(n, mask, ticket, lambda res, sh, cap, need: (
+            self._lib.llfe_collect_batch(self.ctx, C.c_int64(ticket), res, sh, cap, need)))
         del self._inflight[ticket]
         return self._convert(results, shapes, n, mask, w, h, fonts)
 
@@ -485,30 +486,34 @@ class Backend:
             images = images[None]
         return images.to(f"cuda:{self.device}").contiguous()
 
-    def gray_blur5(self, images):
+    def _dev_image(self, x, axis: int = 2):
+        """One image (or mask batch) as a contiguous tensor on this device, a 2-d one made 3-d
+        by a new axis ``axis`` -> (tensor, whether it was 2-d)."""
+        if not _is_torch(x):
+            x = _torch().from_numpy(np.ascontiguousarray(x, np.uint8))
+        x = x.to(f"cuda:{self.device}").contiguous()
+        squeeze = x.dim() == 2
+        return (x.unsqueeze(axis) if squeeze else x), squeeze
+
+    def _u8_map(self, fn: str, images):
+        """The stage function ``fn`` (in, out, n, h, w, stream) over a batch: n x h x w u8 device
+        tensor."""
         torch = _torch()
         x = self._dev_batch(images)
         n, h, w, _ = x.shape
         out = torch.empty((n, h, w), dtype=torch.uint8, device=x.device)
-        self._call("llfe_gray_blur5", x.data_ptr(), out.data_ptr(), n, h, w, self._stream(x))
+        self._call(fn, x.data_ptr(), out.data_ptr(), n, h, w, self._stream(x))
         return out
 
+    def gray_blur5(self, images):
+        return self._u8_map("llfe_gray_blur5", images)
+
     def edge_classes(self, images):
-        torch = _torch()
-        x = self._dev_batch(images)
-        n, h, w, _ = x.shape
-        out = torch.empty((n, h, w), dtype=torch.uint8, device=x.device)
-        self._call("llfe_edge_classes", x.data_ptr(), out.data_ptr(), n, h, w, self._stream(x))
-        return out
+        return self._u8_map("llfe_edge_classes", images)
 
     def font_binary(self, images):
         """FontDetector.preprocess_image on the GPU: n x h x w u8 0/255 device tensor."""
-        torch = _torch()
-        x = self._dev_batch(images)
-        n, h, w, _ = x.shape
-        out = torch.empty((n, h, w), dtype=torch.uint8, device=x.device)
-        self._call("llfe_font_binary", x.data_ptr(), out.data_ptr(), n, h, w, self._stream(x))
-        return out
+        return self._u8_map("llfe_font_binary", images)
 
     def font_bits(self, images):
         """The font binary as bit rows in one kernel (llfe_font_bits): n x h x ceil(w / 64)
@@ -538,9 +543,7 @@ class Backend:
         Images whose descriptor has n_comp == 0 are left untouched in ``out``.  A descriptor
         that points outside its slot raises LlfeError (LLFE_ERR_INVALID) before any launch."""
         torch = _torch()
-        if not (_is_torch(coefs) and coefs.is_cuda and coefs.dtype == torch.uint8 and coefs.dim() == 2 and
-                coefs.is_contiguous()):
-            raise ValueError("jpeg_reconstruct: coefs must be a contiguous n x slot_stride uint8 device tensor")
+        _dev_u8_2d("jpeg_reconstruct: coefs", coefs, "n x slot_stride")
         n, stride = coefs.shape
         if len(descs) != n:
             raise ValueError(f"jpeg_reconstruct: {len(descs)} descriptors for {n} slots")
@@ -563,10 +566,8 @@ class Backend:
         that was not staged or whose scan showed an anomaly (decode it another way).  A record
         or descriptor that points outside its buffer raises LlfeError (LLFE_ERR_INVALID) before
         any launch."""
-        torch = _torch()
-        for name, t in (("records", records), ("slots", slots)):
-            if not (_is_torch(t) and t.is_cuda and t.dtype == torch.uint8 and t.dim() == 2 and t.is_contiguous()):
-                raise ValueError(f"jpeg_entropy_decode: {name} must be a contiguous 2-d uint8 device tensor")
+        _dev_u8_2d("jpeg_entropy_decode: records", records)
+        _dev_u8_2d("jpeg_entropy_decode: slots", slots)
         n, stride = slots.shape
         if records.shape[0] != n or len(scans) != n or len(descs) != n or records.device != slots.device:
             raise ValueError(f"jpeg_entropy_decode: records, scans and descriptors for {n} slots on one device")
@@ -586,9 +587,7 @@ class Backend:
         place in ``out`` is undefined: decode it another way).  A descriptor that points outside
         its record raises LlfeError (LLFE_ERR_INVALID) before any launch."""
         torch = _torch()
-        if not (_is_torch(records) and records.is_cuda and records.dtype == torch.uint8 and records.dim() == 2 and
-                records.is_contiguous()):
-            raise ValueError("png_decode: records must be a contiguous n x record_stride uint8 device tensor")
+        _dev_u8_2d("png_decode: records", records, "n x record_stride")
         n = records.shape[0]
         if len(descs) != n:
             raise ValueError(f"png_decode: {len(descs)} descriptors for {n} records")
@@ -620,12 +619,9 @@ class Backend:
         x = self._dev_batch(images) if images is not None else None
         b = None
         if binary is not None:
-            b = binary if _is_torch(binary) else torch.from_numpy(np.ascontiguousarray(binary, np.uint8))
-            if b.dtype != torch.uint8:
-                raise ValueError(f"expected a uint8 binary, got {b.dtype}")
-            if b.dim() == 2:
-                b = b[None]
-            b = b.to(f"cuda:{self.device}").contiguous()
+            if _is_torch(binary) and binary.dtype != torch.uint8:
+                raise ValueError(f"expected a uint8 binary, got {binary.dtype}")
+            b, _ = self._dev_image(binary, axis=0)
             if b.dim() != 3 or (x is not None and tuple(b.shape) != tuple(x.shape[:3])):
                 raise ValueError(f"binary {tuple(b.shape)} does not match the images")
         n, h, w = (x if x is not None else b).shape[:3]
@@ -646,11 +642,9 @@ class Backend:
             break
         out = []
         for i in range(n):
-            r = res[i]
-            d = {"n_contours": int(r.n_contours), "n_regions": int(r.n_regions), "x": int(r.x), "y": int(r.y),
-                 "width": int(r.width), "height": int(r.height), "gray_sum": int(r.gray_sum)}
+            d = _font_dict(res[i])
             if regions:
-                o = int(r.region_offset)
+                o = int(res[i].region_offset)
                 d["regions"] = [tuple(v) for v in reg[o:o + d["n_regions"]].tolist()]
             out.append(d)
         return out
@@ -660,10 +654,7 @@ class Backend:
         H x W [x C] uint8 image (C = 1, 3 BGR or 4 BGRA) -> (out_h x out_w 0/255 device
         tensor, Otsu threshold)."""
         torch = _torch()
-        x = image if _is_torch(image) else torch.from_numpy(np.ascontiguousarray(image, np.uint8))
-        x = x.to(f"cuda:{self.device}").contiguous()
-        if x.dim() == 2:
-            x = x[:, :, None]
+        x, _ = self._dev_image(image)
         h, w, ch = x.shape
         oh, ow = text_size(h, w)
         out = torch.empty((oh, ow), dtype=torch.uint8, device=x.device)
@@ -673,22 +664,12 @@ class Backend:
         return out, int(t.value)
 
     def shape_mask(self, images):
-        torch = _torch()
-        x = self._dev_batch(images)
-        n, h, w, _ = x.shape
-        out = torch.empty((n, h, w), dtype=torch.uint8, device=x.device)
-        self._call("llfe_shape_mask", x.data_ptr(), out.data_ptr(), n, h, w, self._stream(x))
-        return out
+        return self._u8_map("llfe_shape_mask", images)
 
     def canny(self, images):
         """Canny(blur5(gray), 50, 150) of the shapes path, before its dilation: n x h x w
         u8 0/255 device tensor."""
-        torch = _torch()
-        x = self._dev_batch(images)
-        n, h, w, _ = x.shape
-        out = torch.empty((n, h, w), dtype=torch.uint8, device=x.device)
-        self._call("llfe_canny", x.data_ptr(), out.data_ptr(), n, h, w, self._stream(x))
-        return out
+        return self._u8_map("llfe_canny", images)
 
     def hysteresis(self, classes, tile_flags=True):
         """The hysteresis of canny / shape_mask on caller class maps: an n x h x w (or
@@ -707,10 +688,7 @@ class Backend:
     def dilate3(self, masks):
         """dilate(masks, ones(3, 3)) of an n x h x w (or h x w) u8 batch on the GPU."""
         torch = _torch()
-        x = masks if _is_torch(masks) else torch.from_numpy(np.ascontiguousarray(masks, np.uint8))
-        x = x.to(f"cuda:{self.device}").contiguous()
-        if x.dim() == 2:
-            x = x[None]
+        x, _ = self._dev_image(masks, axis=0)
         n, h, w = x.shape
         out = torch.empty_like(x)
         self._call("llfe_dilate3", x.data_ptr(), out.data_ptr(), n, h, w, self._stream(x))
@@ -755,9 +733,7 @@ class Backend:
             self._chk(rc)
             out, k = [], 0
             for i in range(n):
-                out.append([{"type": L.SHAPE_TYPES[s.type], "x": int(s.x), "y": int(s.y), "width": int(s.width),
-                             "height": int(s.height), "border_radius": float(s.border_radius),
-                             "area": float(s.area)} for s in arr[k:k + ns[i]]])
+                out.append([_shape_dict(s) for s in arr[k:k + ns[i]]])
                 k += int(ns[i])
             return out, nc
 
@@ -825,10 +801,7 @@ class Backend:
     def resize_lanczos_pil(self, image, out_w, out_h, box=None):
         """Pillow LANCZOS resize of one H x W x C uint8 image (torch GPU tensor or numpy)."""
         torch = _torch()
-        x = image if _is_torch(image) else torch.from_numpy(np.ascontiguousarray(image, np.uint8))
-        x = x.to(f"cuda:{self.device}").contiguous()
-        if x.dim() == 2:
-            x = x[:, :, None]
+        x, _ = self._dev_image(image)
         h, w, ch = x.shape
         out = torch.empty((out_h, out_w, ch), dtype=torch.uint8, device=x.device)
         bx = None
@@ -841,10 +814,7 @@ class Backend:
 
     def reduce_pil(self, image, fx, fy):
         torch = _torch()
-        x = image if _is_torch(image) else torch.from_numpy(np.ascontiguousarray(image, np.uint8))
-        x = x.to(f"cuda:{self.device}").contiguous()
-        if x.dim() == 2:
-            x = x[:, :, None]
+        x, _ = self._dev_image(image)
         h, w, ch = x.shape
         out = torch.empty(((h + fy - 1) // fy, (w + fx - 1) // fx, ch), dtype=torch.uint8, device=x.device)
         self._call("llfe_reduce_pil", x.data_ptr(), h, w, ch, fx, fy, out.data_ptr(),
@@ -857,11 +827,7 @@ class Backend:
         code or one of "linear" / "area" / "lanczos4"."""
         torch = _torch()
         code = CV_INTER[interpolation] if isinstance(interpolation, str) else int(interpolation)
-        x = image if _is_torch(image) else torch.from_numpy(np.ascontiguousarray(image, np.uint8))
-        x = x.to(f"cuda:{self.device}").contiguous()
-        squeeze = x.dim() == 2
-        if squeeze:
-            x = x[:, :, None]
+        x, squeeze = self._dev_image(image)
         h, w, ch = x.shape
         out = torch.empty((out_h, out_w, ch), dtype=torch.uint8, device=x.device)
         self._call("llfe_resize_cv", x.data_ptr(), h, w, ch, out.data_ptr(), out_h, out_w, code,
@@ -871,11 +837,7 @@ class Backend:
     def thumbnail_pil(self, image, max_w=1920, max_h=1080):
         """PIL thumbnail((max_w, max_h), LANCZOS) of one H x W x C uint8 image."""
         torch = _torch()
-        x = image if _is_torch(image) else torch.from_numpy(np.ascontiguousarray(image, np.uint8))
-        x = x.to(f"cuda:{self.device}").contiguous()
-        squeeze = x.dim() == 2
-        if squeeze:
-            x = x[:, :, None]
+        x, squeeze = self._dev_image(image)
         h, w, ch = x.shape
         out = torch.empty(h * w * ch, dtype=torch.uint8, device=x.device)
         oh, ow = C.c_int32(0), C.c_int32(0)
@@ -888,8 +850,7 @@ class Backend:
         """PIL thumbnail((max_w, max_h), LANCZOS) of N same-size H x W x 3 uint8 images
         (N x H x W x 3 array / tensor) in one llfe_thumbnail_pil_batch call."""
         torch = _torch()
-        x = images if _is_torch(images) else torch.from_numpy(np.ascontiguousarray(images, np.uint8))
-        x = x.to(f"cuda:{self.device}").contiguous()
+        x, _ = self._dev_image(images)
         n, h, w, ch = x.shape
         plan = thumbnail_size(w, h, max_w, max_h)
         ow, oh = plan if plan else (w, h)
@@ -968,8 +929,7 @@ def classify_contour(contour):
         raise L.LlfeError(rc, "llfe_classify_contour failed")
     if rc == 0:
         return None
-    return {"type": L.SHAPE_TYPES[s.type], "x": int(s.x), "y": int(s.y), "width": int(s.width),
-            "height": int(s.height), "border_radius": float(s.border_radius), "area": float(s.area)}
+    return _shape_dict(s)
 
 
 def shapes_from_mask(mask: np.ndarray) -> list:
@@ -986,6 +946,4 @@ def shapes_from_mask(mask: np.ndarray) -> list:
             continue
         if n < 0:
             raise L.LlfeError(n, "llfe_shapes_from_mask failed")
-        return [{"type": L.SHAPE_TYPES[s.type], "x": int(s.x), "y": int(s.y), "width": int(s.width),
-                 "height": int(s.height), "border_radius": float(s.border_radius), "area": float(s.area)}
-                for s in arr[:n]]
+        return [_shape_dict(s) for s in arr[:n]]

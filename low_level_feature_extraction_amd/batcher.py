@@ -397,11 +397,14 @@ class MicroBatcher:
                     if pending:
                         finish_oldest()
                     continue
-                # one launch per image size (the launch packs one size), at most one device
-                # pass each
+                # one launch per image size (the launch packs one size) and per place (host, or
+                # a GPU's index: a tensor on another GPU fails alone, not with its group), at
+                # most one device pass each
                 groups: dict = {}
                 for it in live:
-                    groups.setdefault((tuple(it[0].shape), _is_torch(it[0]) and it[0].is_cuda), []).append(it)
+                    im = it[0]
+                    place = im.device.index if _is_torch(im) and im.is_cuda else None
+                    groups.setdefault((tuple(im.shape), place), []).append(it)
                 for (shape, _), grp in groups.items():
                     cap = max(1, self._capacity(be, shape[0], shape[1]))
                     for a in range(0, len(grp), cap):

@@ -41,19 +41,24 @@ def _is_native(b) -> bool:
 def _native(blobs, h, w, out, threads) -> list:
     """libllfe's host decoders (PNG / JPEG, llfe_decode_batch) over all blobs into
     out[i]; other formats get LLFE_ERR_UNSUPPORTED.  Returns the per-image status list."""
-    import ctypes as C
-
     from . import _lib
 
-    L = _lib.lib()
-    n = len(blobs)
-    keep = [C.c_char_p(b) if _is_native(b) else None for b in blobs]
-    ptrs = (C.c_void_p * n)(*[C.cast(k, C.c_void_p) if k is not None else None for k in keep])
-    sizes = (C.c_uint64 * n)(*[len(b) for b in blobs])
-    status = (C.c_int32 * n)()
-    L.llfe_decode_batch(ptrs, sizes, n, h, w, out.ctypes.data, status, int(threads))
+    ptrs, sizes, status, keep = _blob_table(blobs, _is_native)
+    _lib.lib().llfe_decode_batch(ptrs, sizes, len(blobs), h, w, out.ctypes.data, status, int(threads))
     del keep
     return list(status)
+
+
+def _blob_table(blobs, take=None):
+    """The arguments every batch entry point of libllfe takes for n blobs: (pointer array, size
+    array, zeroed int32 status array, keep-alive list).  A blob that ``take`` refuses gets a NULL
+    pointer."""
+    import ctypes as C
+
+    n = len(blobs)
+    keep = [C.c_char_p(b) if take is None or take(b) else None for b in blobs]
+    ptrs = (C.c_void_p * n)(*[C.cast(k, C.c_void_p) if k is not None else None for k in keep])
+    return ptrs, (C.c_uint64 * n)(*[len(b) for b in blobs]), (C.c_int32 * n)(), keep
 
 
 def decoder_info() -> str:
@@ -273,8 +278,90 @@ def decode_batch(blobs, out=None, workers=None) -> np.ndarray:
 # (csrc/jpeg_recon.hip) writes the BGR batch in device memory, bit for bit what decode_batch
 # writes on the host.  Opt-in: nothing above calls it.
 _STAGE_RING = 3  # staging buffers per (size, count): extraction of batch k + 1 beside batch k's copy
-_STAGE = {}
+_RINGS = {}  # family ("coefs" / "bytes" / "png") -> {(n, stride): ring}
 _STAGE_LOCK = _threading.Lock()
+
+
+def _ring(family, n, stride, make_descs):
+    """The next of _STAGE_RING staging buffers of ``family`` for n records of `stride` bytes:
+    (numpy view, *make_descs(n), torch tensor or None).  Pinned when torch sees a GPU.  A family
+    that holds more than four (n, stride) keys drops its other ones; families do not evict each
+    other."""
+    with _STAGE_LOCK:
+        rings = _RINGS.setdefault(family, {})
+        ring = rings.setdefault((n, stride), {"next": 0, "bufs": []})
+        if len(rings) > 4:  # other batch shapes: drop their pinned memory
+            for k in [k for k in rings if k != (n, stride)]:
+                del rings[k]
+        if len(ring["bufs"]) < _STAGE_RING:  # (filled in order, then handed out round robin)
+            tensor = None
+            try:
+                import torch
+
+                if torch.cuda.is_available():
+                    tensor = torch.empty((n, stride), dtype=torch.uint8, pin_memory=True)
+            except ImportError:  # pragma: no cover - C-only deployments
+                pass
+            arr = tensor.numpy() if tensor is not None else np.empty((n, stride), np.uint8)
+            ring["bufs"].append((arr, *make_descs(n), tensor))
+        buf = ring["bufs"][ring["next"] % _STAGE_RING]
+        ring["next"] += 1
+        return buf
+
+
+def _batch_blobs(blobs, size=None):
+    """-> (the blobs as bytes, h, w) of a batch of equally sized images: ``size``, else the first
+    blob's header, else a decode of the first blob.  DecodeError for an empty batch."""
+    blobs = [bytes(b) for b in blobs]
+    if not blobs:
+        raise DecodeError("empty batch")
+    hw = size or _image_size(blobs[0])
+    if hw is None:
+        hw = decode_bgr(blobs[0]).shape[:2]
+    return blobs, hw[0], hw[1]
+
+
+def _slot_bytes(slot_bytes, h, w) -> int:
+    if slot_bytes is not None and (slot_bytes <= 0 or slot_bytes % 16):
+        raise ValueError("slot_bytes must be a positive multiple of 16")
+    return slot_bytes or coef_slot_bytes(h, w)
+
+
+def _device(device):
+    import torch
+
+    return torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+
+
+def _out_tensor(device, n, h, w, out):
+    """-> (torch device, ``out`` checked, or a new n x h x w x 3 uint8 tensor on it)."""
+    import torch
+
+    dev = _device(device)
+    if out is None:
+        out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
+    if tuple(out.shape) != (n, h, w, 3) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"out must be a contiguous {(n, h, w, 3)} uint8 tensor on {dev}")
+    return dev, out
+
+
+def _to_device(st, buf, dev, whole=False):
+    """A device copy of a staged batch's buffer ``buf`` (n x stride): the used part of each
+    accepted record (a record fills what its file is long, not the bucket; a subsampled JPEG
+    about half of a 4:4:4 slot), or with ``whole`` the buffer in one copy when more than three
+    quarters of a record is used."""
+    import torch
+
+    used, stride = st.used_bytes, buf.shape[1]
+    host = st.tensor if st.tensor is not None else torch.from_numpy(buf)
+    d = torch.empty(tuple(buf.shape), dtype=torch.uint8, device=dev)
+    if whole and 4 * used > 3 * stride:
+        d.copy_(host, non_blocking=True)
+    else:
+        for i, rc in enumerate(st.status):
+            if rc == 0:
+                d[i, :used].copy_(host[i, :used], non_blocking=True)
+    return d
 
 
 class StagedCoefs:
@@ -309,45 +396,13 @@ def coef_slot_bytes(h: int, w: int) -> int:
 
 def _read_coefs(blobs, h, w, slots, descs, threads) -> list:
     """llfe_jpeg_read_coefs_batch over all blobs into slots[i] / descs[i]; -> status list."""
-    import ctypes as C
-
     from . import _lib
 
-    n = len(blobs)
-    keep = [C.c_char_p(b) for b in blobs]
-    ptrs = (C.c_void_p * n)(*[C.cast(k, C.c_void_p) for k in keep])
-    sizes = (C.c_uint64 * n)(*[len(b) for b in blobs])
-    status = (C.c_int32 * n)()
-    _lib.lib().llfe_jpeg_read_coefs_batch(ptrs, sizes, n, h, w, slots.ctypes.data, slots.strides[0], descs, status,
-                                          int(threads))
+    ptrs, sizes, status, keep = _blob_table(blobs)
+    _lib.lib().llfe_jpeg_read_coefs_batch(ptrs, sizes, len(blobs), h, w, slots.ctypes.data, slots.strides[0], descs,
+                                          status, int(threads))
     del keep
     return list(status)
-
-
-def _staging(n, stride):
-    """The next of _STAGE_RING staging buffers for n slots of `stride` bytes: (numpy view,
-    descriptor array, torch tensor or None).  Pinned when torch sees a GPU."""
-    from . import _lib
-
-    with _STAGE_LOCK:
-        ring = _STAGE.setdefault((n, stride), {"next": 0, "bufs": []})
-        if len(_STAGE) > 4:  # other batch shapes: drop their pinned memory
-            for k in [k for k in _STAGE if k != (n, stride)]:
-                del _STAGE[k]
-        if len(ring["bufs"]) < _STAGE_RING:  # (filled in order, then handed out round robin)
-            tensor = None
-            try:
-                import torch
-
-                if torch.cuda.is_available():
-                    tensor = torch.empty((n, stride), dtype=torch.uint8, pin_memory=True)
-            except ImportError:  # pragma: no cover - C-only deployments
-                pass
-            arr = tensor.numpy() if tensor is not None else np.empty((n, stride), np.uint8)
-            ring["bufs"].append((arr, (_lib.LlfeJpegDesc * n)(), tensor))
-        buf = ring["bufs"][ring["next"] % _STAGE_RING]
-        ring["next"] += 1
-        return buf
 
 
 def stage_coefs(blobs, workers=None, slot_bytes=None, size=None) -> StagedCoefs:
@@ -358,25 +413,21 @@ def stage_coefs(blobs, workers=None, slot_bytes=None, size=None) -> StagedCoefs:
     sizes a slot: a feed known to be 4:2:0 needs half, and an image that does not fit is
     handed back to the host decoders like any other.  ``size`` (h, w) names the batch's image
     size instead of reading it from the first blob (a part of a batch staged on its own)."""
-    blobs = [bytes(b) for b in blobs]
-    if not blobs:
-        raise DecodeError("empty batch")
-    hw = size or _image_size(blobs[0])
-    if hw is None:
-        hw = decode_bgr(blobs[0]).shape[:2]
-    h, w = hw
+    from . import _lib
+
+    blobs, h, w = _batch_blobs(blobs, size)
     if h > 65535 or w > 65535:  # beyond JPEG: nothing to stage, the host decoders take every image
         return StagedCoefs(blobs, h, w, None, None, [-5] * len(blobs))
-    if slot_bytes is not None and (slot_bytes <= 0 or slot_bytes % 16):
-        raise ValueError("slot_bytes must be a positive multiple of 16")
-    slots, descs, tensor = _staging(len(blobs), slot_bytes or coef_slot_bytes(h, w))
+    slots, descs, tensor = _ring("coefs", len(blobs), _slot_bytes(slot_bytes, h, w),
+                                 lambda n: ((_lib.LlfeJpegDesc * n)(),))
     status = _read_coefs(blobs, h, w, slots, descs, workers or default_decode_threads())
     return StagedCoefs(blobs, h, w, slots, descs, status, tensor)
 
 
-def _host_fill(st: StagedCoefs, todo, workers):
-    """decode_batch's treatment of the images in `todo`: the native host decoders, Pillow for
-    what they leave; -> len(todo) x h x w x 3, or DecodeError naming the image."""
+def _host_fill(st, todo, workers):
+    """decode_batch's treatment of the images in `todo` of a staged batch of any family (its
+    blobs, h and w are read): the native host decoders, Pillow for what they leave;
+    -> len(todo) x h x w x 3, or DecodeError naming the image."""
     h, w = st.h, st.w
     sub = [st.blobs[i] for i in todo]
     out = np.empty((len(sub), h, w, 3), np.uint8)
@@ -409,25 +460,11 @@ def reconstruct_staged(st: StagedCoefs, device=0, workers=None, out=None):
     from .backend import Backend
 
     n, h, w = len(st.blobs), st.h, st.w
-    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
-    if out is None:
-        out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
-    if tuple(out.shape) != (n, h, w, 3) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != dev:
-        raise ValueError(f"out must be a contiguous {(n, h, w, 3)} uint8 tensor on {dev}")
+    dev, out = _out_tensor(device, n, h, w, out)
     todo = [i for i, rc in enumerate(st.status) if rc != 0]
     if len(todo) < n:
         with torch.cuda.device(dev):
-            used = st.used_bytes
-            stride = st.slots.shape[1]
-            host = st.tensor if st.tensor is not None else torch.from_numpy(st.slots)
-            d_slots = torch.empty((n, stride), dtype=torch.uint8, device=dev)
-            if 4 * used > 3 * stride:
-                d_slots.copy_(host, non_blocking=True)
-            else:  # subsampled batches fill about half of a 4:4:4 slot: copy what is there
-                for i, rc in enumerate(st.status):
-                    if rc == 0:
-                        d_slots[i, :used].copy_(host[i, :used], non_blocking=True)
-            Backend.get(dev.index).jpeg_reconstruct(d_slots, st.descs, h, w, out)
+            Backend.get(dev.index).jpeg_reconstruct(_to_device(st, st.slots, dev, whole=True), st.descs, h, w, out)
     if todo:
         fill = torch.from_numpy(_host_fill(st, todo, workers)).to(dev)
         out[torch.tensor(todo, device=dev)] = fill
@@ -461,34 +498,6 @@ class StagedBytes:
                    default=0)
 
 
-_BYTES_STAGE = {}
-
-
-def _bytes_staging(n, stride):
-    """_staging for the records of stage_bytes (a ring of _STAGE_RING per (count, stride))."""
-    from . import _lib
-
-    with _STAGE_LOCK:
-        ring = _BYTES_STAGE.setdefault((n, stride), {"next": 0, "bufs": []})
-        if len(_BYTES_STAGE) > 4:
-            for k in [k for k in _BYTES_STAGE if k != (n, stride)]:
-                del _BYTES_STAGE[k]
-        if len(ring["bufs"]) < _STAGE_RING:
-            tensor = None
-            try:
-                import torch
-
-                if torch.cuda.is_available():
-                    tensor = torch.empty((n, stride), dtype=torch.uint8, pin_memory=True)
-            except ImportError:  # pragma: no cover - C-only deployments
-                pass
-            arr = tensor.numpy() if tensor is not None else np.empty((n, stride), np.uint8)
-            ring["bufs"].append((arr, (_lib.LlfeJpegDesc * n)(), (_lib.LlfeJpegScan * n)(), tensor))
-        buf = ring["bufs"][ring["next"] % _STAGE_RING]
-        ring["next"] += 1
-        return buf
-
-
 def stage_bytes(blobs, workers=None, slot_bytes=None, restarts=False, size=None) -> StagedBytes:
     """The host half of decode_batch_device(entropy="device"): parse the headers of every
     eligible JPEG of a batch of equally sized images (llfe_jpeg_parse_batch: baseline Huffman,
@@ -499,30 +508,18 @@ def stage_bytes(blobs, workers=None, slot_bytes=None, restarts=False, size=None)
     (llfe_jpeg_parse_batch_flags, LLFE_JPEG_PARSE_RESTARTS) also takes files with a restart
     interval: their scans are staged with the markers in them and the records carry the
     interval, which is all the device half needs to know.  ``size`` as in stage_coefs."""
-    import ctypes as C
-
     from . import _lib
 
-    blobs = [bytes(b) for b in blobs]
-    if not blobs:
-        raise DecodeError("empty batch")
-    hw = size or _image_size(blobs[0])
-    if hw is None:
-        hw = decode_bgr(blobs[0]).shape[:2]
-    h, w = hw
+    blobs, h, w = _batch_blobs(blobs, size)
     n = len(blobs)
     if h > 65535 or w > 65535:  # beyond JPEG: nothing to stage
         return StagedBytes(blobs, h, w, None, None, None, [-5] * n, 0)
-    if slot_bytes is not None and (slot_bytes <= 0 or slot_bytes % 16):
-        raise ValueError("slot_bytes must be a positive multiple of 16")
-    slot_bytes = slot_bytes or coef_slot_bytes(h, w)
+    slot_bytes = _slot_bytes(slot_bytes, h, w)
     longest = max(len(b) for b in blobs)
     stride = _lib.JPEG_RECORD_HEADER + max(4096, 1 << (longest + 32).bit_length())
-    records, descs, scans, tensor = _bytes_staging(n, stride)
-    keep = [C.c_char_p(b) for b in blobs]
-    ptrs = (C.c_void_p * n)(*[C.cast(k, C.c_void_p) for k in keep])
-    sizes = (C.c_uint64 * n)(*[len(b) for b in blobs])
-    status = (C.c_int32 * n)()
+    records, descs, scans, tensor = _ring("bytes", n, stride,
+                                          lambda n: ((_lib.LlfeJpegDesc * n)(), (_lib.LlfeJpegScan * n)()))
+    ptrs, sizes, status, keep = _blob_table(blobs)
     _lib.lib().llfe_jpeg_parse_batch_flags(ptrs, sizes, n, h, w, records.ctypes.data, stride, slot_bytes, descs, scans,
                                            status, int(workers or default_decode_threads()),
                                            _lib.JPEG_PARSE_RESTARTS if restarts else 0)
@@ -558,14 +555,9 @@ def entropy_decode_staged(sb: StagedBytes, device=0):
     from .backend import Backend
 
     n = len(sb.blobs)
-    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+    dev = _device(device)
     with torch.cuda.device(dev):
-        used = sb.used_bytes
-        host = sb.tensor if sb.tensor is not None else torch.from_numpy(sb.records)
-        d_rec = torch.empty((n, sb.records.shape[1]), dtype=torch.uint8, device=dev)
-        for i, rc in enumerate(sb.status):  # (a record fills what its file is long, not the bucket)
-            if rc == 0:
-                d_rec[i, :used].copy_(host[i, :used], non_blocking=True)
+        d_rec = _to_device(sb, sb.records, dev)
         d_slots = torch.empty((n, sb.slot_bytes), dtype=torch.uint8, device=dev)
         status = Backend.get(dev.index).jpeg_entropy_decode(d_rec, sb.scans, sb.descs, sb.h, sb.w, d_slots)
     descs = (_lib.LlfeJpegDesc * n).from_buffer_copy(sb.descs)
@@ -585,11 +577,7 @@ def decode_staged_bytes(sb: StagedBytes, device=0, workers=None, out=None):
     from .backend import Backend
 
     n, h, w = len(sb.blobs), sb.h, sb.w
-    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
-    if out is None:
-        out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
-    if tuple(out.shape) != (n, h, w, 3) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != dev:
-        raise ValueError(f"out must be a contiguous {(n, h, w, 3)} uint8 tensor on {dev}")
+    dev, out = _out_tensor(device, n, h, w, out)
     status = [-5] * n
     if any(rc == 0 for rc in sb.status):
         d_slots, descs, status = entropy_decode_staged(sb, dev)
@@ -601,10 +589,8 @@ def decode_staged_bytes(sb: StagedBytes, device=0, workers=None, out=None):
         sub = torch.empty((len(todo), h, w, 3), dtype=torch.uint8, device=dev)
         try:
             reconstruct_staged(stage_coefs([sb.blobs[i] for i in todo], workers, size=(h, w)), dev, workers, sub)
-        except DecodeError as e:  # name the image by its place in the whole batch
-            head, sep, tail = str(e).partition(":")
-            k = head[len("image "):]
-            raise DecodeError(f"image {todo[int(k)]}:{tail}" if sep and k.isdigit() else str(e)) from None
+        except DecodeError as e:
+            raise _renumber(e, todo) from None
         out[torch.tensor(todo, device=dev)] = sub
     return out
 
@@ -635,34 +621,6 @@ class StagedPng:
         return max(16, (max([d.raw_bytes for d in self.descs], default=0) + 15) & ~15)
 
 
-_PNG_STAGE = {}
-
-
-def _png_staging(n, stride):
-    """_bytes_staging for the records of stage_png (a ring of _STAGE_RING per (count, stride))."""
-    from . import _lib
-
-    with _STAGE_LOCK:
-        ring = _PNG_STAGE.setdefault((n, stride), {"next": 0, "bufs": []})
-        if len(_PNG_STAGE) > 4:
-            for k in [k for k in _PNG_STAGE if k != (n, stride)]:
-                del _PNG_STAGE[k]
-        if len(ring["bufs"]) < _STAGE_RING:
-            tensor = None
-            try:
-                import torch
-
-                if torch.cuda.is_available():
-                    tensor = torch.empty((n, stride), dtype=torch.uint8, pin_memory=True)
-            except ImportError:  # pragma: no cover - C-only deployments
-                pass
-            arr = tensor.numpy() if tensor is not None else np.empty((n, stride), np.uint8)
-            ring["bufs"].append((arr, (_lib.LlfePngDesc * n)(), tensor))
-        buf = ring["bufs"][ring["next"] % _STAGE_RING]
-        ring["next"] += 1
-        return buf
-
-
 def stage_png(blobs, workers=None, size=None) -> StagedPng:
     """The host half of decode_batch_device(png="device"): walk the chunks of every eligible PNG
     of a batch of equally sized images (llfe_png_parse_batch: 8-bit RGB or RGBA, not interlaced)
@@ -670,27 +628,16 @@ def stage_png(blobs, workers=None, size=None) -> StagedPng:
     inflated here.  The record stride is a bucket of the longest blob (a power of two up to
     1 MiB, 1 MiB steps above), so batches of like files reuse their pinned buffers.  ``size`` (h, w) names the batch's image size
     instead of reading it from the first blob (a part of a batch staged on its own)."""
-    import ctypes as C
-
     from . import _lib
 
-    blobs = [bytes(b) for b in blobs]
-    if not blobs:
-        raise DecodeError("empty batch")
-    hw = size or _image_size(blobs[0])
-    if hw is None:
-        hw = decode_bgr(blobs[0]).shape[:2]
-    h, w = hw
+    blobs, h, w = _batch_blobs(blobs, size)
     n = len(blobs)
     longest = max(len(b) for b in blobs)
     stride = max(4096, 1 << (longest + 64).bit_length())
     if stride > 1 << 20:  # (above 1 MiB a power of two wastes pinned memory: 1 MiB steps)
         stride = (longest + 64 + (1 << 20) - 1) >> 20 << 20
-    records, descs, tensor = _png_staging(n, stride)
-    keep = [C.c_char_p(b) for b in blobs]
-    ptrs = (C.c_void_p * n)(*[C.cast(k, C.c_void_p) for k in keep])
-    sizes = (C.c_uint64 * n)(*[len(b) for b in blobs])
-    status = (C.c_int32 * n)()
+    records, descs, tensor = _ring("png", n, stride, lambda n: ((_lib.LlfePngDesc * n)(),))
+    ptrs, sizes, status, keep = _blob_table(blobs)
     _lib.lib().llfe_png_parse_batch(ptrs, sizes, n, h, w, records.ctypes.data, stride, descs, status,
                                     int(workers or default_decode_threads()))
     del keep
@@ -725,16 +672,11 @@ def png_decode_staged(sp: StagedPng, device=0, out=None, raw=None):
     from .backend import Backend
 
     n, h, w = len(sp.blobs), sp.h, sp.w
-    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+    dev = _device(device)
     with torch.cuda.device(dev):
         if out is None:
             out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
-        used = sp.used_bytes
-        host = sp.tensor if sp.tensor is not None else torch.from_numpy(sp.records)
-        d_rec = torch.empty((n, sp.records.shape[1]), dtype=torch.uint8, device=dev)
-        for i, rc in enumerate(sp.status):  # (a record fills what its file is long, not the bucket)
-            if rc == 0:
-                d_rec[i, :used].copy_(host[i, :used], non_blocking=True)
+        d_rec = _to_device(sp, sp.records, dev)
         if raw is None:
             raw = torch.empty((n, sp.raw_stride), dtype=torch.uint8, device=dev)
         status = Backend.get(dev.index).png_decode(d_rec, sp.descs, h, w, out, raw)
@@ -749,11 +691,7 @@ def decode_staged_png(sp: StagedPng, device=0, workers=None, out=None):
     import torch
 
     n, h, w = len(sp.blobs), sp.h, sp.w
-    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
-    if out is None:
-        out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
-    if tuple(out.shape) != (n, h, w, 3) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != dev:
-        raise ValueError(f"out must be a contiguous {(n, h, w, 3)} uint8 tensor on {dev}")
+    dev, out = _out_tensor(device, n, h, w, out)
     status = list(sp.status)
     if any(rc == 0 for rc in sp.status):
         status = png_decode_staged(sp, dev, out)[1]
@@ -815,16 +753,9 @@ def _decode_split(blobs, pngs, device, workers, out, entropy, restarts):
     as decode_batch would."""
     import torch
 
-    hw = _image_size(blobs[0])
-    if hw is None:
-        hw = decode_bgr(blobs[0]).shape[:2]
-    h, w = hw
+    blobs, h, w = _batch_blobs(blobs)
     n = len(blobs)
-    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
-    if out is None:
-        out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
-    if tuple(out.shape) != (n, h, w, 3) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != dev:
-        raise ValueError(f"out must be a contiguous {(n, h, w, 3)} uint8 tensor on {dev}")
+    dev, out = _out_tensor(device, n, h, w, out)
 
     def png_part(sub, o):
         return decode_staged_png(stage_png(sub, workers, size=(h, w)), dev, workers, o)
