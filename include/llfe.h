@@ -411,6 +411,38 @@ int llfe_thumbnail_pil(llfe_ctx *ctx, const uint8_t *src, int32_t h, int32_t w, 
 int llfe_thumbnail_pil_batch(llfe_ctx *ctx, const uint8_t *src, int32_t n, int32_t h, int32_t w, int32_t ch,
                              int32_t max_w, int32_t max_h, uint8_t *dst, int64_t dst_capacity, int32_t *out_h,
                              int32_t *out_w, llfe_stream stream);
+/* Image.thumbnail((max_w, max_h), LANCZOS) (reducing_gap 2.0) of a batch whose images each have
+ * their own size: where one image's result lies in the packed destination. */
+typedef struct {
+    int64_t offset;         /* byte offset of this image's result in dst, a multiple of 16 */
+    int32_t height, width;  /* result size: llfe_thumbnail_size of the source */
+    int32_t resized;        /* 0: the source already fits and is copied */
+    int32_t pad_;
+} llfe_thumb_out;           /* 24 bytes */
+/* host only, no ctx: the layout a call below will write (results in input order, each packed
+ * height x width x 3, each starting at a multiple of 16); *dst_bytes = bytes dst must hold (the end
+ * of the last result).  LLFE_ERR_INVALID: n < 0, a NULL output, a box side <= 0, or a
+ * descriptor llfe_process_images would reject (NULL data, invalid dimensions, a row stride that
+ * is neither 0 nor at least 3 * width). */
+int llfe_thumbnail_images_layout(const llfe_image_desc *images, int32_t n, int32_t max_w, int32_t max_h,
+                                 llfe_thumb_out *outs, int64_t *dst_bytes);
+/* ImageProcessor.auto_process_image's resize step over a batch of n BGR u8 images, each its own
+ * size, row stride and memory (host or device; the noise fields are ignored), into dst
+ * (device), packed as `outs` says (filled as llfe_thumbnail_images_layout fills it).  Every
+ * result is byte-identical to llfe_thumbnail_pil of that image.  One plan per distinct size,
+ * one upload of all tables, one reduce and one resample launch over all images
+ * (thumb_images.hip); device sources are read in place, host sources are staged through a
+ * bounded workspace (in chunks when the batch exceeds it; LLFE_THUMB_STAGE_BYTES overrides the
+ * bound).  Everything is checked on the host before the first launch: dst_capacity below the
+ * layout's total is LLFE_ERR_CAPACITY with dst untouched, a NULL ctx or a bad descriptor
+ * LLFE_ERR_INVALID; n == 0 is LLFE_OK.  Synchronous: one stream synchronisation, at the end. */
+int llfe_thumbnail_pil_images(llfe_ctx *ctx, const llfe_image_desc *images, int32_t n, int32_t max_w,
+                              int32_t max_h, uint8_t *dst, int64_t dst_capacity, llfe_thumb_out *outs,
+                              llfe_stream stream);
+/* host only: the output tile of the resample kernel (tile_w pixels x at most tile_h rows; the
+ * host picks a smaller power-of-two height for an image whose tiles would need more than
+ * lds_rows source rows) and the widest filter it takes, so that tests can stand on its seams */
+int llfe_thumbnail_images_tiling(int32_t *tile_w, int32_t *tile_h, int32_t *lds_rows, int32_t *max_ksize);
 /* host-side external contours (findContours RETR_EXTERNAL/CHAIN_APPROX_SIMPLE,
  * shape pyc @L140) on a host u8 mask; points x,y pairs; offsets[n_contours+1].
  * Returns the number of contours, or LLFE_ERR_CAPACITY with *needed_points set. */

@@ -159,6 +159,28 @@ def font_bits_tiling(h: int, w: int):
     return sw.value, sh.value
 
 
+def thumbnail_images_tiling():
+    """(tile width, largest tile height, LDS rows, largest ksize) of k_thumb_lanczos
+    (llfe_thumbnail_images_tiling)."""
+    v = [C.c_int32(0) for _ in range(4)]
+    if L.lib().llfe_thumbnail_images_tiling(*[C.byref(x) for x in v]) < 0:  # pragma: no cover
+        raise ValueError("thumbnail_images_tiling")
+    return tuple(x.value for x in v)
+
+
+def thumbnail_images_layout(images, max_w=1920, max_h=1080, device: int = 0):
+    """Where llfe_thumbnail_pil_images puts each result: -> (list of (offset, height, width,
+    resized), bytes the packed destination must hold).  Host only."""
+    descs, keep, _, _, _ = _image_descs(images, device)
+    outs = (L.LlfeThumbOut * max(len(keep), 1))()
+    total = C.c_int64(0)
+    rc = L.lib().llfe_thumbnail_images_layout(descs.ctypes.data, len(keep), int(max_w), int(max_h), outs,
+                                              C.byref(total))
+    if rc < 0:
+        raise L.LlfeError(rc, "invalid thumbnail batch")
+    return [(int(o.offset), int(o.height), int(o.width), int(o.resized)) for o in outs[:len(keep)]], int(total.value)
+
+
 def text_size(h: int, w: int):
     """Output (height, width) of TextExtractor.preprocess_image (llfe_text_size)."""
     oh, ow = C.c_int32(0), C.c_int32(0)
@@ -860,6 +882,27 @@ class Backend:
                                                      out.numel(), C.byref(ro), C.byref(co), self._stream(x))
         assert (ro.value, co.value) == (oh, ow)
         return out
+
+    def thumbnail_pil_images(self, images, max_w=1920, max_h=1080) -> list:
+        """PIL thumbnail((max_w, max_h), LANCZOS) of a list of H x W x 3 uint8 images of any
+        sizes -- numpy arrays and / or torch tensors, host or GPU, rows may be strided -- in one
+        llfe_thumbnail_pil_images call.  -> one device tensor H' x W' x 3 per image, in input
+        order, each a view into one packed uint8 tensor."""
+        torch = _torch()
+        n = len(images)
+        if n == 0:
+            return []
+        descs, keep, _, _, first = _image_descs(images, self.device)
+        outs = (L.LlfeThumbOut * n)()
+        total = C.c_int64(0)
+        rc = self._lib.llfe_thumbnail_images_layout(descs.ctypes.data, n, int(max_w), int(max_h), outs, C.byref(total))
+        if rc < 0:
+            raise L.LlfeError(rc, "invalid thumbnail batch")
+        packed = torch.empty(max(int(total.value), 1), dtype=torch.uint8, device=f"cuda:{self.device}")
+        self._call("llfe_thumbnail_pil_images", descs.ctypes.data, n, int(max_w), int(max_h), packed.data_ptr(),
+                   packed.numel(), outs, self._stream(first))
+        del keep
+        return [packed[o.offset: o.offset + o.height * o.width * 3].view(o.height, o.width, 3) for o in outs]
 
 
 _FONT_FIELDS = ("n_contours", "n_regions", "x", "y", "width", "height", "gray_sum")

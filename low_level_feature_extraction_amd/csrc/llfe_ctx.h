@@ -354,6 +354,10 @@ struct llfe_ctx {
     llfe_host::DevBuf<uint8_t> d_ragged;       // llfe_process_images: one size group's packed images
     llfe_host::DevBuf<int8_t> d_ragged_noise;
     llfe_host::DevBuf<int32_t> d_coef;
+    // llfe_thumbnail_pil_images: the call's tables (pinned, then on the device) and the staging
+    // workspace of one chunk of images
+    llfe_host::HostBuf<uint8_t> h_thumb_tab;
+    llfe_host::DevBuf<uint8_t> d_thumb_tab, d_thumb_ws;
     llfe_host::DevBuf<uint8_t> d_text;                  // llfe_text_binary: gray, then its upscale
     llfe_host::DevBuf<unsigned long long> d_text_hist;  // 256 bins + threshold + count of 255s
     // contours on the GPU (contours_gpu.hip) or on the host pool from the D2H'd mask

@@ -347,6 +347,32 @@ hipError_t launch_reduce(const uint8_t *src, int src_w, int ch, int x0, int y0, 
                          uint8_t *dst, int out_w, int out_h, hipStream_t s, int n = 1, long long src_img = 0,
                          long long dst_img = 0);
 
+// Thumbnails of a mixed-size batch (thumb_images.hip): one launch covers every image; a
+// workgroup takes one (image, tile) entry of the work table and reads that image's record.
+constexpr int kThumbTileW = 64;      // output pixels per tile row (192 bytes)
+constexpr int kThumbTileH = 32;      // output rows per tile at most; the host picks per image
+constexpr int kThumbMaxK = 25;       // Pillow's ksize at a residual scale below 4
+constexpr int kThumbLdsRows = 160;   // rows of the horizontal pass one tile may keep in LDS
+constexpr int kThumbReduceBytes = 256, kThumbReduceRows = 8;  // tile of the reduce pre-pass
+enum ThumbMode : int32_t { kThumbCopy = 0, kThumbH = 1, kThumbV = 2, kThumbBoth = 3 };
+struct ThumbRec {
+    const uint8_t *rsrc;  // the source, h x w BGR, rows rsrc_stride bytes apart (reduce pre-pass)
+    uint8_t *red;         // the pre-pass result, rh x rw packed (null without a pre-pass)
+    const uint8_t *src;   // what the resample (or the copy) reads: rh x rw, rows src_stride apart
+    uint8_t *dst;         // oh x ow packed
+    int64_t rsrc_stride, src_stride;
+    int32_t h, w, rh, rw, oh, ow, fx, fy;
+    int32_t mode, ksh, ksv, yfirst;
+    int32_t bh, kh, bv, kv;  // offsets of the plan's tables in the int32 table
+    int32_t tile_h, tiles_x, rtiles_x, pad_;
+};
+struct ThumbWork {
+    int32_t image, tile;
+};
+hipError_t launch_thumb_reduce(const ThumbRec *recs, const ThumbWork *work, int n_work, hipStream_t s);
+hipError_t launch_thumb_lanczos(const ThumbRec *recs, const ThumbWork *work, int n_work, const int32_t *tab,
+                                hipStream_t s);
+
 // cv2.resize for the preprocessing modes (cvresize.hip); OpenCV interpolation codes
 constexpr int kCvInterLinear = 1, kCvInterCubic = 2, kCvInterArea = 3, kCvInterLanczos4 = 4;
 struct CvResizePlan {

@@ -41,16 +41,30 @@ class ImageProcessor:
             raise ValueError(f"Image processing error: {str(e)}")
 
     @staticmethod
-    def auto_process_images(images_bytes, max_width: int = 1920, max_height: int = 1080) -> list:
+    def auto_process_images(images_bytes, max_width: int = 1920, max_height: int = 1080, device: bool = False) -> list:
         """Batched auto_process_image: host decode on the decode pool, then one GPU
         thumbnail launch sequence per group of equally sized images
         (llfe_thumbnail_pil_batch).  Returns arrays in input order; an input that fails
-        to decode gets the ValueError auto_process_image would raise, in its place."""
+        to decode gets the ValueError auto_process_image would raise, in its place.
+
+        ``device=True``: every decoded image, whatever its size, goes through one
+        llfe_thumbnail_pil_images call, and the results are device tensors (views into one
+        packed tensor), which Backend.process / submit and MicroBatcher.submit take as they
+        are; the bytes are those of the default route."""
         from .backend import Backend, thumbnail_size
         from .decode import decode_many
 
         decoded = decode_many(list(images_bytes))
         out: list = [None] * len(decoded)
+        if device:
+            good = [i for i, im in enumerate(decoded) if not isinstance(im, Exception)]
+            for i in set(range(len(decoded))) - set(good):
+                out[i] = ValueError("Image processing error: Failed to decode image")
+            if good:
+                res = Backend.get().thumbnail_pil_images([decoded[i] for i in good], max_width, max_height)
+                for i, t in zip(good, res):
+                    out[i] = t
+            return out
         groups: dict = {}
         for i, im in enumerate(decoded):
             if isinstance(im, Exception):
