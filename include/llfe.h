@@ -544,6 +544,57 @@ int llfe_jpeg_read_coefs_batch(const uint8_t *const *data, const uint64_t *sizes
 int llfe_jpeg_reconstruct(llfe_ctx *ctx, const uint8_t *coefs, int64_t slot_stride, const llfe_jpeg_desc *descs,
                           int32_t n, int32_t h, int32_t w, uint8_t *out_bgr, llfe_stream stream);
 
+/* ---- the same split decode for a batch whose images each have their own size (opt-in): the
+ * coefficient slots are tight and lie one behind the other in one staging buffer, the results
+ * are packed height x width x 3 where the caller says, and one launch of csrc/jpeg_images.hip
+ * reconstructs every image, whatever its size and sampling class, bit for bit what
+ * llfe_decode_batch writes.  llfe_jpeg_image says where one image's slot and result lie. */
+typedef struct {
+    int64_t slot_offset;   /* of this image's coefficient slot in the staged buffer, 16-byte aligned */
+    int64_t slot_bytes;    /* room in that slot, a multiple of 16; 0: nothing staged */
+    int64_t out_offset;    /* of this image's height x width x 3 BGR result in `out`, a multiple of 16 */
+    int32_t height, width;
+} llfe_jpeg_image;         /* 32 bytes */
+/* host only, no ctx, headers only: images[n] for n blobs.  A JPEG that is eligible as far as its
+ * header tells (what llfe_jpeg_read_coefs_batch takes) gets its height and width, a tight
+ * slot_bytes (the end of its last component as llfe_jpeg_read_coefs_batch lays a slot out,
+ * rounded up to 16: a 4:2:0 file takes half a 4:4:4 slot) and slot_offset, the running sum;
+ * *slots_bytes receives the total.  Any other image keeps slot_bytes = 0 and gets
+ * LLFE_ERR_UNSUPPORTED (PNG, CMYK, an EXIF orientation other than 1, other samplings, 12-bit
+ * files, other formats), LLFE_ERR_INVALID (corrupt data, a NULL blob) or LLFE_ERR_CAPACITY (a
+ * size above LLFE_MAX_PIXELS, as llfe_image_info); its size is still written when the header
+ * gave one, else 0 x 0.  out_offset is not touched: the caller lays out the output, because it
+ * knows the sizes of the images its other decoder takes.  status[i] per image; returns the
+ * first non-OK status. */
+int llfe_jpeg_images_layout(const uint8_t *const *data, const uint64_t *sizes, int32_t n, llfe_jpeg_image *images,
+                            int64_t *slots_bytes, int32_t *status, int32_t threads);
+/* host only, no ctx: llfe_jpeg_read_coefs_batch with each image's own height, width and slot
+ * (images[i], as laid out above) in slots (host, slots_bytes bytes).  The llfe_jpeg_desc offsets
+ * stay relative to the image's slot.  status[i] as llfe_jpeg_read_coefs_batch's: an image that
+ * does not fit its slot_bytes is LLFE_ERR_UNSUPPORTED with n_comp = 0, another size than its
+ * record says LLFE_ERR_CAPACITY; slot_bytes == 0 is LLFE_ERR_UNSUPPORTED and nothing is read.
+ * A slot outside slots_bytes (or one not 16-byte aligned) is LLFE_ERR_INVALID for the whole
+ * call, before any decode.  Returns the first non-OK status. */
+int llfe_jpeg_read_coefs_images(const uint8_t *const *data, const uint64_t *sizes, int32_t n,
+                                const llfe_jpeg_image *images, uint8_t *slots, int64_t slots_bytes,
+                                llfe_jpeg_desc *descs, int32_t *status, int32_t threads);
+/* the device half: coefs (device, coefs_bytes bytes, 16-byte aligned, as staged above) -> out
+ * (device, out_capacity bytes), image i packed height x width x 3 at images[i].out_offset.
+ * images and descs are host arrays, validated on the host before anything is launched; for
+ * every image with n_comp != 0: its descriptor against its own height x width and slot_bytes
+ * (as llfe_jpeg_reconstruct checks one), its slot inside coefs_bytes, out_offset a multiple of
+ * 16, its result inside out_capacity and apart from every other image's.  A bad record is
+ * LLFE_ERR_INVALID, or LLFE_ERR_CAPACITY when only out_capacity is short; out is untouched in
+ * both cases.  Images with n_comp == 0 are skipped, their records are not read and their
+ * places in out stay as they are.  Runs on `stream` and returns when it has finished. */
+int llfe_jpeg_reconstruct_images(llfe_ctx *ctx, const uint8_t *coefs, int64_t coefs_bytes, const llfe_jpeg_image *images,
+                                 const llfe_jpeg_desc *descs, int32_t n, uint8_t *out, int64_t out_capacity,
+                                 llfe_stream stream);
+/* host only: the output tile of csrc/jpeg_images.hip for a sampling class (LLFE_JPEG_*), a
+ * multiple of the class's MCU, so that tests can stand on its seams; LLFE_ERR_INVALID for an
+ * unknown class */
+int llfe_jpeg_images_tiling(int32_t sampling, int32_t *tile_w, int32_t *tile_h);
+
 /* ---- the entropy half on the device too (opt-in): baseline sequential Huffman files with one
  * interleaved scan, without restart markers or (llfe_jpeg_parse_batch_flags) with them.  The host only parses the headers; the file's scan
  * bytes cross to the device instead of its coefficients, csrc/jpeg_huff.hip writes exactly the

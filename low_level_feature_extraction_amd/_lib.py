@@ -161,6 +161,16 @@ class LlfeJpegDesc(C.Structure):
     ]
 
 
+class LlfeJpegImage(C.Structure):
+    _fields_ = [
+        ("slot_offset", C.c_int64),
+        ("slot_bytes", C.c_int64),
+        ("out_offset", C.c_int64),
+        ("height", C.c_int32),
+        ("width", C.c_int32),
+    ]
+
+
 class LlfeJpegScan(C.Structure):
     _fields_ = [
         ("record_offset", C.c_int64),
@@ -269,6 +279,12 @@ SIGNATURES = {
     "llfe_jpeg_coef_slot_bytes": (C.c_int64, [_i32, _i32]),
     "llfe_jpeg_read_coefs_batch": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _i64, C.POINTER(LlfeJpegDesc), _vp, _i32]),
     "llfe_jpeg_reconstruct": (C.c_int, [_vp, _vp, _i64, C.POINTER(LlfeJpegDesc), _i32, _i32, _i32, _vp, _vp]),
+    "llfe_jpeg_images_layout": (C.c_int, [_vp, _vp, _i32, C.POINTER(LlfeJpegImage), C.POINTER(_i64), _vp, _i32]),
+    "llfe_jpeg_read_coefs_images": (C.c_int, [_vp, _vp, _i32, C.POINTER(LlfeJpegImage), _vp, _i64,
+                                              C.POINTER(LlfeJpegDesc), _vp, _i32]),
+    "llfe_jpeg_reconstruct_images": (C.c_int, [_vp, _vp, _i64, C.POINTER(LlfeJpegImage), C.POINTER(LlfeJpegDesc), _i32,
+                                               _vp, _i64, _vp]),
+    "llfe_jpeg_images_tiling": (C.c_int, [_i32, C.POINTER(_i32), C.POINTER(_i32)]),
     "llfe_jpeg_parse_batch": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _i64, _i64, C.POINTER(LlfeJpegDesc),
                                         C.POINTER(LlfeJpegScan), _vp, _i32]),
     "llfe_jpeg_parse_batch_flags": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _i64, _i64, C.POINTER(LlfeJpegDesc),

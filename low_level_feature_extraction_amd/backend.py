@@ -168,6 +168,14 @@ def thumbnail_images_tiling():
     return tuple(x.value for x in v)
 
 
+def jpeg_images_tiling(sampling: int):
+    """(tile width, tile height) of k_jpeg_images for a sampling class (llfe_jpeg_images_tiling)."""
+    tw, th = C.c_int32(0), C.c_int32(0)
+    if L.lib().llfe_jpeg_images_tiling(int(sampling), C.byref(tw), C.byref(th)) < 0:
+        raise ValueError(f"jpeg_images_tiling: unknown sampling class {sampling}")
+    return tw.value, th.value
+
+
 def thumbnail_images_layout(images, max_w=1920, max_h=1080, device: int = 0):
     """Where llfe_thumbnail_pil_images puts each result: -> (list of (offset, height, width,
     resized), bytes the packed destination must hold).  Host only."""
@@ -576,6 +584,29 @@ class Backend:
             raise ValueError(f"jpeg_reconstruct: out must be a contiguous {(n, h, w, 3)} uint8 tensor on {coefs.device}")
         self._call("llfe_jpeg_reconstruct", coefs.data_ptr(), stride, descs, n, int(h), int(w), out.data_ptr(),
                    self._stream(coefs))
+        return out
+
+    def jpeg_reconstruct_images(self, coefs, images, descs, out):
+        """The device half of a JPEG decode of images of any sizes (llfe_jpeg_reconstruct_images):
+        ``coefs`` a 1-d uint8 device tensor of staged coefficient slots, ``images`` / ``descs`` the n
+        llfe_jpeg_image / llfe_jpeg_desc records (decode.stage_coefs_images, with every
+        out_offset set), ``out`` a 1-d uint8 device tensor that receives image i packed
+        height x width x 3 BGR at its out_offset, on the current stream.  Images whose descriptor
+        has n_comp == 0 are left untouched in ``out``.  A record that points outside its slot,
+        ``coefs`` or ``out``, or into another image's result, raises LlfeError (LLFE_ERR_INVALID,
+        or LLFE_ERR_CAPACITY when only ``out`` is short) before any launch.  -> ``out``."""
+        torch = _torch()
+        for name, t in (("coefs", coefs), ("out", out)):
+            if not (_is_torch(t) and t.is_cuda and t.dtype == torch.uint8 and t.dim() == 1 and t.is_contiguous()):
+                raise ValueError(f"jpeg_reconstruct_images: {name} must be a contiguous 1-d uint8 device tensor")
+        if coefs.device.index != self.device or out.device != coefs.device:
+            raise ValueError(f"jpeg_reconstruct_images: coefs on {coefs.device}, out on {out.device}, context on "
+                             f"cuda:{self.device}")
+        n = len(images)
+        if len(descs) != n:
+            raise ValueError(f"jpeg_reconstruct_images: {len(descs)} descriptors for {n} image records")
+        self._call("llfe_jpeg_reconstruct_images", coefs.data_ptr(), coefs.numel(), images, descs, n, out.data_ptr(),
+                   out.numel(), self._stream(coefs))
         return out
 
     def jpeg_entropy_decode(self, records, scans, descs, h: int, w: int, slots) -> list:

@@ -21,7 +21,9 @@
 // half (jpeg_read_coefficients) and copies the quantised coefficients and quantisation tables
 // out for the device reconstruction (jpeg_recon.hip); it takes fewer files than the decoder
 // above (no libjpeg warning, complete progressive scans, 4:4:4 / 4:2:2 / 4:2:0 / grey only)
-// and hands the rest back with LLFE_ERR_UNSUPPORTED.
+// and hands the rest back with LLFE_ERR_UNSUPPORTED.  llfe_jpeg_read_coefs_images is the same
+// extraction for images that each have their own size and tight slot (jpeg_images.hip), laid
+// out from the headers alone by layout_one behind llfe_jpeg_images_layout (png_decode.cpp).
 #include <dlfcn.h>
 #include <setjmp.h>
 
@@ -431,6 +433,8 @@ int read_coefs(const uint8_t *data, size_t size, int32_t h, int32_t w, uint8_t *
     if (rc == LLFE_OK) rc = geometry(comp, nc, sampling, h, w, slot_bytes, true, &d);
     if (rc == LLFE_OK) {
         const MemoryMgr *mem = (const MemoryMgr *)ci.mem;
+        // (the table room a grey image leaves unused: a slot's bytes depend on the file alone)
+        memset(slot + 128 * nc, 0, (size_t)(kQuantBytes - 128 * nc));
         for (int c = 0; c < nc; c++) {
             memcpy(slot + d.comp[c].quant_offset, comp[c].quant_table->quantval, 128);
             uint8_t *dst = slot + d.comp[c].coef_offset;
@@ -441,6 +445,45 @@ int read_coefs(const uint8_t *data, size_t size, int32_t h, int32_t w, uint8_t *
             }
         }
         *desc = d;
+    }
+    A.destroy(&ci);
+    return rc;
+}
+
+// llfe_jpeg_images_layout for one JPEG, headers only: its size (written once the header gave
+// one, else 0 x 0) and, for a file read_coefs would take as far as its header tells, the tight
+// bytes of its slot -- the end of its last component as geometry() lays a slot out, up to 16
+int layout_one(const uint8_t *data, size_t size, int32_t *h, int32_t *w, int64_t *slot_bytes) {
+    *h = *w = 0;
+    *slot_bytes = 0;
+    const Api &A = api();
+    if (!A.ok || !A.read_coefficients) return LLFE_ERR_UNSUPPORTED;
+    if (size < 3 || data[0] != 0xFF || data[1] != 0xD8 || data[2] != 0xFF) return LLFE_ERR_UNSUPPORTED;
+    Decompress ci;
+    Err err;
+    memset(&ci, 0, sizeof ci);
+    ci.err = A.std_error(&err.mgr);
+    err.mgr.error_exit = on_error;
+    err.mgr.output_message = on_output;
+    err.code = 0;
+    if (setjmp(err.jb)) {
+        A.destroy(&ci);
+        return err.code;
+    }
+    A.create(&ci, kJpegLibVersion, sizeof(Decompress));
+    A.mem_src(&ci, data, (unsigned long)size);
+    A.read_header(&ci, 1);
+    *w = (int32_t)ci.image_width;
+    *h = (int32_t)ci.image_height;
+    int sampling = 0;
+    llfe_jpeg_desc d;
+    memset(&d, 0, sizeof d);
+    const ComponentInfo *comp = (const ComponentInfo *)ci.comp_info;
+    volatile int rc = exif_orientation(data, size) != 1 ? LLFE_ERR_UNSUPPORTED : classify(ci, comp, *h, *w, &sampling);
+    if (rc == LLFE_OK) rc = geometry(comp, ci.num_components, sampling, *h, *w, INT64_MAX, false, &d);
+    if (rc == LLFE_OK) {
+        const auto &k = d.comp[d.n_comp - 1];
+        *slot_bytes = (k.coef_offset + (int64_t)k.blocks_w * k.blocks_h * 128 + 15) & ~(int64_t)15;
     }
     A.destroy(&ci);
     return rc;
@@ -755,6 +798,52 @@ extern "C" int llfe_jpeg_read_coefs_batch(const uint8_t *const *data, const uint
                 rc = data[i] ? llfe_jpeg::read_coefs(data[i], (size_t)sizes[i], height, width,
                                                      slots + (size_t)i * (size_t)slot_stride, slot_stride, &descs[i])
                              : LLFE_ERR_INVALID;
+            } catch (const std::bad_alloc &) {
+                rc = LLFE_ERR_OOM;
+            }
+            status[i] = rc;
+        }
+    };
+    std::vector<std::thread> th;
+    for (int t = 1; t < nt; t++) th.emplace_back(work);
+    work();
+    for (auto &t : th) t.join();
+    for (int i = 0; i < n; i++)
+        if (status[i]) return status[i];
+    return LLFE_OK;
+}
+
+// used by png_decode.cpp's llfe_jpeg_images_layout (which owns the format dispatch and the pixel limit)
+int llfe_jpeg_layout_one(const uint8_t *data, size_t size, int32_t *h, int32_t *w, int64_t *slot_bytes) {
+    return llfe_jpeg::layout_one(data, size, h, w, slot_bytes);
+}
+
+extern "C" int llfe_jpeg_read_coefs_images(const uint8_t *const *data, const uint64_t *sizes, int32_t n,
+                                           const llfe_jpeg_image *images, uint8_t *slots, int64_t slots_bytes,
+                                           llfe_jpeg_desc *descs, int32_t *status, int32_t threads) {
+    if (n < 0 || (n && (!data || !sizes || !images || !slots || !descs || !status)) || slots_bytes < 0)
+        return LLFE_ERR_INVALID;
+    for (int i = 0; i < n; i++) {  // every slot inside the buffer, before the first byte is written
+        const llfe_jpeg_image &m = images[i];
+        if (m.slot_bytes == 0) continue;
+        if (m.slot_bytes < 0 || (m.slot_bytes & 15) || m.slot_offset < 0 || (m.slot_offset & 15) ||
+            m.slot_offset > slots_bytes || m.slot_bytes > slots_bytes - m.slot_offset)
+            return LLFE_ERR_INVALID;
+    }
+    const int nt = std::max(1, std::min<int>(threads > 0 ? threads : 1, n));
+    std::atomic<int> next{0};
+    auto work = [&]() {
+        for (int i; (i = next.fetch_add(1)) < n;) {
+            const llfe_jpeg_image &m = images[i];
+            int rc;
+            memset(&descs[i], 0, sizeof descs[i]);  // n_comp 0: nothing staged for this image
+            try {
+                rc = m.slot_bytes == 0 ? LLFE_ERR_UNSUPPORTED
+                     : !data[i]        ? LLFE_ERR_INVALID
+                     : m.height <= 0 || m.width <= 0 || m.height > 65535 || m.width > 65535
+                         ? LLFE_ERR_CAPACITY  // (no JPEG has that size)
+                         : llfe_jpeg::read_coefs(data[i], (size_t)sizes[i], m.height, m.width, slots + m.slot_offset,
+                                                 m.slot_bytes, &descs[i]);
             } catch (const std::bad_alloc &) {
                 rc = LLFE_ERR_OOM;
             }

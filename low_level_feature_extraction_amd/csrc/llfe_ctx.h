@@ -380,6 +380,9 @@ struct llfe_ctx {
     llfe_host::HostBuf<llfe_jpeg_desc> h_jpeg_desc;
     llfe_host::DevBuf<llfe_jpeg_desc> d_jpeg_desc;
     llfe_host::DevBuf<uint8_t> d_jpeg_planes;
+    // llfe_jpeg_reconstruct_images: the call's image records, then its (image, tile) work table
+    llfe_host::HostBuf<uint8_t> h_jpeg_img_tab;
+    llfe_host::DevBuf<uint8_t> d_jpeg_img_tab;
     // llfe_jpeg_entropy_decode: the validated scan records and the kernels' workspace
     // (subsequence states, block counts, DC differences)
     llfe_host::HostBuf<llfe_jpeg_scan> h_jpeg_scan;

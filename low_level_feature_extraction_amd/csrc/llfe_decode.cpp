@@ -2,7 +2,12 @@
 // JPEG entropy decode and PNG inflate / unfilter, each on the caller's stream.  Every entry
 // point validates on the host, uploads its records through pinned buffers, runs its launches
 // under the stage profiler tag and waits for the stream.
+#include <algorithm>
+#include <utility>
+#include <vector>
+
 #include "jpeg_huff_core.h"
+#include "jpeg_images.h"
 #include "llfe_ctx.h"
 #include "png_inflate_core.h"
 
@@ -82,6 +87,103 @@ int llfe_jpeg_reconstruct(llfe_ctx *ctx, const uint8_t *coefs, int64_t slot_stri
     }
     HIPCHK(ctx, hipStreamSynchronize(s));  // (the pinned descriptors and the planes are free again)
     ctx->prof.collect(Profiler::kStageSlot);
+    return LLFE_OK;
+}
+
+int llfe_jpeg_images_tiling(int32_t sampling, int32_t *tile_w, int32_t *tile_h) {
+    llfe::JpegTiling t;
+    if (!tile_w || !tile_h || !llfe::jpeg_tiling(sampling, &t)) return LLFE_ERR_INVALID;
+    *tile_w = t.tw;
+    *tile_h = t.th;
+    return LLFE_OK;
+}
+
+int llfe_jpeg_reconstruct_images(llfe_ctx *ctx, const uint8_t *coefs, int64_t coefs_bytes, const llfe_jpeg_image *images,
+                                 const llfe_jpeg_desc *descs, int32_t n, uint8_t *out, int64_t out_capacity,
+                                 llfe_stream stream) {
+    using llfe::JpegImageRec;
+    using llfe::JpegWork;
+    if (!ctx) return LLFE_ERR_INVALID;
+    if (n < 0 || (n && (!coefs || !images || !descs || !out)) || coefs_bytes < 0 || out_capacity < 0 ||
+        ((uintptr_t)coefs & 15))
+        return ctx->fail(LLFE_ERR_INVALID, "llfe_jpeg_reconstruct_images: bad arguments (n=%d coefs_bytes=%lld "
+                                           "out_capacity=%lld)", n, (long long)coefs_bytes, (long long)out_capacity);
+    // nothing is launched on a record the host check has not passed
+    std::vector<JpegImageRec> recs;
+    std::vector<std::pair<int64_t, int64_t>> ranges;  // [begin, end) of every result
+    int64_t n_work = 0, out_end = 0;
+    double bytes = 0;
+    try {
+        recs.reserve((size_t)n);
+        ranges.reserve((size_t)n);
+        for (int i = 0; i < n; i++) {
+            const llfe_jpeg_desc &d = descs[i];
+            if (d.n_comp == 0) continue;  // staged elsewhere: its place in out stays as it is
+            const llfe_jpeg_image &m = images[i];
+            int64_t blocks = 0;
+            llfe::JpegTiling t;
+            if (m.height <= 0 || m.width <= 0 || m.height > 65535 || m.width > 65535 || m.slot_offset < 0 ||
+                (m.slot_offset & 15) || m.slot_bytes <= 0 || (m.slot_bytes & 15) || m.slot_offset > coefs_bytes ||
+                m.slot_bytes > coefs_bytes - m.slot_offset || m.out_offset < 0 || (m.out_offset & 15) ||
+                !llfe::check_jpeg_desc(d, m.height, m.width, m.slot_bytes, &blocks) || !llfe::jpeg_tiling(d.sampling, &t))
+                return ctx->fail(LLFE_ERR_INVALID, "llfe_jpeg_reconstruct_images: image %d: a record or descriptor "
+                                                   "points outside its slot, the coefficient buffer or does not "
+                                                   "cover %dx%d", i, m.width, m.height);
+            JpegImageRec r;
+            r.d = d;
+            r.slot_offset = m.slot_offset;
+            r.out_offset = m.out_offset;
+            r.h = m.height;
+            r.w = m.width;
+            r.tiles_x = (m.width + t.tw - 1) / t.tw;
+            r.vec = (m.width % 4 == 0 && ((uintptr_t)out & 3) == 0) ? 1 : 0;
+            recs.push_back(r);
+            const int64_t px_bytes = (int64_t)m.height * m.width * 3;
+            ranges.emplace_back(m.out_offset, m.out_offset + px_bytes);
+            out_end = std::max(out_end, m.out_offset + px_bytes);
+            n_work += (int64_t)r.tiles_x * ((m.height + t.th - 1) / t.th);
+            for (int c = 0; c < d.n_comp; c++) bytes += (double)d.comp[c].blocks_w * d.comp[c].blocks_h * 128 + 128;
+            bytes += (double)px_bytes;
+        }
+        std::sort(ranges.begin(), ranges.end());
+        for (size_t k = 1; k < ranges.size(); k++)
+            if (ranges[k].first < ranges[k - 1].second)
+                return ctx->fail(LLFE_ERR_INVALID, "llfe_jpeg_reconstruct_images: two results overlap in out");
+        if (out_end > out_capacity)
+            return ctx->fail(LLFE_ERR_CAPACITY, "llfe_jpeg_reconstruct_images: out holds %lld bytes, the results end at "
+                                                "%lld", (long long)out_capacity, (long long)out_end);
+        if (n_work > 0x7fffffff)
+            return ctx->fail(LLFE_ERR_CAPACITY, "llfe_jpeg_reconstruct_images: %lld tiles in one call",
+                             (long long)n_work);
+        if (recs.empty()) return LLFE_OK;
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        hipStream_t s = (hipStream_t)stream;
+        // the records, then the work table, through one pinned buffer
+        const size_t rec_bytes = (recs.size() * sizeof(JpegImageRec) + 15) & ~(size_t)15;
+        const size_t tab_bytes = rec_bytes + (size_t)n_work * sizeof(JpegWork);
+        HIPCHK(ctx, ctx->h_jpeg_img_tab.ensure(tab_bytes));
+        HIPCHK(ctx, ctx->d_jpeg_img_tab.ensure(tab_bytes));
+        std::memcpy(ctx->h_jpeg_img_tab.p, recs.data(), recs.size() * sizeof(JpegImageRec));
+        JpegWork *wk = (JpegWork *)(ctx->h_jpeg_img_tab.p + rec_bytes);
+        for (size_t k = 0; k < recs.size(); k++) {
+            llfe::JpegTiling t;
+            llfe::jpeg_tiling(recs[k].d.sampling, &t);
+            const int tiles = recs[k].tiles_x * ((recs[k].h + t.th - 1) / t.th);
+            for (int q = 0; q < tiles; q++) *wk++ = JpegWork{(int32_t)k, q};
+        }
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_jpeg_img_tab.p, ctx->h_jpeg_img_tab.p, tab_bytes, hipMemcpyHostToDevice, s));
+        {
+            StageSlotScope tag(ctx->prof);
+            // coefficients and tables in, BGR out: no plane goes through memory
+            TIMED(ctx, s, "k_jpeg_images", bytes,
+                  llfe::launch_jpeg_images(coefs, (const JpegImageRec *)ctx->d_jpeg_img_tab.p,
+                                           (const JpegWork *)(ctx->d_jpeg_img_tab.p + rec_bytes), (int)n_work, out, s));
+        }
+        HIPCHK(ctx, hipStreamSynchronize(s));  // (the pinned table is free again)
+        ctx->prof.collect(Profiler::kStageSlot);
+    } catch (const std::bad_alloc &) {
+        return ctx->fail(LLFE_ERR_OOM, "llfe_jpeg_reconstruct_images: out of host memory");
+    }
     return LLFE_OK;
 }
 

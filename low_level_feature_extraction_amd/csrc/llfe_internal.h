@@ -413,6 +413,14 @@ hipError_t launch_jpeg_reconstruct(const uint8_t *coefs, int64_t slot_stride, co
                                    int h, int w, int max_blocks, uint8_t *planes, int64_t plane_stride, uint8_t *out,
                                    hipStream_t s, int stage);
 
+// llfe_jpeg_reconstruct_images (jpeg_images.hip; records and tiling in jpeg_images.h): one
+// launch over n_work (image, tile) entries; d_recs holds the validated records of the call's
+// images, coefs / out are the bases their slot / result offsets count from.
+struct JpegImageRec;
+struct JpegWork;
+hipError_t launch_jpeg_images(const uint8_t *coefs, const JpegImageRec *d_recs, const JpegWork *d_work, int n_work,
+                              uint8_t *out, hipStream_t s);
+
 // llfe_jpeg_entropy_decode (jpeg_huff.hip).  The scans and descriptors are validated on the
 // host first (jpeg_huff_core.h validate_scans, validate_jpeg_descs above); max_sub / max_blocks
 // are what that check returned.  workspace: jpeg_huff_workspace_bytes of device memory,

@@ -591,6 +591,48 @@ extern "C" int llfe_image_info(const uint8_t *data, uint64_t size, int32_t *widt
     return LLFE_OK;
 }
 
+int llfe_jpeg_layout_one(const uint8_t *data, size_t size, int32_t *h, int32_t *w, int64_t *slot_bytes);
+
+extern "C" int llfe_jpeg_images_layout(const uint8_t *const *data, const uint64_t *sizes, int32_t n,
+                                       llfe_jpeg_image *images, int64_t *slots_bytes, int32_t *status, int32_t threads) {
+    if (n < 0 || !slots_bytes || (n && (!data || !sizes || !images || !status))) return LLFE_ERR_INVALID;
+    const int nt = std::max(1, std::min<int>(threads > 0 ? threads : 1, n));
+    std::atomic<int> next{0};
+    auto work = [&]() {
+        for (int i; (i = next.fetch_add(1)) < n;) {
+            llfe_jpeg_image &m = images[i];  // (out_offset is the caller's)
+            m.slot_offset = m.slot_bytes = 0;
+            m.height = m.width = 0;
+            int rc;
+            if (!data[i]) {
+                rc = LLFE_ERR_INVALID;
+            } else if (is_jpeg(data[i], (size_t)sizes[i])) {
+                rc = llfe_jpeg_layout_one(data[i], (size_t)sizes[i], &m.height, &m.width, &m.slot_bytes);
+                if ((uint64_t)(uint32_t)m.width * (uint32_t)m.height > max_pixels()) rc = LLFE_ERR_CAPACITY;
+                if (rc) m.slot_bytes = 0;
+            } else {  // another format: its size when its header gives one
+                rc = llfe_image_info(data[i], sizes[i], &m.width, &m.height);
+                if (rc == LLFE_OK) rc = LLFE_ERR_UNSUPPORTED;
+                if (rc != LLFE_ERR_UNSUPPORTED && rc != LLFE_ERR_CAPACITY) m.height = m.width = 0;
+            }
+            status[i] = rc;
+        }
+    };
+    std::vector<std::thread> th;
+    for (int t = 1; t < nt; t++) th.emplace_back(work);
+    work();
+    for (auto &t : th) t.join();
+    int64_t off = 0;
+    for (int i = 0; i < n; i++) {
+        images[i].slot_offset = off;
+        off += images[i].slot_bytes;
+    }
+    *slots_bytes = off;
+    for (int i = 0; i < n; i++)
+        if (status[i]) return status[i];
+    return LLFE_OK;
+}
+
 namespace {
 template <typename F>
 int decode_fanout(const uint8_t *const *data, const uint64_t *sizes, int32_t n, int32_t height, int32_t width,

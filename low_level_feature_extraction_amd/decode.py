@@ -15,7 +15,9 @@ above ``MAX_PIXELS`` (cv2's CV_IO_MAX_IMAGE_PIXELS, 2^30) fail like cv2.imdecode
 memory: for JPEG the host stops after the entropy half and csrc/jpeg_recon.hip reconstructs;
 with ``entropy="device"`` baseline files are entropy-decoded on the device too (csrc/jpeg_huff.hip);
 with ``png="device"`` 8-bit RGB / RGBA PNGs are inflated, unfiltered and converted there
-(csrc/png_inflate.hip).
+(csrc/png_inflate.hip).  ``decode_images_device`` (opt-in too) is decode_many's device form for
+images that each have their own size: the JPEG coefficient path over tight slots, one launch of
+csrc/jpeg_images.hip, the results views into one packed device tensor.
 """
 from __future__ import annotations
 
@@ -469,6 +471,208 @@ def reconstruct_staged(st: StagedCoefs, device=0, workers=None, out=None):
         fill = torch.from_numpy(_host_fill(st, todo, workers)).to(dev)
         out[torch.tensor(todo, device=dev)] = fill
     return out
+
+
+# ------------------------------------------------- JPEG decode of a mixed-size batch on the device
+# The coefficient path for images that each have their own size (DESIGN.md §3 "JPEG decode of a
+# mixed-size batch"): llfe_jpeg_images_layout reads the headers and lays tight slots one behind the
+# other, llfe_jpeg_read_coefs_images fills them, the staged prefix crosses PCIe in one copy and
+# llfe_jpeg_reconstruct_images (csrc/jpeg_images.hip) writes every image in one launch into one
+# packed tensor, each image at a multiple of 16 (the packing Backend.thumbnail_pil_images uses).
+# Opt-in: nothing above calls it.
+_STAGE_BYTES = 1 << 30  # one staging buffer at most (LLFE_JPEG_STAGE_BYTES): three ring buffers
+# of it stay at what the same-size path pins for 512 x 1080p
+
+
+class StagedImages:
+    """A batch of images of any sizes after its host half: ``images`` (the llfe_jpeg_image
+    records: size and slot of every image), ``descs`` (the llfe_jpeg_desc array), ``slots`` (1-d
+    uint8, pinned when a GPU is present; its first ``used_bytes`` bytes hold the slots),
+    ``layout_status`` / ``status`` per image (the header stage's, and the final one: the header
+    stage's where that is not 0, else the extraction's) and the blobs (for the images handed back
+    to the host decoders)."""
+
+    def __init__(self, blobs, images, descs, layout_status, status, slots, used_bytes, tensor=None):
+        self.blobs, self.images, self.descs = blobs, images, descs
+        self.layout_status, self.status = layout_status, status
+        self.slots, self.used_bytes, self.tensor = slots, used_bytes, tensor
+
+
+def _stage_cap() -> int:
+    import os
+
+    env = os.environ.get("LLFE_JPEG_STAGE_BYTES")
+    return int(env) if env and int(env) > 0 else _STAGE_BYTES
+
+
+def _stage_bucket(nbytes: int) -> int:
+    """The ring key of a staging buffer: a power of two from 4 KiB to 16 MiB, 16 MiB steps above,
+    so like feeds reuse their pinned memory."""
+    if nbytes <= 1 << 24:
+        return max(4096, 1 << max(nbytes - 1, 0).bit_length())
+    return (nbytes + (1 << 24) - 1) >> 24 << 24
+
+
+def images_layout(blobs, workers=None):
+    """llfe_jpeg_images_layout: -> (the llfe_jpeg_image array, status list, total slot bytes).
+    Host only, headers only; out_offset is left 0."""
+    import ctypes as C
+
+    from . import _lib
+
+    n = len(blobs)
+    images = (_lib.LlfeJpegImage * n)()
+    total = C.c_int64(0)
+    ptrs, sizes, status, keep = _blob_table(blobs)
+    _lib.lib().llfe_jpeg_images_layout(ptrs, sizes, n, images, C.byref(total), status,
+                                       int(workers or default_decode_threads()))
+    del keep
+    return images, list(status), int(total.value)
+
+
+def _stage_images(blobs, images, layout_status, workers) -> StagedImages:
+    """llfe_jpeg_read_coefs_images of ``blobs`` into the next staging buffer of the ring, the
+    slots of ``images`` (laid one behind the other here) in it."""
+    from . import _lib
+
+    n, total = len(blobs), 0
+    for m in images:
+        m.slot_offset = total
+        total += m.slot_bytes
+    slots, tensor = _ring("images", 1, _stage_bucket(total), lambda n: ())
+    descs = (_lib.LlfeJpegDesc * n)()
+    status = [-5] * n  # (LLFE_ERR_UNSUPPORTED: nothing staged)
+    if total:
+        ptrs, sizes, st, keep = _blob_table(blobs)
+        _lib.lib().llfe_jpeg_read_coefs_images(ptrs, sizes, n, images, slots.ctypes.data, total, descs, st,
+                                               int(workers or default_decode_threads()))
+        del keep
+        status = list(st)
+    status = [a if a != 0 else b for a, b in zip(layout_status, status)]
+    return StagedImages(blobs, images, descs, list(layout_status), status, slots[0], total, tensor)
+
+
+def stage_coefs_images(blobs, workers=None) -> StagedImages:
+    """The host half of decode_images_device for one staging buffer: the headers of every blob
+    (images_layout), then the entropy decode of every eligible JPEG, whatever its size and
+    sampling class, into tight slots in the next staging buffer of a ring of three, keyed by a
+    bucket of the total bytes.  Host only.  An image this path does not take has a non-zero
+    status and slot_bytes 0."""
+    blobs = [bytes(b) for b in blobs]
+    images, layout_status, _ = images_layout(blobs, workers)
+    return _stage_images(blobs, images, layout_status, workers)
+
+
+def _decode_or_error(b):
+    try:
+        return decode_bgr(b)
+    except DecodeError as e:
+        return e
+
+
+def _run_images(blobs, images, layout_status, chunks, first, device, workers) -> list:
+    """decode_images_device after the header stage: ``chunks`` (lists of image indices, in order,
+    together all of them) are staged and reconstructed one after the other into one packed
+    tensor; ``first`` is chunk 0 already staged."""
+    import torch
+
+    from . import _lib
+    from .backend import Backend
+
+    n = len(blobs)
+    dev = _device(device)
+    pool = _pool(workers)
+    # what the host decoders take is known after the header stage and chunk 0's extraction; the
+    # output is laid out once those are decoded: such an image has the decoded array's size, not
+    # the header's (an EXIF orientation 5..8 swaps height and width)
+    known = {i for i in range(n) if layout_status[i] != 0 or images[i].slot_bytes == 0}
+    known |= {i for k, i in enumerate(chunks[0]) if first.status[k] != 0}
+    order = sorted(known)
+    host = dict(zip(order, pool.map(_decode_or_error, [blobs[i] for i in order])))
+    shape, offset, total = [], [], 0
+    for i in range(n):
+        r = host.get(i)
+        hw = (0, 0) if isinstance(r, Exception) else r.shape[:2] if r is not None else (images[i].height, images[i].width)
+        shape.append(hw)
+        offset.append(total)
+        total = (total + hw[0] * hw[1] * 3 + 15) & ~15
+    packed = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+
+    def place(i):
+        return packed[offset[i]: offset[i] + shape[i][0] * shape[i][1] * 3].view(shape[i][0], shape[i][1], 3)
+
+    out = [host[i] if isinstance(host.get(i), Exception) else place(i) for i in range(n)]
+    for k, idx in enumerate(chunks):
+        if k == 0:
+            st = first
+        else:
+            sub = (_lib.LlfeJpegImage * len(idx))(*[_lib.LlfeJpegImage.from_buffer_copy(images[i]) for i in idx])
+            st = _stage_images([blobs[i] for i in idx], sub, [layout_status[i] for i in idx], workers)
+        for m, i in zip(st.images, idx):
+            m.out_offset = offset[i]
+        if any(rc == 0 for rc in st.status):
+            src = st.tensor[0] if st.tensor is not None else torch.from_numpy(st.slots)
+            with torch.cuda.device(dev):  # the staged prefix in one copy: the slots are tight
+                coefs = torch.empty(st.used_bytes, dtype=torch.uint8, device=dev)
+                coefs.copy_(src[:st.used_bytes], non_blocking=True)
+                Backend.get(dev.index).jpeg_reconstruct_images(coefs, st.images, st.descs, packed)
+        # a later chunk's extraction handed an image back: its place is laid out by its header
+        late = [i for j, i in enumerate(idx) if st.status[j] != 0 and i not in known]
+        for i, r in zip(late, pool.map(_decode_or_error, [blobs[i] for i in late])):
+            if isinstance(r, Exception):
+                out[i] = r
+            elif r.shape[:2] == shape[i]:
+                host[i] = r
+            else:  # (no file does this: its own tensor)
+                out[i] = torch.from_numpy(r).to(dev)
+    for i, r in host.items():
+        if not isinstance(r, Exception):
+            out[i].copy_(torch.from_numpy(r))
+    return out
+
+
+def reconstruct_staged_images(st: StagedImages, device=0, workers=None) -> list:
+    """The device half of a StagedImages: the staged coefficients across in one copy, one
+    llfe_jpeg_reconstruct_images launch on the current stream, and for every image with a
+    non-zero status decode_bgr on the decode pool, copied into its place.  -> a list in input
+    order: H x W x 3 uint8 device tensors (views into one packed tensor, each starting at a
+    multiple of 16), a DecodeError instance in the place of an image nothing decodes."""
+    if not st.blobs:
+        return []
+    return _run_images(st.blobs, st.images, st.layout_status, [list(range(len(st.blobs)))], st, device, workers)
+
+
+def decode_images_device(blobs, device=0, workers=None) -> list:
+    """decode_many with the JPEG reconstruction on the GPU, for images of any sizes: -> a list in
+    input order of H x W x 3 BGR uint8 device tensors, the same bytes decode_bgr returns, each a
+    view into one packed tensor and starting at a multiple of 16; a DecodeError instance stands
+    in the place of an image that cannot be decoded at all (decode_many's convention).  Eligible
+    JPEGs (what decode_batch_device takes) are entropy-decoded on ``workers`` host threads into
+    tight slots and reconstructed by csrc/jpeg_images.hip in one launch; every other image (PNG,
+    CMYK, EXIF-rotated, other samplings, truncated files) goes through decode_bgr on the decode
+    pool and is copied into its place, with the size of the decoded array.  Staging is bounded
+    (LLFE_JPEG_STAGE_BYTES, default 1 GiB): a batch above it is staged and reconstructed in
+    chunks of whole images into the one packed tensor, and an image that alone exceeds it takes
+    the host decoder.  The result feeds Backend.process_images, Backend.thumbnail_pil_images and
+    MicroBatcher.submit unchanged."""
+    from . import _lib
+
+    blobs = [bytes(b) for b in blobs]
+    if not blobs:
+        return []
+    images, layout_status, _ = images_layout(blobs, workers)
+    cap, chunks, room = _stage_cap(), [[]], 0
+    for i, m in enumerate(images):
+        if m.slot_bytes > cap:
+            m.slot_bytes = 0  # (the host decoder's)
+        if chunks[-1] and room + m.slot_bytes > cap:
+            chunks.append([])
+            room = 0
+        chunks[-1].append(i)
+        room += m.slot_bytes
+    sub = (_lib.LlfeJpegImage * len(chunks[0]))(*[_lib.LlfeJpegImage.from_buffer_copy(images[i]) for i in chunks[0]])
+    first = _stage_images([blobs[i] for i in chunks[0]], sub, [layout_status[i] for i in chunks[0]], workers)
+    return _run_images(blobs, images, layout_status, chunks, first, device, workers)
 
 
 # ------------------------------------------------------------ JPEG entropy decode on the device

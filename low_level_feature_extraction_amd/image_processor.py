@@ -41,7 +41,8 @@ class ImageProcessor:
             raise ValueError(f"Image processing error: {str(e)}")
 
     @staticmethod
-    def auto_process_images(images_bytes, max_width: int = 1920, max_height: int = 1080, device: bool = False) -> list:
+    def auto_process_images(images_bytes, max_width: int = 1920, max_height: int = 1080, device: bool = False,
+                            decode: str = "host") -> list:
         """Batched auto_process_image: host decode on the decode pool, then one GPU
         thumbnail launch sequence per group of equally sized images
         (llfe_thumbnail_pil_batch).  Returns arrays in input order; an input that fails
@@ -50,11 +51,23 @@ class ImageProcessor:
         ``device=True``: every decoded image, whatever its size, goes through one
         llfe_thumbnail_pil_images call, and the results are device tensors (views into one
         packed tensor), which Backend.process / submit and MicroBatcher.submit take as they
-        are; the bytes are those of the default route."""
-        from .backend import Backend, thumbnail_size
-        from .decode import decode_many
+        are; the bytes are those of the default route.
 
-        decoded = decode_many(list(images_bytes))
+        ``decode="device"`` (with ``device=True`` only): the uploads, whatever their sizes, are
+        decoded by decode.decode_images_device -- the JPEG reconstruction runs on the GPU in one
+        launch and the pixels never cross PCIe -- and the thumbnail call reads the device tensors
+        in place; the bytes are again the same.  ``decode="host"`` is the route above."""
+        from .backend import Backend, thumbnail_size
+        from .decode import decode_images_device, decode_many
+
+        if decode not in ("host", "device"):
+            raise ValueError('decode must be "host" or "device"')
+        if decode == "device" and not device:
+            raise ValueError('decode="device" needs device=True')
+        if decode == "device":
+            decoded = decode_images_device(list(images_bytes), Backend.get().device)
+        else:
+            decoded = decode_many(list(images_bytes))
         out: list = [None] * len(decoded)
         if device:
             good = [i for i, im in enumerate(decoded) if not isinstance(im, Exception)]

@@ -1,0 +1,150 @@
+#!/usr/bin/env python
+"""JPEG decode of a batch of uploads into device memory: the mixed-size device path against the
+two routes there were before it (DESIGN.md §3 "JPEG decode of a mixed-size batch"; figures in
+profiles/jpeg_images/).  bench.py is not touched: this tool measures the new entry point beside it.
+
+  A  decode.decode_many (decode_bgr per image on the decode pool) and one upload per image:
+     what ImageProcessor.auto_process_images(device=True) does by default
+  B  group the feed by size, decode.decode_batch_device per group (csrc/jpeg_recon.hip)
+  C  decode.decode_images_device: one staging buffer, one launch (csrc/jpeg_images.hip)
+
+A seeded feed of --images quality-85 4:2:0 JPEGs, one process, one rank, a warm-up of all three
+(which also compares their bytes), then A, B and C alternating for --legs legs each, every leg
+--reps passes over the feed:
+  --feed mixed    the 16 sizes of tools/bench_thumb.py --feed mixed (2000 x 1500 .. 4032 x 3024)
+  --feed uniform  every image 1920 x 1080, where B is at its best
+After the timed legs one profiled pass of B and of C gives the kernel ms (llfe_kernel_stats):
+k_jpeg_idct + k_jpeg_color against k_jpeg_images on the same coefficients.  One JSON line on
+stdout.
+"""
+from __future__ import annotations
+
+import argparse
+import io
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "tools")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import numpy as np  # noqa: E402
+
+
+def make_feed(kind: str, n: int, seed: int):
+    """-> (list of (h, w), list of JPEG blobs): smooth colour fields with some texture, so the
+    files are of a photo's length rather than noise's."""
+    from bench_thumb import feed_sizes
+    from PIL import Image
+
+    from concurrent.futures import ThreadPoolExecutor
+
+    sizes = [(1080, 1920)] * n if kind == "uniform" else feed_sizes("mixed", n, seed)
+
+    def one(i):
+        h, w = sizes[i]
+        rng = np.random.default_rng([seed, i])
+        y, x = np.arange(h, dtype=np.float32)[:, None], np.arange(w, dtype=np.float32)[None, :]
+        f = rng.uniform(0.002, 0.02, (3, 2)).astype(np.float32)
+        img = np.stack([127 + 100 * np.sin(f[c, 0] * x + f[c, 1] * y + i + c) for c in range(3)], axis=-1)
+        img += rng.normal(0, 6, (h, w, 1)).astype(np.float32)
+        b = io.BytesIO()
+        Image.fromarray(np.clip(img, 0, 255).astype(np.uint8)).save(b, "JPEG", quality=85, subsampling=2)
+        return b.getvalue()
+
+    with ThreadPoolExecutor(8) as pool:
+        return sizes, list(pool.map(one, range(n)))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--feed", choices=("mixed", "uniform"), default="mixed")
+    ap.add_argument("--images", type=int, default=64)
+    ap.add_argument("--legs", type=int, default=3)
+    ap.add_argument("--reps", type=int, default=8)
+    ap.add_argument("--seed", type=int, default=0)
+    args = ap.parse_args()
+    if args.legs < 3:
+        ap.error("--legs: at least three legs each")
+
+    import torch
+
+    from low_level_feature_extraction_amd import decode
+    from low_level_feature_extraction_amd.backend import Backend
+
+    if not torch.cuda.is_available():
+        sys.exit("bench_jpeg_mixed: no GPU (this tool measures nothing without one)")
+    be = Backend.get(0)
+    sizes, blobs = make_feed(args.feed, args.images, args.seed)
+
+    def route_a():
+        return [torch.from_numpy(a).cuda() for a in decode.decode_many(blobs)]
+
+    def route_b():
+        groups: dict = {}
+        for i, s in enumerate(sizes):
+            groups.setdefault(s, []).append(i)
+        out = [None] * len(blobs)
+        for idx in groups.values():
+            res = decode.decode_batch_device([blobs[i] for i in idx])
+            for j, i in enumerate(idx):
+                out[i] = res[j]
+        return out
+
+    def route_c():
+        return decode.decode_images_device(blobs)
+
+    routes = {"A": route_a, "B": route_b, "C": route_c}
+    # warm-up: three passes each, so that every buffer of the pinned staging rings of three exists
+    # (allocations, code objects), and the three routes give the same bytes
+    for _ in range(3):
+        ra, rb, rc = route_a(), route_b(), route_c()
+    same = all(torch.equal(a, b) and torch.equal(a, c) for a, b, c in zip(ra, rb, rc))
+    del ra, rb, rc
+
+    def leg(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.reps):
+            fn()
+        torch.cuda.synchronize()
+        return args.reps * len(blobs) / (time.perf_counter() - t0)
+
+    legs = {k: [] for k in routes}
+    for _ in range(args.legs):
+        for k, fn in routes.items():
+            legs[k].append(round(leg(fn), 1))
+
+    def profiled(fn):
+        be.set_profiling(True)
+        try:
+            fn()
+            st = be.kernel_stats()
+        finally:
+            be.set_profiling(False)
+        return {k: {"launches": v["launches"], "ms": round(v["total_ms"], 3)} for k, v in st.items()
+                if k.startswith("k_jpeg")}
+
+    kb, kc = profiled(route_b), profiled(route_c)
+    summary = {k: {"median": statistics.median(v), "min": min(v), "max": max(v)} for k, v in legs.items()}
+    spread = max(summary[k]["max"] - summary[k]["min"] for k in ("A", "B"))
+    out = {
+        "tool": "bench_jpeg_mixed", "feed": args.feed, "images": len(blobs), "distinct_sizes": len(set(sizes)),
+        "megapixels": round(sum(h * w for h, w in sizes) / 1e6, 1), "file_mib": round(sum(map(len, blobs)) / 2**20, 1),
+        "reps_per_leg": args.reps, "same_bytes": same, "decode_threads": decode.default_decode_threads(),
+        "images_per_s": legs, "summary": summary,
+        # a speed claim needs the medians further apart than three times the base routes' spread
+        "C_minus_best_base_median": round(summary["C"]["median"] - max(summary["A"]["median"], summary["B"]["median"]), 1),
+        "three_times_base_spread": round(3 * spread, 1),
+        "kernels_ms_per_pass": {"B": kb, "C": kc},
+        "device": torch.cuda.get_device_name(0),
+    }
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

@@ -3,7 +3,9 @@
 // source file (tests/test_jpeg_coefs_sanitized.py does), it reads the JPEG files named on
 // the command line, extracts each one's coefficients into an exactly sized heap slot -- so
 // a write past the slot, or a read past libjpeg's block rows, is a sanitizer report -- and
-// then the files of the most common size once more as one batch on three threads.
+// then the files of the most common size once more as one batch on three threads, and all
+// files, whatever their sizes, as one ragged batch (llfe_jpeg_read_coefs_images) into tight
+// slots laid out from their headers in one exactly sized buffer.
 // Prints one line per file; exit status 0 when every call returned a documented status.
 #include <algorithm>
 #include <cstdio>
@@ -17,6 +19,7 @@
 #include "llfe.h"
 
 int llfe_jpeg_info_one(const uint8_t *data, size_t size, int32_t *w, int32_t *h, int *ncomp);
+int llfe_jpeg_layout_one(const uint8_t *data, size_t size, int32_t *h, int32_t *w, int64_t *slot_bytes);
 
 static std::vector<uint8_t> slurp(const char *path) {
     std::vector<uint8_t> v;
@@ -35,7 +38,7 @@ static bool documented(int rc) {
 int main(int argc, char **argv) {
     std::vector<std::vector<uint8_t>> files;
     std::map<std::pair<int, int>, std::vector<int>> by_size;
-    int bad = 0;
+    int bad = 0, extracted = 0;
     for (int a = 1; a < argc; a++) {
         files.push_back(slurp(argv[a]));
         const std::vector<uint8_t> &f = files.back();
@@ -59,6 +62,7 @@ int main(int argc, char **argv) {
         printf("%s: %dx%d status %d components %d class %d extent %lld of %lld\n", argv[a], w, h, st, d.n_comp, d.sampling,
                (long long)end, (long long)stride);
         if (rc != st || !documented(st) || end > stride || (st != LLFE_OK && d.n_comp != 0)) bad++;
+        extracted += st == LLFE_OK;
         // half a slot: a subsampled image still fits, a 4:4:4 one is handed back, nothing overruns
         const int64_t half = (stride / 2 + 15) & ~(int64_t)15;
         std::vector<uint8_t> small((size_t)half);
@@ -87,6 +91,35 @@ int main(int argc, char **argv) {
             if (!documented(st[(size_t)i])) bad++;
         }
         printf("batch of %d at %dx%d on 3 threads: %d extracted\n", n, hw.second, hw.first, ok);
+    }
+    {  // every file in one ragged batch: the same files are extracted, none past its tight slot
+        const int n = (int)files.size();
+        std::vector<llfe_jpeg_image> images((size_t)n);
+        std::vector<const uint8_t *> ptrs;
+        std::vector<uint64_t> sizes;
+        int64_t total = 0;
+        for (int i = 0; i < n; i++) {
+            const std::vector<uint8_t> &f = files[(size_t)i];
+            llfe_jpeg_image &m = images[(size_t)i];
+            memset(&m, 0, sizeof m);
+            if (!documented(llfe_jpeg_layout_one(f.data(), f.size(), &m.height, &m.width, &m.slot_bytes))) bad++;
+            m.slot_offset = total;
+            total += m.slot_bytes;
+            ptrs.push_back(f.data());
+            sizes.push_back(f.size());
+        }
+        std::vector<uint8_t> slots((size_t)total);
+        std::vector<llfe_jpeg_desc> descs((size_t)n);
+        std::vector<int32_t> st((size_t)n, 1);
+        llfe_jpeg_read_coefs_images(ptrs.data(), sizes.data(), n, images.data(), slots.data(), total, descs.data(),
+                                    st.data(), 3);
+        int ok = 0;
+        for (int i = 0; i < n; i++) {
+            ok += st[(size_t)i] == LLFE_OK;
+            if (!documented(st[(size_t)i]) || (st[(size_t)i] != LLFE_OK && descs[(size_t)i].n_comp != 0)) bad++;
+        }
+        printf("ragged batch of %d on 3 threads: %d extracted into %lld bytes\n", n, ok, (long long)total);
+        if (ok != extracted) bad++;
     }
     printf("%s\n", bad ? "FAILED" : "ok");
     return bad ? 1 : 0;
