@@ -683,6 +683,49 @@ int llfe_jpeg_entropy_decode(llfe_ctx *ctx, const uint8_t *staging, int64_t stag
                              const llfe_jpeg_desc *descs, int32_t n, int32_t h, int32_t w, uint8_t *slots,
                              int64_t slot_stride, int32_t *status_out, llfe_stream stream);
 
+/* ---- the device entropy decode for a batch whose images each have their own size (opt-in): the
+ * records lie one behind the other in one staging buffer, each as long as its file needs, and
+ * csrc/jpeg_huff.hip writes the tight slots llfe_jpeg_read_coefs_images writes, for
+ * llfe_jpeg_reconstruct_images to run on unchanged. */
+/* host only, no ctx: where the records go.  For every image whose images[i].slot_bytes != 0 (as
+ * llfe_jpeg_images_layout left it) record_offsets[i] is the running sum and the record takes
+ * LLFE_JPEG_RECORD_HEADER + sizes[i] rounded up to 16 + 16 bytes; the other images take no room
+ * (their offset is the running sum too).  *staging_bytes receives the total.  Returns LLFE_OK, or
+ * LLFE_ERR_INVALID for a NULL argument or a negative n. */
+int llfe_jpeg_records_layout(const uint64_t *sizes, const llfe_jpeg_image *images, int32_t n, int64_t *record_offsets,
+                             int64_t *staging_bytes);
+/* host only, no ctx: llfe_jpeg_parse_batch_flags with each image's own height, width and
+ * slot_bytes (images[i]) and its record at record_offsets[i] in staging (host, staging_bytes
+ * bytes).  The llfe_jpeg_desc offsets are relative to the image's tight slot: byte for byte the
+ * descriptor llfe_jpeg_read_coefs_images produces for the file.  The same eligibility rules and
+ * the same flags.  status[i] as llfe_jpeg_parse_batch's: a file that does not fit its slot_bytes
+ * is LLFE_ERR_UNSUPPORTED, another size than its record says LLFE_ERR_CAPACITY; slot_bytes == 0
+ * is LLFE_ERR_UNSUPPORTED and nothing is read.  A record (as llfe_jpeg_records_layout sizes it)
+ * outside staging_bytes, or one not 16-byte aligned, is LLFE_ERR_INVALID for the whole call,
+ * before any parse.  Returns the first non-OK status. */
+int llfe_jpeg_parse_images(const uint8_t *const *data, const uint64_t *sizes, int32_t n, const llfe_jpeg_image *images,
+                           const int64_t *record_offsets, uint8_t *staging, int64_t staging_bytes,
+                           llfe_jpeg_desc *descs, llfe_jpeg_scan *scans, int32_t *status, int32_t threads,
+                           uint32_t flags);
+/* host only: llfe_jpeg_entropy_reference over tight slots (slots on the host, slots_bytes bytes,
+ * image i at images[i].slot_offset); the validation of llfe_jpeg_entropy_decode_images. */
+int llfe_jpeg_entropy_reference_images(const uint8_t *staging, int64_t staging_bytes, const llfe_jpeg_scan *scans,
+                                       const llfe_jpeg_desc *descs, const llfe_jpeg_image *images, int32_t n,
+                                       uint8_t *slots, int64_t slots_bytes, int32_t *status, int32_t one_piece);
+/* the device half: staging (device, staging_bytes, 16-byte aligned, as parsed above) -> slots
+ * (device, slots_bytes, 16-byte aligned).  scans, descs and images are host arrays, validated on
+ * the host before anything is launched; for every image with blocks_in_mcu != 0: its descriptor
+ * against its own height x width and slot_bytes, its slot 16-byte aligned, inside slots_bytes and
+ * apart from every other such image's, its record as llfe_jpeg_entropy_decode checks one.  A bad
+ * record is LLFE_ERR_INVALID with the slots untouched; more than 2^31 subsequences or blocks in
+ * one call is LLFE_ERR_CAPACITY.  status_out as llfe_jpeg_entropy_decode's; for an image the
+ * device does not take the slot may hold anything, but only its own slot.  Runs on `stream` and
+ * returns when it has finished. */
+int llfe_jpeg_entropy_decode_images(llfe_ctx *ctx, const uint8_t *staging, int64_t staging_bytes,
+                                    const llfe_jpeg_scan *scans, const llfe_jpeg_desc *descs,
+                                    const llfe_jpeg_image *images, int32_t n, uint8_t *slots, int64_t slots_bytes,
+                                    int32_t *status_out, llfe_stream stream);
+
 /* ---- PNG decode on the device (opt-in; llfe_decode_batch is unchanged): 8-bit RGB / RGBA,
  * not interlaced.  The host only walks the chunks; the file's deflate stream crosses to the
  * device instead of its pixels, and csrc/png_inflate.hip inflates, checks the Adler-32, undoes

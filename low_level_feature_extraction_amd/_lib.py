@@ -293,6 +293,13 @@ SIGNATURES = {
                                               _i32, _vp, _i64, _vp, _i32]),
     "llfe_jpeg_entropy_decode": (C.c_int, [_vp, _vp, _i64, C.POINTER(LlfeJpegScan), C.POINTER(LlfeJpegDesc), _i32, _i32,
                                            _i32, _vp, _i64, _vp, _vp]),
+    "llfe_jpeg_records_layout": (C.c_int, [_vp, C.POINTER(LlfeJpegImage), _i32, _vp, C.POINTER(_i64)]),
+    "llfe_jpeg_parse_images": (C.c_int, [_vp, _vp, _i32, C.POINTER(LlfeJpegImage), _vp, _vp, _i64,
+                                         C.POINTER(LlfeJpegDesc), C.POINTER(LlfeJpegScan), _vp, _i32, _u32]),
+    "llfe_jpeg_entropy_reference_images": (C.c_int, [_vp, _i64, C.POINTER(LlfeJpegScan), C.POINTER(LlfeJpegDesc),
+                                                     C.POINTER(LlfeJpegImage), _i32, _vp, _i64, _vp, _i32]),
+    "llfe_jpeg_entropy_decode_images": (C.c_int, [_vp, _vp, _i64, C.POINTER(LlfeJpegScan), C.POINTER(LlfeJpegDesc),
+                                                  C.POINTER(LlfeJpegImage), _i32, _vp, _i64, _vp, _vp]),
     "llfe_png_parse_batch": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _i64, C.POINTER(LlfePngDesc), _vp, _i32]),
     "llfe_png_decode_reference": (C.c_int, [_vp, _i64, C.POINTER(LlfePngDesc), _i32, _i32, _i32, _vp, _i64, _vp, _vp]),
     "llfe_png_decode_device": (C.c_int, [_vp, _vp, _i64, C.POINTER(LlfePngDesc), _i32, _i32, _i32, _vp, _i64, _vp, _vp,

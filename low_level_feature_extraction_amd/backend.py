@@ -629,6 +629,33 @@ class Backend:
                    slots.data_ptr(), stride, status, self._stream(slots))
         return list(status)
 
+    def jpeg_entropy_decode_images(self, records, scans, descs, images, slots) -> list:
+        """The entropy half of a JPEG decode of images of any sizes on the device
+        (llfe_jpeg_entropy_decode_images): ``records`` a 1-d uint8 device tensor of staged records,
+        ``scans`` / ``descs`` / ``images`` the n llfe_jpeg_scan / llfe_jpeg_desc / llfe_jpeg_image
+        records (decode.stage_bytes_images), ``slots`` a 1-d uint8 device tensor that receives
+        every image's quantisation tables and coefficients in its tight slot, as
+        decode.stage_coefs_images lays them out, on the current stream.  -> the per-image status
+        list: 0 for a slot that is ready for jpeg_reconstruct_images, LLFE_ERR_UNSUPPORTED for an
+        image that was not staged or whose scan showed an anomaly (decode it another way).  A
+        record or descriptor that points outside its buffer, or a slot that lies outside ``slots``
+        or in another image's, raises LlfeError (LLFE_ERR_INVALID) before any launch."""
+        torch = _torch()
+        for name, t in (("records", records), ("slots", slots)):
+            if not (_is_torch(t) and t.is_cuda and t.dtype == torch.uint8 and t.dim() == 1 and t.is_contiguous()):
+                raise ValueError(f"jpeg_entropy_decode_images: {name} must be a contiguous 1-d uint8 device tensor")
+        if slots.device.index != self.device or records.device != slots.device:
+            raise ValueError(f"jpeg_entropy_decode_images: records on {records.device}, slots on {slots.device}, "
+                             f"context on cuda:{self.device}")
+        n = len(images)
+        if len(scans) != n or len(descs) != n:
+            raise ValueError(f"jpeg_entropy_decode_images: {len(scans)} scan records and {len(descs)} descriptors for "
+                             f"{n} image records")
+        status = (C.c_int32 * n)()
+        self._call("llfe_jpeg_entropy_decode_images", records.data_ptr(), records.numel(), scans, descs, images, n,
+                   slots.data_ptr(), slots.numel(), status, self._stream(slots))
+        return list(status)
+
     def png_decode(self, records, descs, h: int, w: int, out, raw=None) -> list:
         """PNG decode on the device (llfe_png_decode_device): ``records`` an n x record_stride
         uint8 device tensor of staged deflate streams, ``descs`` the n llfe_png_desc records

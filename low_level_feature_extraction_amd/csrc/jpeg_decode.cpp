@@ -695,6 +695,9 @@ int parse_one(const uint8_t *data, size_t size, int32_t h, int32_t w, uint8_t *r
     return rc;
 }
 
+// the record of a file of `size` bytes in a ragged staging buffer (llfe_jpeg_records_layout)
+inline int64_t record_bytes(uint64_t size) { return LLFE_JPEG_RECORD_HEADER + (((int64_t)size + 15) & ~(int64_t)15) + 16; }
+
 // One image of llfe_jpeg_entropy_reference: the phases of jpeg_huff.hip, serially.  RST: the
 // record has a restart interval.
 template <bool RST>
@@ -902,6 +905,24 @@ extern "C" int llfe_jpeg_parse_batch(const uint8_t *const *data, const uint64_t 
                                        status, threads, 0);
 }
 
+namespace llfe_jpeg {
+// the twin's loop over validated records; slot_of(i): where image i's slot starts
+template <class SlotOf>
+int reference_all(const uint8_t *staging, const llfe_jpeg_scan *scans, const llfe_jpeg_desc *descs, int n, int32_t *status,
+                  bool one_piece, SlotOf slot_of) {
+    try {
+        for (int i = 0; i < n; i++)
+            status[i] = scans[i].blocks_in_mcu == 0
+                            ? LLFE_ERR_UNSUPPORTED
+                            : (scans[i].restart_interval ? reference_one<true> : reference_one<false>)(
+                                  staging + scans[i].record_offset, scans[i], descs[i], slot_of(i), one_piece);
+    } catch (const std::bad_alloc &) {
+        return LLFE_ERR_OOM;
+    }
+    return LLFE_OK;
+}
+}  // namespace llfe_jpeg
+
 extern "C" int llfe_jpeg_entropy_reference(const uint8_t *staging, int64_t staging_bytes, const llfe_jpeg_scan *scans,
                                            const llfe_jpeg_desc *descs, int32_t n, int32_t h, int32_t w, uint8_t *slots,
                                            int64_t slot_stride, int32_t *status, int32_t one_piece) {
@@ -913,15 +934,80 @@ extern "C" int llfe_jpeg_entropy_reference(const uint8_t *staging, int64_t stagi
     if (!llfe::check_jpeg_descs(descs, n, h, w, slot_stride, &plane_stride, &mb) ||
         !llfe_huff::validate_scans(scans, descs, n, staging_bytes, &max_sub, &max_blocks))
         return LLFE_ERR_INVALID;
+    return llfe_jpeg::reference_all(staging, scans, descs, n, status, one_piece != 0,
+                                    [&](int i) { return slots + (size_t)i * (size_t)slot_stride; });
+}
+
+extern "C" int llfe_jpeg_entropy_reference_images(const uint8_t *staging, int64_t staging_bytes,
+                                                  const llfe_jpeg_scan *scans, const llfe_jpeg_desc *descs,
+                                                  const llfe_jpeg_image *images, int32_t n, uint8_t *slots,
+                                                  int64_t slots_bytes, int32_t *status, int32_t one_piece) {
+    if (n < 0 || (n && (!staging || !scans || !descs || !images || !slots || !status)) || slots_bytes < 0 ||
+        staging_bytes < 0 || ((uintptr_t)staging & 15))
+        return LLFE_ERR_INVALID;
     try {
-        for (int i = 0; i < n; i++)
-            status[i] = scans[i].blocks_in_mcu == 0
-                            ? LLFE_ERR_UNSUPPORTED
-                            : (scans[i].restart_interval ? llfe_jpeg::reference_one<true> : llfe_jpeg::reference_one<false>)(
-                                  staging + scans[i].record_offset, scans[i], descs[i],
-                                  slots + (size_t)i * (size_t)slot_stride, one_piece != 0);
+        if (!llfe_huff::validate_scans_images(scans, descs, images, n, staging_bytes, slots_bytes)) return LLFE_ERR_INVALID;
     } catch (const std::bad_alloc &) {
         return LLFE_ERR_OOM;
     }
+    return llfe_jpeg::reference_all(staging, scans, descs, n, status, one_piece != 0,
+                                    [&](int i) { return slots + images[i].slot_offset; });
+}
+
+extern "C" int llfe_jpeg_records_layout(const uint64_t *sizes, const llfe_jpeg_image *images, int32_t n,
+                                        int64_t *record_offsets, int64_t *staging_bytes) {
+    if (n < 0 || !staging_bytes || (n && (!sizes || !images || !record_offsets))) return LLFE_ERR_INVALID;
+    int64_t total = 0;
+    for (int i = 0; i < n; i++) {
+        record_offsets[i] = total;
+        if (images[i].slot_bytes != 0) total += llfe_jpeg::record_bytes(sizes[i]);
+    }
+    *staging_bytes = total;
+    return LLFE_OK;
+}
+
+extern "C" int llfe_jpeg_parse_images(const uint8_t *const *data, const uint64_t *sizes, int32_t n,
+                                      const llfe_jpeg_image *images, const int64_t *record_offsets, uint8_t *staging,
+                                      int64_t staging_bytes, llfe_jpeg_desc *descs, llfe_jpeg_scan *scans, int32_t *status,
+                                      int32_t threads, uint32_t flags) {
+    if ((flags & ~LLFE_JPEG_PARSE_RESTARTS) || n < 0 ||
+        (n && (!data || !sizes || !images || !record_offsets || !staging || !descs || !scans || !status)) ||
+        staging_bytes < 0)
+        return LLFE_ERR_INVALID;
+    for (int i = 0; i < n; i++) {  // every record inside the buffer, before the first byte is written
+        if (images[i].slot_bytes == 0) continue;
+        const int64_t off = record_offsets[i];
+        if (sizes[i] >= ((uint64_t)1 << 40) || off < 0 || (off & 15) || off > staging_bytes ||
+            llfe_jpeg::record_bytes(sizes[i]) > staging_bytes - off)
+            return LLFE_ERR_INVALID;
+    }
+    const int nt = std::max(1, std::min<int>(threads > 0 ? threads : 1, n));
+    std::atomic<int> next{0};
+    auto work = [&]() {
+        for (int i; (i = next.fetch_add(1)) < n;) {
+            const llfe_jpeg_image &m = images[i];
+            int rc;
+            memset(&descs[i], 0, sizeof descs[i]);  // n_comp 0, blocks_in_mcu 0: nothing staged for this image
+            memset(&scans[i], 0, sizeof scans[i]);
+            try {
+                rc = m.slot_bytes == 0 ? LLFE_ERR_UNSUPPORTED
+                     : !data[i]        ? LLFE_ERR_INVALID
+                     : m.height <= 0 || m.width <= 0 || m.height > 65535 || m.width > 65535
+                         ? LLFE_ERR_CAPACITY  // (no JPEG has that size)
+                         : llfe_jpeg::parse_one(data[i], (size_t)sizes[i], m.height, m.width, staging + record_offsets[i],
+                                                record_offsets[i], llfe_jpeg::record_bytes(sizes[i]), m.slot_bytes,
+                                                &descs[i], &scans[i], (flags & LLFE_JPEG_PARSE_RESTARTS) != 0);
+            } catch (const std::bad_alloc &) {
+                rc = LLFE_ERR_OOM;
+            }
+            status[i] = rc;
+        }
+    };
+    std::vector<std::thread> th;
+    for (int t = 1; t < nt; t++) th.emplace_back(work);
+    work();
+    for (auto &t : th) t.join();
+    for (int i = 0; i < n; i++)
+        if (status[i]) return status[i];
     return LLFE_OK;
 }

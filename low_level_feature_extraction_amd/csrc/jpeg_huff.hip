@@ -34,18 +34,38 @@
 //   k_huff_dc      one workgroup per image: per-component prefix sums over the DC differences
 //                  of all blocks in scan order, scattered to the real blocks.
 // Restart intervals.  Every kernel behind k_huff_init exists twice, <RST = false> for the images
-// whose record has restart_interval 0 and <true> for the others; each instance skips the other's
-// images, and the host launches an instance only when the batch has images for it, so a batch
-// without restart intervals runs the launches and the code it always ran.  With RST the lanes
+// whose record has restart_interval 0 and <true> for the others; each instance is launched on
+// the records and the work table of its own images, and only when the batch has such images, so
+// a batch without restart intervals runs the launches and the code it always ran.  With RST the lanes
 // cross markers (jpeg_huff_core.h) and keep, next to the block count, the Marks of their last
 // decode; k_huff_verify scans the marker counts along with the block counts and accepts an
 // image only if no lane's Marks are bad, the first marker of every lane is the one its ordinal k
 // asks for (FF D0 + (k & 7), behind exactly (k + 1) * Ri * blocks_in_mcu blocks) and the markers
 // are (MCUs - 1) / Ri in all; the later markers of a lane are checked against its first one by
 // the decode itself.  k_huff_dc restarts its sums at every interval (a segmented scan).
-// Everything an image's lanes write lies in its own slot and its own rows of the workspace.
+// Images of any sizes.  Nothing here assumes one size per batch: every image the host takes has a
+// HuffImage record (llfe_internal.h) with the offset of its slot in the coefficient buffer and
+// its first lane, first workgroup and first DC difference in the workspace -- prefix sums of the
+// subsequence counts, the workgroup counts and the block counts (padding blocks included) over
+// the call's images, so the workspace holds the sums, not images x the longest scan.  The lane
+// kernels (k_huff_sync, k_huff_write) run over a work table of (record, workgroup of that image)
+// entries, as k_jpeg_images runs over (image, tile) entries; k_huff_verify and k_huff_dc take one
+// workgroup per record.  The records of the images without a restart interval come first and each
+// kind has its own work table, so an instance is launched on its own images only.
+// llfe_jpeg_entropy_decode (one size, slot i at i x slot_stride) and
+// llfe_jpeg_entropy_decode_images (tight slots) build the same records and tables.
+// Only the undecided suffix is launched.  After pass p workgroup p of an image is final (above),
+// and the number of passes is the largest workgroup count of any image, so in a batch of mixed
+// sizes most entries are final long before the last pass.  The work table is ordered by workgroup
+// index (then record), and pass p launches only the entries with g >= p.  This is sound with the
+// double-buffered boundary array: an entry g launched in pass p reads, in buffer p & 1, what
+// g - 1 wrote in pass p - 1, and g - 1 >= p - 1 was launched then; an entry g < p is not launched
+// and its lanes' states and the boundary it wrote in pass g stay as they are, which is what entry
+// g + 1 read in pass g + 1, its last.
+// Everything an image's lanes write lies in its own slot and its own part of the workspace.
 // Every index derives from records and descriptors the host validated (validate_scans,
-// validate_jpeg_descs); every loop has a bound that follows from the scan length.
+// check_jpeg_desc) or from records the host built from them; every loop has a bound that follows
+// from the scan length.
 #include "jpeg_huff_core.h"
 #include "llfe_internal.h"
 
@@ -54,34 +74,32 @@ namespace {
 
 using namespace llfe_huff;
 
-constexpr int HT = 256;  // lanes (subsequences) per workgroup
+constexpr int HT = kJpegHuffLanes;  // lanes (subsequences) per workgroup
 
 __constant__ uint8_t c_nat[64] = {LLFE_JPEG_NATURAL_ORDER};
 
 struct Ws {
-    State *in, *out;  // n x max_sub
-    int *cnt, *first;  // n x max_sub
-    State *bnd;        // 2 x n x max_wg: the last exit state of each workgroup, double-buffered
-    int16_t *dcd;      // n x max_blocks
-    Marks *marks;      // n x max_sub (RST)
-    int max_sub, max_wg, max_blocks;
+    State *in, *out;   // per lane
+    int *cnt, *first;  // per lane
+    State *bnd;        // 2 x wgs: the last exit state of each workgroup, double-buffered
+    int16_t *dcd;      // per block
+    Marks *marks;      // per lane (RST)
+    int wgs;
 };
 
 inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 
-Ws carve(uint8_t *base, int n, int max_sub, int max_blocks, size_t *bytes) {
+// the workspace of a call: the sums of its images' lanes, workgroups and blocks
+Ws carve(uint8_t *base, size_t lanes, size_t wgs, size_t blocks, size_t *bytes) {
     Ws w;
-    w.max_sub = max_sub;
-    w.max_wg = (max_sub + HT - 1) / HT;
-    w.max_blocks = max_blocks;
+    w.wgs = (int)wgs;
     size_t o = 0;
-    const size_t lanes = (size_t)n * (size_t)max_sub;
     w.in = (State *)(base + o), o += up16(lanes * sizeof(State));
     w.out = (State *)(base + o), o += up16(lanes * sizeof(State));
     w.cnt = (int *)(base + o), o += up16(lanes * sizeof(int));
     w.first = (int *)(base + o), o += up16(lanes * sizeof(int));
-    w.bnd = (State *)(base + o), o += up16(2 * (size_t)n * (size_t)w.max_wg * sizeof(State));
-    w.dcd = (int16_t *)(base + o), o += up16((size_t)n * (size_t)max_blocks * sizeof(int16_t));
+    w.bnd = (State *)(base + o), o += up16(2 * wgs * sizeof(State));
+    w.dcd = (int16_t *)(base + o), o += up16(blocks * sizeof(int16_t));
     w.marks = (Marks *)(base + o), o += up16(lanes * sizeof(Marks));
     *bytes = o;
     return w;
@@ -114,21 +132,22 @@ __device__ __forceinline__ void load_shared(Shared &S, const uint8_t *staging, c
 __global__ __launch_bounds__(HT) void k_huff_init(const uint8_t *__restrict__ staging,
                                                   const llfe_jpeg_scan *__restrict__ scans,
                                                   const llfe_jpeg_desc *__restrict__ descs, uint8_t *__restrict__ slots,
-                                                  int64_t slot_stride) {
-    const int img = blockIdx.y;
-    const llfe_jpeg_scan &sc = scans[img];
-    if (sc.blocks_in_mcu == 0) return;
-    const llfe_jpeg_desc &d = descs[img];
-    uint8_t *slot = slots + (int64_t)img * slot_stride;
+                                                  const HuffImage *__restrict__ recs, int per_image) {
+    // per_image workgroups for every record
+    const HuffImage &im = recs[blockIdx.x / per_image];
+    const int bx = blockIdx.x % per_image;
+    const llfe_jpeg_scan &sc = scans[im.img];
+    const llfe_jpeg_desc &d = descs[im.img];
+    uint8_t *slot = slots + im.slot_offset;
     const uint8_t *rec = staging + sc.record_offset;
-    if (blockIdx.x == 0 && (int)threadIdx.x < d.n_comp * 8) {
+    if (bx == 0 && (int)threadIdx.x < d.n_comp * 8) {
         const int c = threadIdx.x >> 3, j = threadIdx.x & 7;
         *(uint4 *)(slot + d.comp[c].quant_offset + j * 16) = *(const uint4 *)(rec + sc.quant_offset + c * 128 + j * 16);
     }
     for (int c = 0; c < d.n_comp; c++) {
         const int64_t vecs = (int64_t)d.comp[c].blocks_w * d.comp[c].blocks_h * 8;  // 16-byte stores
         uint4 *dst = (uint4 *)(slot + d.comp[c].coef_offset);
-        for (int64_t k = (int64_t)blockIdx.x * HT + threadIdx.x; k < vecs; k += (int64_t)gridDim.x * HT)
+        for (int64_t k = (int64_t)bx * HT + threadIdx.x; k < vecs; k += (int64_t)per_image * HT)
             dst[k] = make_uint4(0, 0, 0, 0);
     }
 }
@@ -136,12 +155,14 @@ __global__ __launch_bounds__(HT) void k_huff_init(const uint8_t *__restrict__ st
 template <bool RST>
 __global__ __launch_bounds__(HT) void k_huff_sync(const uint8_t *__restrict__ staging,
                                                   const llfe_jpeg_scan *__restrict__ scans,
-                                                  const llfe_jpeg_desc *__restrict__ descs, const int *__restrict__ status,
-                                                  Ws w, int n, int pass) {
+                                                  const llfe_jpeg_desc *__restrict__ descs,
+                                                  const HuffImage *__restrict__ recs,
+                                                  const HuffWork *__restrict__ work, Ws w, int pass) {
     __shared__ Shared S;
     __shared__ State lds_out[HT];
-    const int img = blockIdx.y, g = blockIdx.x, t = threadIdx.x;
-    if (status[img] != 0 || (scans[img].restart_interval != 0) != RST) return;  // (whole workgroup)
+    const HuffWork wk = work[blockIdx.x];  // (the entries of this kind with g >= pass)
+    const HuffImage &im = recs[wk.rec];
+    const int img = im.img, g = wk.g, t = threadIdx.x;
     const int len = scans[img].scan_bytes, nsub = subsequences(len);
     if (g * HT >= nsub) return;  // (whole workgroup)
     load_shared(S, staging, &scans[img], &descs[img]);
@@ -151,7 +172,8 @@ __global__ __launch_bounds__(HT) void k_huff_sync(const uint8_t *__restrict__ st
     const uint8_t *scan = staging + sc.record_offset + sc.scan_offset;
     const int i = g * HT + t;
     const bool act = i < nsub;
-    const int64_t lane = (int64_t)img * w.max_sub + i;
+    const int64_t lane = (int64_t)im.lane0 + i;
+    const int64_t wg = (int64_t)im.wg0 + g;
     const int end = min(len, (i + 1) * kSub);
     const State start{0, 0}, none{kNone, 0};
     const Geometry geo{&sc, &S.d, nullptr};
@@ -171,7 +193,7 @@ __global__ __launch_bounds__(HT) void k_huff_sync(const uint8_t *__restrict__ st
     }
     // the exit state in front of this workgroup: what its predecessor left in the last launch
     State before = g == 0 ? start : none;
-    if (g > 0 && pass > 0) before = w.bnd[((int64_t)(pass & 1) * n + img) * w.max_wg + g - 1];
+    if (g > 0 && pass > 0) before = w.bnd[(int64_t)(pass & 1) * w.wgs + wg - 1];
     for (int r = 0; r < HT; r++) {
         lds_out[t] = out;
         __syncthreads();
@@ -188,21 +210,21 @@ __global__ __launch_bounds__(HT) void k_huff_sync(const uint8_t *__restrict__ st
         w.out[lane] = out;
         w.cnt[lane] = cnt;
         if (RST) w.marks[lane] = mk;
-        if (t == HT - 1 || i == nsub - 1) w.bnd[((int64_t)((pass + 1) & 1) * n + img) * w.max_wg + g] = out;
+        if (t == HT - 1 || i == nsub - 1) w.bnd[(int64_t)((pass + 1) & 1) * w.wgs + wg] = out;
     }
 }
 
 template <bool RST>
 __global__ __launch_bounds__(HT) void k_huff_verify(const llfe_jpeg_scan *__restrict__ scans, int *__restrict__ status,
-                                                    Ws w) {
+                                                    const HuffImage *__restrict__ recs, Ws w) {
     __shared__ int s_scan[HT];
     __shared__ int s_mark[RST ? HT : 1];
-    const int img = blockIdx.x, t = threadIdx.x;
-    if (status[img] != 0 || (scans[img].restart_interval != 0) != RST) return;  // (whole workgroup)
+    const HuffImage &im = recs[blockIdx.x];  // (the records of this kind)
+    const int img = im.img, t = threadIdx.x;
     const llfe_jpeg_scan &sc = scans[img];
     const int len = sc.scan_bytes, nsub = subsequences(len);
     const int total = sc.mcus_w * sc.mcus_h * sc.blocks_in_mcu;
-    const int64_t row = (int64_t)img * w.max_sub;
+    const int64_t row = im.lane0;
     int bad = 0, carry = 0, mcarry = 0;  // mcarry: the markers in front of this round's lanes
     for (int base = 0; base < nsub; base += HT) {
         const int i = base + t;
@@ -250,10 +272,13 @@ template <bool RST>
 __global__ __launch_bounds__(HT) void k_huff_write(const uint8_t *__restrict__ staging,
                                                    const llfe_jpeg_scan *__restrict__ scans,
                                                    const llfe_jpeg_desc *__restrict__ descs, const int *__restrict__ status,
-                                                   uint8_t *__restrict__ slots, int64_t slot_stride, Ws w) {
+                                                   uint8_t *__restrict__ slots, const HuffImage *__restrict__ recs,
+                                                   const HuffWork *__restrict__ work, Ws w) {
     __shared__ Shared S;
-    const int img = blockIdx.y, g = blockIdx.x, t = threadIdx.x;
-    if (status[img] != 0 || (scans[img].restart_interval != 0) != RST) return;  // (whole workgroup)
+    const HuffWork wk = work[blockIdx.x];  // (every entry of this kind)
+    const HuffImage &im = recs[wk.rec];
+    const int img = im.img, g = wk.g, t = threadIdx.x;
+    if (status[img] != 0) return;  // (whole workgroup) the verification refused the image
     const int len = scans[img].scan_bytes, nsub = subsequences(len);
     if (g * HT >= nsub) return;  // (whole workgroup)
     load_shared(S, staging, &scans[img], &descs[img]);
@@ -263,30 +288,31 @@ __global__ __launch_bounds__(HT) void k_huff_write(const uint8_t *__restrict__ s
     const uint8_t *rec = staging + sc.record_offset;
     const int i = g * HT + t;
     if (i >= nsub) return;
-    const Geometry geo{&sc, &S.d, slots + (int64_t)img * slot_stride};
-    const int64_t lane = (int64_t)img * w.max_sub + i;
+    const Geometry geo{&sc, &S.d, slots + im.slot_offset};
+    const int64_t lane = (int64_t)im.lane0 + i;
     const int total = sc.mcus_w * sc.mcus_h * sc.blocks_in_mcu;
     const int first = w.first[lane];
     if (first < 0 || first >= total) return;
     int cnt = 0;
     decode_sub<true, RST>(rec + sc.scan_offset, len, tabs, sc, w.in[lane], min(len, (i + 1) * kSub), &cnt, nat, geo,
-                          w.dcd + (int64_t)img * w.max_blocks, first, total, nullptr);
+                          w.dcd + im.dcd0, first, total, nullptr);
 }
 
 template <bool RST>
 __global__ __launch_bounds__(HT) void k_huff_dc(const uint8_t *__restrict__ staging,
                                                 const llfe_jpeg_scan *__restrict__ scans,
                                                 const llfe_jpeg_desc *__restrict__ descs, const int *__restrict__ status,
-                                                uint8_t *__restrict__ slots, int64_t slot_stride, Ws w) {
+                                                uint8_t *__restrict__ slots, const HuffImage *__restrict__ recs, Ws w) {
     __shared__ int s_sum[3][HT];
     __shared__ int s_cut[RST ? HT : 1];  // RST: a sum restarted in or in front of this lane's MCUs
     __shared__ Shared S;
-    const int img = blockIdx.x, t = threadIdx.x;
-    if (status[img] != 0 || (scans[img].restart_interval != 0) != RST) return;  // (whole workgroup)
+    const HuffImage &im = recs[blockIdx.x];  // (the records of this kind)
+    const int img = im.img, t = threadIdx.x;
+    if (status[img] != 0) return;  // (whole workgroup) the verification refused the image
     load_shared(S, staging, &scans[img], &descs[img]);
     const llfe_jpeg_scan &sc = S.sc;
-    const Geometry geo{&sc, &S.d, slots + (int64_t)img * slot_stride};
-    const int16_t *dcd = w.dcd + (int64_t)img * w.max_blocks;
+    const Geometry geo{&sc, &S.d, slots + im.slot_offset};
+    const int16_t *dcd = w.dcd + im.dcd0;
     const int bim = sc.blocks_in_mcu;
     const int64_t mcus = (int64_t)sc.mcus_w * sc.mcus_h;
     const int m0 = (int)(mcus * t / HT), m1 = (int)(mcus * (t + 1) / HT);  // this lane's MCUs
@@ -341,49 +367,51 @@ __global__ __launch_bounds__(HT) void k_huff_dc(const uint8_t *__restrict__ stag
 
 }  // namespace
 
-size_t jpeg_huff_workspace_bytes(int n, int max_sub, int max_blocks) {
+size_t jpeg_huff_workspace_bytes(const HuffPlan &p) {
     size_t bytes = 0;
-    carve(nullptr, n, max_sub, max_blocks, &bytes);
+    carve(nullptr, (size_t)p.lanes, (size_t)p.wgs, (size_t)p.blocks, &bytes);
     return bytes;
 }
 
-int jpeg_huff_passes(int max_sub) { return (max_sub + HT - 1) / HT; }
-
 template <bool RST>
-static void launch_stage(int stage, int pass, const uint8_t *staging, const llfe_jpeg_scan *d_scans,
-                         const llfe_jpeg_desc *d_descs, int n, uint8_t *slots, int64_t slot_stride, const Ws &w,
+static void launch_stage(int stage, int pass, int from, const HuffPlan &p, const uint8_t *staging,
+                         const llfe_jpeg_scan *d_scans, const llfe_jpeg_desc *d_descs, uint8_t *slots, const Ws &w,
                          int *d_status, hipStream_t s) {
-    const dim3 lanes((unsigned)w.max_wg, (unsigned)n);
+    const int k = RST ? 1 : 0;
+    const HuffImage *mine = p.d_recs + (RST ? p.n_recs[0] : 0);
     switch (stage) {
     case 1:
-        hipLaunchKernelGGL(k_huff_sync<RST>, lanes, dim3(HT), 0, s, staging, d_scans, d_descs, d_status, w, n, pass);
+        hipLaunchKernelGGL(k_huff_sync<RST>, dim3((unsigned)(p.n_work[k] - from)), dim3(HT), 0, s, staging, d_scans, d_descs,
+                           p.d_recs, p.d_work[k] + from, w, pass);
         break;
     case 2:
-        hipLaunchKernelGGL(k_huff_verify<RST>, dim3((unsigned)n), dim3(HT), 0, s, d_scans, d_status, w);
+        hipLaunchKernelGGL(k_huff_verify<RST>, dim3((unsigned)p.n_recs[k]), dim3(HT), 0, s, d_scans, d_status, mine, w);
         break;
     case 3:
-        hipLaunchKernelGGL(k_huff_write<RST>, lanes, dim3(HT), 0, s, staging, d_scans, d_descs, d_status, slots, slot_stride, w);
+        hipLaunchKernelGGL(k_huff_write<RST>, dim3((unsigned)p.n_work[k]), dim3(HT), 0, s, staging, d_scans, d_descs,
+                           d_status, slots, p.d_recs, p.d_work[k], w);
         break;
     default:
-        hipLaunchKernelGGL(k_huff_dc<RST>, dim3((unsigned)n), dim3(HT), 0, s, staging, d_scans, d_descs, d_status, slots,
-                           slot_stride, w);
+        hipLaunchKernelGGL(k_huff_dc<RST>, dim3((unsigned)p.n_recs[k]), dim3(HT), 0, s, staging, d_scans, d_descs, d_status,
+                           slots, mine, w);
         break;
     }
 }
 
-hipError_t launch_jpeg_huff(int stage, int pass, int kinds, const uint8_t *staging, const llfe_jpeg_scan *d_scans,
-                            const llfe_jpeg_desc *d_descs, int n, int max_sub, int max_blocks, int64_t max_coef_bytes,
-                            uint8_t *slots, int64_t slot_stride, uint8_t *workspace, int *d_status, hipStream_t s) {
-    if (n <= 0 || max_sub <= 0 || max_blocks <= 0) return hipSuccess;
+hipError_t launch_jpeg_huff(int stage, int pass, const int from[2], const HuffPlan &p, const uint8_t *staging,
+                            const llfe_jpeg_scan *d_scans, const llfe_jpeg_desc *d_descs, uint8_t *slots,
+                            uint8_t *workspace, int *d_status, hipStream_t s) {
+    if (p.n_recs[0] + p.n_recs[1] <= 0) return hipSuccess;
     size_t bytes = 0;
-    const Ws w = carve(workspace, n, max_sub, max_blocks, &bytes);
+    const Ws w = carve(workspace, (size_t)p.lanes, (size_t)p.wgs, (size_t)p.blocks, &bytes);
     if (stage == 0) {
-        const int64_t wgs = (max_coef_bytes / 16 + HT - 1) / HT;
-        const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>(wgs, 64)), (unsigned)n);
-        hipLaunchKernelGGL(k_huff_init, grid, dim3(HT), 0, s, staging, d_scans, d_descs, slots, slot_stride);
+        hipLaunchKernelGGL(k_huff_init, dim3((unsigned)((p.n_recs[0] + p.n_recs[1]) * p.init_wgs)), dim3(HT), 0, s, staging,
+                           d_scans, d_descs, slots, p.d_recs, p.init_wgs);
     } else {
-        if (kinds & 1) launch_stage<false>(stage, pass, staging, d_scans, d_descs, n, slots, slot_stride, w, d_status, s);
-        if (kinds & 2) launch_stage<true>(stage, pass, staging, d_scans, d_descs, n, slots, slot_stride, w, d_status, s);
+        const int none[2] = {0, 0};
+        const int *f = stage == 1 ? from : none;
+        if (p.n_work[0] - f[0] > 0) launch_stage<false>(stage, pass, f[0], p, staging, d_scans, d_descs, slots, w, d_status, s);
+        if (p.n_work[1] - f[1] > 0) launch_stage<true>(stage, pass, f[1], p, staging, d_scans, d_descs, slots, w, d_status, s);
     }
     return hipGetLastError();
 }

@@ -31,8 +31,12 @@
 // an anomaly, never to an access outside the record.
 #ifndef LLFE_JPEG_HUFF_CORE_H
 #define LLFE_JPEG_HUFF_CORE_H
+#include <algorithm>
 #include <cstdint>
+#include <utility>
+#include <vector>
 
+#include "jpeg_desc_check.h"
 #include "llfe.h"
 
 #if defined(__HIPCC__)
@@ -336,6 +340,31 @@ inline bool validate_scans(const llfe_jpeg_scan *scans, const llfe_jpeg_desc *de
     *max_sub = ms;
     *max_blocks = mb;
     return true;
+}
+
+// The same check for images that each have their own size and tight slot
+// (llfe_jpeg_entropy_decode_images and its host twin): every staged image's (blocks_in_mcu != 0)
+// descriptor against its own height x width and slot_bytes, its slot 16-byte aligned, inside
+// slots_bytes and apart from every other staged image's, and validate_scans for the records.
+inline bool validate_scans_images(const llfe_jpeg_scan *scans, const llfe_jpeg_desc *descs, const llfe_jpeg_image *images,
+                                  int n, int64_t staging_bytes, int64_t slots_bytes) {
+    std::vector<std::pair<int64_t, int64_t>> ranges;  // [begin, end) of every slot
+    for (int i = 0; i < n; i++) {
+        if (scans[i].blocks_in_mcu == 0) continue;
+        const llfe_jpeg_image &m = images[i];
+        int64_t blocks = 0;
+        if (m.height <= 0 || m.width <= 0 || m.height > 65535 || m.width > 65535 || m.slot_offset < 0 ||
+            (m.slot_offset & 15) || m.slot_bytes <= 0 || (m.slot_bytes & 15) || m.slot_offset > slots_bytes ||
+            m.slot_bytes > slots_bytes - m.slot_offset ||
+            !llfe::check_jpeg_desc(descs[i], m.height, m.width, m.slot_bytes, &blocks))
+            return false;
+        ranges.emplace_back(m.slot_offset, m.slot_offset + m.slot_bytes);
+    }
+    std::sort(ranges.begin(), ranges.end());
+    for (size_t k = 1; k < ranges.size(); k++)
+        if (ranges[k].first < ranges[k - 1].second) return false;
+    int max_sub = 0, max_blocks = 0;
+    return validate_scans(scans, descs, n, staging_bytes, &max_sub, &max_blocks);
 }
 
 }  // namespace llfe_huff

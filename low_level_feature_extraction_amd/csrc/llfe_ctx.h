@@ -388,6 +388,9 @@ struct llfe_ctx {
     llfe_host::HostBuf<llfe_jpeg_scan> h_jpeg_scan;
     llfe_host::DevBuf<llfe_jpeg_scan> d_jpeg_scan;
     llfe_host::DevBuf<uint8_t> d_jpeg_huff_ws;
+    // the call's HuffImage records, then its two work tables
+    llfe_host::HostBuf<uint8_t> h_jpeg_huff_tab;
+    llfe_host::DevBuf<uint8_t> d_jpeg_huff_tab;
     // llfe_png_decode_device: the validated descriptors
     llfe_host::HostBuf<llfe_png_desc> h_png_desc;
     llfe_host::DevBuf<llfe_png_desc> d_png_desc;

@@ -45,6 +45,104 @@ int download_status(llfe_ctx *ctx, int32_t *status_out, int n, hipStream_t s) {
 // (1.5 plane bytes per pixel), 4 M blocks of IDCT per launch.
 constexpr int64_t kJpegPlaneBudget = (int64_t)256 << 20;
 
+// What both entropy entry points do behind their host checks.  For the images with
+// blocks_in_mcu != 0: the HuffImage records (those without a restart interval first; slot i at
+// images[i].slot_offset, or at i x slot_stride when images is null) and per kind the work table
+// ordered by workgroup index, then record, up through one pinned buffer in one copy; then the
+// kernels and the status back.  Totals of lanes, blocks or work entries beyond an int32 are
+// LLFE_ERR_CAPACITY, before any launch.
+int run_jpeg_huff(llfe_ctx *ctx, const char *who, const uint8_t *staging, int64_t staging_bytes,
+                  const llfe_jpeg_scan *scans, const llfe_jpeg_desc *descs, int n, const llfe_jpeg_image *images,
+                  int64_t slot_stride, uint8_t *slots, int32_t *status_out, hipStream_t s) {
+    using llfe::HuffImage;
+    using llfe::HuffWork;
+    constexpr int HT = llfe::kJpegHuffLanes;
+    llfe::HuffPlan plan;
+    std::vector<HuffImage> recs;
+    std::vector<int> wgs_of;  // per record
+    int64_t max_coef_bytes = 0;
+    double coef_bytes = 0;
+    try {
+        for (int kind = 0; kind < 2; kind++)
+            for (int i = 0; i < n; i++) {
+                const llfe_jpeg_scan &sc = scans[i];
+                if (sc.blocks_in_mcu == 0 || (sc.restart_interval != 0) != (kind == 1)) continue;
+                const int64_t nsub = llfe_huff::subsequences(sc.scan_bytes), wgs = (nsub + HT - 1) / HT;
+                HuffImage r;
+                r.slot_offset = images ? images[i].slot_offset : (int64_t)i * slot_stride;
+                r.img = i;
+                r.lane0 = (int32_t)plan.lanes;
+                r.wg0 = (int32_t)plan.wgs;
+                r.dcd0 = (int32_t)plan.blocks;
+                plan.lanes += nsub;
+                plan.wgs += wgs;
+                plan.blocks += (int64_t)sc.mcus_w * sc.mcus_h * sc.blocks_in_mcu;
+                if (plan.lanes > 0x7fffffff || plan.blocks > 0x7fffffff)
+                    return ctx->fail(LLFE_ERR_CAPACITY, "%s: more than 2^31 subsequences or blocks in one call", who);
+                plan.n_recs[kind]++;
+                plan.n_work[kind] += (int)wgs;
+                plan.passes = std::max(plan.passes, (int)wgs);
+                recs.push_back(r);
+                wgs_of.push_back((int)wgs);
+                for (int c = 0; c < descs[i].n_comp; c++) {
+                    const int64_t b = (int64_t)descs[i].comp[c].blocks_w * descs[i].comp[c].blocks_h * 128;
+                    max_coef_bytes = std::max(max_coef_bytes, b);
+                    coef_bytes += (double)b;
+                }
+            }
+        for (int i = 0; i < n; i++) status_out[i] = scans[i].blocks_in_mcu ? LLFE_OK : LLFE_ERR_UNSUPPORTED;
+        if (recs.empty()) return LLFE_OK;
+        plan.init_wgs = (int)std::max<int64_t>(1, std::min<int64_t>((max_coef_bytes / 16 + HT - 1) / HT, 64));
+        if ((int64_t)recs.size() * plan.init_wgs > 0x7fffffff)
+            return ctx->fail(LLFE_ERR_CAPACITY, "%s: %zu images in one call", who, recs.size());
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        const size_t rec_bytes = (recs.size() * sizeof(HuffImage) + 15) & ~(size_t)15;
+        const size_t tab_bytes = rec_bytes + (size_t)plan.wgs * sizeof(HuffWork);
+        HIPCHK(ctx, ctx->h_jpeg_huff_tab.ensure(tab_bytes));
+        HIPCHK(ctx, ctx->d_jpeg_huff_tab.ensure(tab_bytes));
+        std::memcpy(ctx->h_jpeg_huff_tab.p, recs.data(), recs.size() * sizeof(HuffImage));
+        // from[k][p]: the entries of kind k with a workgroup index below p
+        std::vector<int> from[2];
+        HuffWork *wk = (HuffWork *)(ctx->h_jpeg_huff_tab.p + rec_bytes);
+        plan.d_recs = (const HuffImage *)ctx->d_jpeg_huff_tab.p;
+        for (int kind = 0, r0 = 0, w0 = 0; kind < 2; r0 += plan.n_recs[kind], w0 += plan.n_work[kind], kind++) {
+            plan.d_work[kind] = (const HuffWork *)(ctx->d_jpeg_huff_tab.p + rec_bytes) + w0;
+            from[kind].assign((size_t)plan.passes + 1, plan.n_work[kind]);
+            int k = 0;
+            for (int g = 0; g < plan.passes; g++) {
+                from[kind][(size_t)g] = k;
+                for (int r = r0; r < r0 + plan.n_recs[kind]; r++)
+                    if (g < wgs_of[(size_t)r]) wk[w0 + k++] = HuffWork{r, g};
+            }
+        }
+        HIPCHK(ctx, ensure_records(ctx->h_jpeg_desc, ctx->d_jpeg_desc, n));
+        HIPCHK(ctx, ensure_records(ctx->h_jpeg_scan, ctx->d_jpeg_scan, n));
+        HIPCHK(ctx, ensure_records(ctx->h_dec_status, ctx->d_dec_status, n));
+        HIPCHK(ctx, ctx->d_jpeg_huff_ws.ensure(jpeg_huff_workspace_bytes(plan)));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_jpeg_huff_tab.p, ctx->h_jpeg_huff_tab.p, tab_bytes, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, upload_records(ctx->h_jpeg_desc, ctx->d_jpeg_desc, descs, n, s));
+        HIPCHK(ctx, upload_records(ctx->h_jpeg_scan, ctx->d_jpeg_scan, scans, n, s));
+        HIPCHK(ctx, upload_records(ctx->h_dec_status, ctx->d_dec_status, (const int32_t *)status_out, n, s));
+        auto launch = [&](int stage, int pass) {
+            const int f[2] = {from[0][(size_t)pass], from[1][(size_t)pass]};
+            return launch_jpeg_huff(stage, pass, f, plan, staging, ctx->d_jpeg_scan.p, ctx->d_jpeg_desc.p, slots,
+                                    ctx->d_jpeg_huff_ws.p, ctx->d_dec_status.p, s);
+        };
+        {
+            StageSlotScope tag(ctx->prof);
+            TIMED(ctx, s, "k_huff_init", coef_bytes, launch(0, 0));
+            // the cross-workgroup passes, fixed here from the scan lengths
+            for (int p = 0; p < plan.passes; p++) TIMED(ctx, s, "k_huff_sync", (double)staging_bytes, launch(1, p));
+            TIMED(ctx, s, "k_huff_verify", (double)plan.lanes * 20, launch(2, 0));
+            TIMED(ctx, s, "k_huff_write", (double)staging_bytes + (double)plan.blocks * 2, launch(3, 0));
+            TIMED(ctx, s, "k_huff_dc", (double)plan.blocks * 6, launch(4, 0));
+        }
+    } catch (const std::bad_alloc &) {
+        return ctx->fail(LLFE_ERR_OOM, "%s: out of host memory", who);
+    }
+    return download_status(ctx, status_out, n, s);
+}
+
 }  // namespace
 
 extern "C" {
@@ -206,38 +304,31 @@ int llfe_jpeg_entropy_decode(llfe_ctx *ctx, const uint8_t *staging, int64_t stag
         return ctx->fail(LLFE_ERR_INVALID, "llfe_jpeg_entropy_decode: a scan record points outside the staging buffer, "
                                            "its MCU geometry does not cover the block grids or its restart interval is "
                                            "not 0..65535");
-    int64_t max_coef_bytes = 0;
-    int kinds = 0;  // bit 0: images without a restart interval, bit 1: with one
-    for (int i = 0; i < n; i++) {
-        status_out[i] = scans[i].blocks_in_mcu ? LLFE_OK : LLFE_ERR_UNSUPPORTED;
-        if (scans[i].blocks_in_mcu) kinds |= scans[i].restart_interval ? 2 : 1;
-        for (int c = 0; c < descs[i].n_comp; c++)
-            max_coef_bytes = std::max<int64_t>(max_coef_bytes, (int64_t)descs[i].comp[c].blocks_w * descs[i].comp[c].blocks_h * 128);
+    return run_jpeg_huff(ctx, "llfe_jpeg_entropy_decode", staging, staging_bytes, scans, descs, n, nullptr, slot_stride,
+                         slots, status_out, (hipStream_t)stream);
+}
+
+int llfe_jpeg_entropy_decode_images(llfe_ctx *ctx, const uint8_t *staging, int64_t staging_bytes,
+                                    const llfe_jpeg_scan *scans, const llfe_jpeg_desc *descs,
+                                    const llfe_jpeg_image *images, int32_t n, uint8_t *slots, int64_t slots_bytes,
+                                    int32_t *status_out, llfe_stream stream) {
+    if (!ctx) return LLFE_ERR_INVALID;
+    if (n < 0 || (n && (!staging || !scans || !descs || !images || !slots || !status_out)) || slots_bytes < 0 ||
+        ((uintptr_t)slots & 15) || staging_bytes < 0 || ((uintptr_t)staging & 15))
+        return ctx->fail(LLFE_ERR_INVALID, "llfe_jpeg_entropy_decode_images: bad arguments (n=%d staging_bytes=%lld "
+                                           "slots_bytes=%lld)", n, (long long)staging_bytes, (long long)slots_bytes);
+    // nothing is launched on a descriptor or a record the host check has not passed
+    try {
+        if (!llfe_huff::validate_scans_images(scans, descs, images, n, staging_bytes, slots_bytes))
+            return ctx->fail(LLFE_ERR_INVALID, "llfe_jpeg_entropy_decode_images: a scan record points outside the "
+                                               "staging buffer, a descriptor outside its slot, a slot outside the "
+                                               "coefficient buffer or into another image's, or a geometry does not "
+                                               "cover its image");
+    } catch (const std::bad_alloc &) {
+        return ctx->fail(LLFE_ERR_OOM, "llfe_jpeg_entropy_decode_images: out of host memory");
     }
-    if (n == 0 || max_sub == 0) return LLFE_OK;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(ctx, ensure_records(ctx->h_jpeg_desc, ctx->d_jpeg_desc, n));
-    HIPCHK(ctx, ensure_records(ctx->h_jpeg_scan, ctx->d_jpeg_scan, n));
-    HIPCHK(ctx, ensure_records(ctx->h_dec_status, ctx->d_dec_status, n));
-    HIPCHK(ctx, ctx->d_jpeg_huff_ws.ensure(jpeg_huff_workspace_bytes(n, max_sub, max_blocks)));
-    HIPCHK(ctx, upload_records(ctx->h_jpeg_desc, ctx->d_jpeg_desc, descs, n, s));
-    HIPCHK(ctx, upload_records(ctx->h_jpeg_scan, ctx->d_jpeg_scan, scans, n, s));
-    HIPCHK(ctx, upload_records(ctx->h_dec_status, ctx->d_dec_status, (const int32_t *)status_out, n, s));
-    const int passes = jpeg_huff_passes(max_sub);  // the cross-workgroup passes, fixed here from the scan lengths
-    auto launch = [&](int stage, int pass) {
-        return launch_jpeg_huff(stage, pass, kinds, staging, ctx->d_jpeg_scan.p, ctx->d_jpeg_desc.p, n, max_sub, max_blocks,
-                                max_coef_bytes, slots, slot_stride, ctx->d_jpeg_huff_ws.p, ctx->d_dec_status.p, s);
-    };
-    {
-        StageSlotScope tag(ctx->prof);
-        TIMED(ctx, s, "k_huff_init", (double)n * max_coef_bytes, launch(0, 0));
-        for (int p = 0; p < passes; p++) TIMED(ctx, s, "k_huff_sync", (double)staging_bytes, launch(1, p));
-        TIMED(ctx, s, "k_huff_verify", (double)n * max_sub * 20, launch(2, 0));
-        TIMED(ctx, s, "k_huff_write", (double)staging_bytes + (double)n * max_blocks * 2, launch(3, 0));
-        TIMED(ctx, s, "k_huff_dc", (double)n * max_blocks * 6, launch(4, 0));
-    }
-    return download_status(ctx, status_out, n, s);
+    return run_jpeg_huff(ctx, "llfe_jpeg_entropy_decode_images", staging, staging_bytes, scans, descs, n, images, 0,
+                         slots, status_out, (hipStream_t)stream);
 }
 
 int llfe_png_decode_device(llfe_ctx *ctx, const uint8_t *staging, int64_t staging_bytes, const llfe_png_desc *descs,

@@ -421,20 +421,38 @@ struct JpegWork;
 hipError_t launch_jpeg_images(const uint8_t *coefs, const JpegImageRec *d_recs, const JpegWork *d_work, int n_work,
                               uint8_t *out, hipStream_t s);
 
-// llfe_jpeg_entropy_decode (jpeg_huff.hip).  The scans and descriptors are validated on the
-// host first (jpeg_huff_core.h validate_scans, validate_jpeg_descs above); max_sub / max_blocks
-// are what that check returned.  workspace: jpeg_huff_workspace_bytes of device memory,
-// d_status: n ints, non-zero for the images to skip.  Stages, in this order on one stream:
-// 0 = zero the coefficient areas (max_coef_bytes: the largest component of an image) and copy the
-// quantisation tables, 1 = a synchronisation pass (pass = 0 .. jpeg_huff_passes - 1),
-// 2 = verification and block scan (sets d_status of an image that fails), 3 = the write pass,
-// 4 = the DC sums.  kinds: bit 0 = the batch has images without a restart interval, bit 1 = with
-// one; the stages behind 0 are launched once per kind present.
-size_t jpeg_huff_workspace_bytes(int n, int max_sub, int max_blocks);
-int jpeg_huff_passes(int max_sub);
-hipError_t launch_jpeg_huff(int stage, int pass, int kinds, const uint8_t *staging, const llfe_jpeg_scan *d_scans,
-                            const llfe_jpeg_desc *d_descs, int n, int max_sub, int max_blocks, int64_t max_coef_bytes,
-                            uint8_t *slots, int64_t slot_stride, uint8_t *workspace, int *d_status, hipStream_t s);
+// llfe_jpeg_entropy_decode and llfe_jpeg_entropy_decode_images (jpeg_huff.hip).  The scans and
+// descriptors are validated on the host first (jpeg_huff_core.h validate_scans,
+// jpeg_desc_check.h); from them the host builds, for the images it takes, one HuffImage record
+// each (those without a restart interval first) and per kind a work table of (record, workgroup
+// of that image) entries ordered by workgroup index, then record.  d_status: one int per image of
+// the call, non-zero for the images to skip.  Stages, in this order on one stream: 0 = zero the
+// coefficient areas (init_wgs workgroups per record) and copy the quantisation tables, 1 = a
+// synchronisation pass (pass = 0 .. passes - 1; from[k]: the first entry of kind k's table with
+// g >= pass, the entries in front of it are final and are not launched), 2 = verification and
+// block scan (sets d_status of an image that fails), 3 = the write pass, 4 = the DC sums.  A
+// stage behind 0 is launched once per kind present.
+constexpr int kJpegHuffLanes = 256;  // lanes (subsequences) per workgroup
+struct HuffImage {
+    int64_t slot_offset;  // of the image's slot in the coefficient buffer
+    int32_t img;          // its index in the call's scans / descs / status
+    int32_t lane0, wg0;   // its first lane and first workgroup in the workspace
+    int32_t dcd0;         // its first entry in the DC-difference array
+};
+struct HuffWork {
+    int32_t rec, g;  // record, workgroup of that image
+};
+struct HuffPlan {
+    const HuffImage *d_recs = nullptr;              // device: kind 0 (no restart interval) first
+    const HuffWork *d_work[2] = {nullptr, nullptr};  // device: per kind
+    int n_recs[2] = {0, 0}, n_work[2] = {0, 0};
+    int64_t lanes = 0, wgs = 0, blocks = 0;  // the sums the workspace is carved by
+    int init_wgs = 1, passes = 0;
+};
+size_t jpeg_huff_workspace_bytes(const HuffPlan &p);
+hipError_t launch_jpeg_huff(int stage, int pass, const int from[2], const HuffPlan &p, const uint8_t *staging,
+                            const llfe_jpeg_scan *d_scans, const llfe_jpeg_desc *d_descs, uint8_t *slots,
+                            uint8_t *workspace, int *d_status, hipStream_t s);
 
 // llfe_png_decode_device (png_inflate.hip).  The descriptors are validated on the host first
 // (png_inflate_core.h validate_png_descs); d_descs is that array on the device, d_status n ints,

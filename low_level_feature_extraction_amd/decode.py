@@ -17,7 +17,8 @@ with ``entropy="device"`` baseline files are entropy-decoded on the device too (
 with ``png="device"`` 8-bit RGB / RGBA PNGs are inflated, unfiltered and converted there
 (csrc/png_inflate.hip).  ``decode_images_device`` (opt-in too) is decode_many's device form for
 images that each have their own size: the JPEG coefficient path over tight slots, one launch of
-csrc/jpeg_images.hip, the results views into one packed device tensor.
+csrc/jpeg_images.hip, the results views into one packed device tensor; with ``entropy="device"``
+the tight slots are filled on the device too (csrc/jpeg_huff.hip) from the files' bytes.
 """
 from __future__ import annotations
 
@@ -570,13 +571,26 @@ def _decode_or_error(b):
         return e
 
 
-def _run_images(blobs, images, layout_status, chunks, first, device, workers) -> list:
+class _Chunk:
+    """What one chunk of decode_images_device holds after its staging: ``status`` per image
+    (non-zero: the host decoders take it) and ``parts``, each (places in the chunk, llfe_jpeg_image
+    records, llfe_jpeg_desc records, coefficients): a StagedImages whose used prefix has yet to
+    cross, or a device tensor of slots."""
+
+    def __init__(self, status, parts):
+        self.status, self.parts = status, parts
+
+
+def _host_chunk(st: StagedImages) -> _Chunk:
+    return _Chunk(st.status, [(list(range(len(st.blobs))), st.images, st.descs, st)])
+
+
+def _run_images(blobs, images, layout_status, chunks, first, device, workers, stage) -> list:
     """decode_images_device after the header stage: ``chunks`` (lists of image indices, in order,
-    together all of them) are staged and reconstructed one after the other into one packed
-    tensor; ``first`` is chunk 0 already staged."""
+    together all of them) are staged (``stage(idx)`` -> _Chunk) and reconstructed one after the
+    other into one packed tensor; ``first`` is chunk 0 already staged."""
     import torch
 
-    from . import _lib
     from .backend import Backend
 
     n = len(blobs)
@@ -603,21 +617,21 @@ def _run_images(blobs, images, layout_status, chunks, first, device, workers) ->
 
     out = [host[i] if isinstance(host.get(i), Exception) else place(i) for i in range(n)]
     for k, idx in enumerate(chunks):
-        if k == 0:
-            st = first
-        else:
-            sub = (_lib.LlfeJpegImage * len(idx))(*[_lib.LlfeJpegImage.from_buffer_copy(images[i]) for i in idx])
-            st = _stage_images([blobs[i] for i in idx], sub, [layout_status[i] for i in idx], workers)
-        for m, i in zip(st.images, idx):
-            m.out_offset = offset[i]
-        if any(rc == 0 for rc in st.status):
-            src = st.tensor[0] if st.tensor is not None else torch.from_numpy(st.slots)
-            with torch.cuda.device(dev):  # the staged prefix in one copy: the slots are tight
-                coefs = torch.empty(st.used_bytes, dtype=torch.uint8, device=dev)
-                coefs.copy_(src[:st.used_bytes], non_blocking=True)
-                Backend.get(dev.index).jpeg_reconstruct_images(coefs, st.images, st.descs, packed)
+        ch = first if k == 0 else stage(idx)
+        for sub, recs, descs, coefs in ch.parts:
+            for m, j in zip(recs, sub):
+                m.out_offset = offset[idx[j]]
+            if not any(d.n_comp for d in descs):
+                continue
+            with torch.cuda.device(dev):
+                if isinstance(coefs, StagedImages):  # the staged prefix in one copy: the slots are tight
+                    st = coefs
+                    src = st.tensor[0] if st.tensor is not None else torch.from_numpy(st.slots)
+                    coefs = torch.empty(st.used_bytes, dtype=torch.uint8, device=dev)
+                    coefs.copy_(src[:st.used_bytes], non_blocking=True)
+                Backend.get(dev.index).jpeg_reconstruct_images(coefs, recs, descs, packed)
         # a later chunk's extraction handed an image back: its place is laid out by its header
-        late = [i for j, i in enumerate(idx) if st.status[j] != 0 and i not in known]
+        late = [i for j, i in enumerate(idx) if ch.status[j] != 0 and i not in known]
         for i, r in zip(late, pool.map(_decode_or_error, [blobs[i] for i in late])):
             if isinstance(r, Exception):
                 out[i] = r
@@ -631,6 +645,13 @@ def _run_images(blobs, images, layout_status, chunks, first, device, workers) ->
     return out
 
 
+def _sub_images(images, idx):
+    """Copies of the llfe_jpeg_image records at the places ``idx``."""
+    from . import _lib
+
+    return (_lib.LlfeJpegImage * len(idx))(*[_lib.LlfeJpegImage.from_buffer_copy(images[i]) for i in idx])
+
+
 def reconstruct_staged_images(st: StagedImages, device=0, workers=None) -> list:
     """The device half of a StagedImages: the staged coefficients across in one copy, one
     llfe_jpeg_reconstruct_images launch on the current stream, and for every image with a
@@ -639,10 +660,11 @@ def reconstruct_staged_images(st: StagedImages, device=0, workers=None) -> list:
     multiple of 16), a DecodeError instance in the place of an image nothing decodes."""
     if not st.blobs:
         return []
-    return _run_images(st.blobs, st.images, st.layout_status, [list(range(len(st.blobs)))], st, device, workers)
+    return _run_images(st.blobs, st.images, st.layout_status, [list(range(len(st.blobs)))], _host_chunk(st), device,
+                       workers, None)
 
 
-def decode_images_device(blobs, device=0, workers=None) -> list:
+def decode_images_device(blobs, device=0, workers=None, entropy="host", restarts=False) -> list:
     """decode_many with the JPEG reconstruction on the GPU, for images of any sizes: -> a list in
     input order of H x W x 3 BGR uint8 device tensors, the same bytes decode_bgr returns, each a
     view into one packed tensor and starting at a multiple of 16; a DecodeError instance stands
@@ -654,9 +676,17 @@ def decode_images_device(blobs, device=0, workers=None) -> list:
     (LLFE_JPEG_STAGE_BYTES, default 1 GiB): a batch above it is staged and reconstructed in
     chunks of whole images into the one packed tensor, and an image that alone exceeds it takes
     the host decoder.  The result feeds Backend.process_images, Backend.thumbnail_pil_images and
-    MicroBatcher.submit unchanged."""
-    from . import _lib
+    MicroBatcher.submit unchanged.
 
+    ``entropy="device"`` moves the entropy decode of baseline single-scan JPEGs (without restart
+    markers, or with them under ``restarts=True``) to the device as well, chunk by chunk
+    (stage_bytes_images, entropy_decode_staged_images: csrc/jpeg_huff.hip): the host parses the
+    headers, the file bytes cross PCIe in one copy and the kernels fill a device tensor of the
+    chunk's tight slots, so LLFE_JPEG_STAGE_BYTES then bounds coefficient bytes that live in
+    device memory only.  What the device hands back takes the host coefficient path above, what
+    that hands back decode_bgr; the result is the same bytes in every case."""
+    if entropy not in ("host", "device"):
+        raise ValueError('entropy must be "host" or "device"')
     blobs = [bytes(b) for b in blobs]
     if not blobs:
         return []
@@ -670,9 +700,14 @@ def decode_images_device(blobs, device=0, workers=None) -> list:
             room = 0
         chunks[-1].append(i)
         room += m.slot_bytes
-    sub = (_lib.LlfeJpegImage * len(chunks[0]))(*[_lib.LlfeJpegImage.from_buffer_copy(images[i]) for i in chunks[0]])
-    first = _stage_images([blobs[i] for i in chunks[0]], sub, [layout_status[i] for i in chunks[0]], workers)
-    return _run_images(blobs, images, layout_status, chunks, first, device, workers)
+
+    def stage(idx):
+        sub, status = [blobs[i] for i in idx], [layout_status[i] for i in idx]
+        if entropy == "host":
+            return _host_chunk(_stage_images(sub, _sub_images(images, idx), status, workers))
+        return _device_chunk(sub, _sub_images(images, idx), status, device, workers, restarts)
+
+    return _run_images(blobs, images, layout_status, chunks, stage(chunks[0]), device, workers, stage)
 
 
 # ------------------------------------------------------------ JPEG entropy decode on the device
@@ -797,6 +832,131 @@ def decode_staged_bytes(sb: StagedBytes, device=0, workers=None, out=None):
             raise _renumber(e, todo) from None
         out[torch.tensor(todo, device=dev)] = sub
     return out
+
+
+# ------------------------------------------- JPEG entropy decode of a mixed-size batch on the device
+# The two paths above joined (DESIGN.md §3 "JPEG entropy decode of a mixed-size batch"): the
+# headers give tight slots (llfe_jpeg_images_layout) and records as long as their files
+# (llfe_jpeg_records_layout), llfe_jpeg_parse_images stages the records one behind the other, the
+# used prefix crosses PCIe in one copy and llfe_jpeg_entropy_decode_images (csrc/jpeg_huff.hip)
+# fills the tight slots llfe_jpeg_reconstruct_images reads.
+class StagedByteImages:
+    """A batch of images of any sizes after llfe_jpeg_parse_images: ``images`` (the llfe_jpeg_image
+    records: size and tight slot of every image), ``descs`` / ``scans`` (the llfe_jpeg_desc /
+    llfe_jpeg_scan arrays), ``records`` (1-d uint8, pinned when a GPU is present; its first
+    ``used_bytes`` bytes hold the records), ``slot_bytes`` (the bytes of all slots),
+    ``layout_status`` / ``status`` per image (the header stage's, and the final one) and the
+    blobs."""
+
+    def __init__(self, blobs, images, descs, scans, layout_status, status, records, used_bytes, slot_bytes, tensor=None):
+        self.blobs, self.images, self.descs, self.scans = blobs, images, descs, scans
+        self.layout_status, self.status = layout_status, status
+        self.records, self.used_bytes, self.slot_bytes, self.tensor = records, used_bytes, slot_bytes, tensor
+
+
+def _stage_bytes_images(blobs, images, layout_status, workers, restarts) -> StagedByteImages:
+    """llfe_jpeg_parse_images of ``blobs`` into the next staging buffer of the ring, the slots of
+    ``images`` and the records (llfe_jpeg_records_layout) laid one behind the other here."""
+    import ctypes as C
+
+    from . import _lib
+
+    n, total = len(blobs), 0
+    for m in images:
+        m.slot_offset = total
+        total += m.slot_bytes
+    ptrs, sizes, st, keep = _blob_table(blobs)
+    offsets, used = (C.c_int64 * n)(), C.c_int64(0)
+    _lib.lib().llfe_jpeg_records_layout(sizes, images, n, offsets, C.byref(used))
+    records, tensor = _ring("byte_images", 1, _stage_bucket(used.value), lambda n: ())
+    descs, scans = (_lib.LlfeJpegDesc * n)(), (_lib.LlfeJpegScan * n)()
+    status = [-5] * n  # (LLFE_ERR_UNSUPPORTED: nothing staged)
+    if used.value:
+        _lib.lib().llfe_jpeg_parse_images(ptrs, sizes, n, images, offsets, records.ctypes.data, used.value, descs, scans,
+                                          st, int(workers or default_decode_threads()),
+                                          _lib.JPEG_PARSE_RESTARTS if restarts else 0)
+        status = list(st)
+    del keep
+    status = [a if a != 0 else b for a, b in zip(layout_status, status)]
+    return StagedByteImages(blobs, images, descs, scans, list(layout_status), status, records[0], int(used.value), total,
+                            tensor)
+
+
+def stage_bytes_images(blobs, workers=None, restarts=False) -> StagedByteImages:
+    """The host half of decode_images_device(entropy="device") for one staging buffer: the headers
+    of every blob (images_layout), then llfe_jpeg_parse_images: quantisation tables, decode tables
+    and the scan's bytes of every eligible JPEG (what stage_bytes takes), whatever its size and
+    sampling class, one record behind the other in the next staging buffer of a ring of three,
+    keyed by a bucket of the total bytes.  Host only; no entropy decoding happens here.  An image
+    this path does not take has a non-zero status, n_comp 0 and blocks_in_mcu 0.  ``restarts`` as
+    in stage_bytes."""
+    blobs = [bytes(b) for b in blobs]
+    images, layout_status, _ = images_layout(blobs, workers)
+    return _stage_bytes_images(blobs, images, layout_status, workers, restarts)
+
+
+def entropy_reference_images(st: StagedByteImages, one_piece=False):
+    """llfe_jpeg_entropy_reference_images, the host twin of csrc/jpeg_huff.hip over tight slots:
+    -> (1-d uint8 array of st.slot_bytes, status list).  For tests and for debugging the kernels."""
+    import ctypes as C
+
+    from . import _lib
+
+    n = len(st.blobs)
+    slots = np.zeros(max(st.slot_bytes, 1), np.uint8)
+    status = (C.c_int32 * n)()
+    rc = _lib.lib().llfe_jpeg_entropy_reference_images(st.records.ctypes.data, st.used_bytes, st.scans, st.descs, st.images,
+                                                       n, slots.ctypes.data, st.slot_bytes, status, int(bool(one_piece)))
+    if rc != 0:
+        raise ValueError(f"llfe_jpeg_entropy_reference_images: {rc}")
+    return slots[:st.slot_bytes], list(status)
+
+
+def entropy_decode_staged_images(st: StagedByteImages, device=0, slots=None):
+    """The device half of the entropy decode of images of any sizes: one H2D of the used prefix
+    of the staged records, then llfe_jpeg_entropy_decode_images on the current stream into
+    ``slots`` (a 1-d uint8 device tensor of at least st.slot_bytes; allocated when None).
+    -> (the coefficient tensor, the descriptors of the images the device took (n_comp 0 for the
+    others), the device's status list)."""
+    import torch
+
+    from . import _lib
+    from .backend import Backend
+
+    n = len(st.blobs)
+    dev = _device(device)
+    with torch.cuda.device(dev):
+        src = st.tensor[0] if st.tensor is not None else torch.from_numpy(st.records)
+        d_rec = torch.empty(max(st.used_bytes, 1), dtype=torch.uint8, device=dev)
+        d_rec[:st.used_bytes].copy_(src[:st.used_bytes], non_blocking=True)
+        if slots is None:
+            slots = torch.empty(max(st.slot_bytes, 1), dtype=torch.uint8, device=dev)
+        status = Backend.get(dev.index).jpeg_entropy_decode_images(d_rec[:st.used_bytes], st.scans, st.descs, st.images,
+                                                                   slots)
+    descs = (_lib.LlfeJpegDesc * n).from_buffer_copy(st.descs)
+    for i, rc in enumerate(status):
+        if rc != 0:
+            descs[i].n_comp = 0
+    return slots, descs, status
+
+
+def _device_chunk(blobs, images, layout_status, device, workers, restarts) -> _Chunk:
+    """One chunk of decode_images_device(entropy="device"): parse, copy, entropy kernels; the
+    images the device hands back go through the host coefficient path (_stage_images)."""
+    n = len(blobs)
+    sb = _stage_bytes_images(blobs, images, layout_status, workers, restarts)
+    status, parts = [-5] * n, []
+    if any(rc == 0 for rc in sb.status):
+        d_slots, descs, status = entropy_decode_staged_images(sb, device)
+        parts.append((list(range(n)), sb.images, descs, d_slots))
+    todo = [j for j, rc in enumerate(status) if rc != 0]
+    status = list(status)
+    if todo:
+        st = _stage_images([blobs[j] for j in todo], _sub_images(images, todo), [layout_status[j] for j in todo], workers)
+        parts.append((todo, st.images, st.descs, st))
+        for j, rc in zip(todo, st.status):
+            status[j] = rc
+    return _Chunk(status, parts)
 
 
 # ------------------------------------------------------------------ PNG decode on the device

@@ -42,7 +42,7 @@ class ImageProcessor:
 
     @staticmethod
     def auto_process_images(images_bytes, max_width: int = 1920, max_height: int = 1080, device: bool = False,
-                            decode: str = "host") -> list:
+                            decode: str = "host", entropy: str = "host", restarts: bool = False) -> list:
         """Batched auto_process_image: host decode on the decode pool, then one GPU
         thumbnail launch sequence per group of equally sized images
         (llfe_thumbnail_pil_batch).  Returns arrays in input order; an input that fails
@@ -56,7 +56,13 @@ class ImageProcessor:
         ``decode="device"`` (with ``device=True`` only): the uploads, whatever their sizes, are
         decoded by decode.decode_images_device -- the JPEG reconstruction runs on the GPU in one
         launch and the pixels never cross PCIe -- and the thumbnail call reads the device tensors
-        in place; the bytes are again the same.  ``decode="host"`` is the route above."""
+        in place; the bytes are again the same.  ``decode="host"`` is the route above.
+
+        ``entropy="device"`` (with ``decode="device"`` only) moves the entropy decode of the
+        baseline JPEGs among them to the GPU as well (decode_images_device(entropy="device"):
+        the file bytes cross PCIe, not the coefficients), ``restarts=True`` (with
+        ``entropy="device"`` only) lets it take files with restart intervals; the bytes are the
+        same in every case."""
         from .backend import Backend, thumbnail_size
         from .decode import decode_images_device, decode_many
 
@@ -64,8 +70,14 @@ class ImageProcessor:
             raise ValueError('decode must be "host" or "device"')
         if decode == "device" and not device:
             raise ValueError('decode="device" needs device=True')
+        if entropy not in ("host", "device"):
+            raise ValueError('entropy must be "host" or "device"')
+        if entropy == "device" and decode != "device":
+            raise ValueError('entropy="device" needs decode="device"')
+        if restarts and entropy != "device":
+            raise ValueError('restarts=True needs entropy="device"')
         if decode == "device":
-            decoded = decode_images_device(list(images_bytes), Backend.get().device)
+            decoded = decode_images_device(list(images_bytes), Backend.get().device, entropy=entropy, restarts=restarts)
         else:
             decoded = decode_many(list(images_bytes))
         out: list = [None] * len(decoded)

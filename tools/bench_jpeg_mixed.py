@@ -7,15 +7,18 @@ profiles/jpeg_images/).  bench.py is not touched: this tool measures the new ent
      what ImageProcessor.auto_process_images(device=True) does by default
   B  group the feed by size, decode.decode_batch_device per group (csrc/jpeg_recon.hip)
   C  decode.decode_images_device: one staging buffer, one launch (csrc/jpeg_images.hip)
+  D  decode.decode_images_device(entropy="device"): C with the entropy decode on the device too
+     (csrc/jpeg_huff.hip; DESIGN.md §3 "JPEG entropy decode of a mixed-size batch"; figures in
+     profiles/jpeg_huff_images/), measured against C, the path it replaces
 
-A seeded feed of --images quality-85 4:2:0 JPEGs, one process, one rank, a warm-up of all three
-(which also compares their bytes), then A, B and C alternating for --legs legs each, every leg
+A seeded feed of --images quality-85 4:2:0 JPEGs, one process, one rank, a warm-up of all four
+(which also compares their bytes), then A, B, C and D alternating for --legs legs each, every leg
 --reps passes over the feed:
   --feed mixed    the 16 sizes of tools/bench_thumb.py --feed mixed (2000 x 1500 .. 4032 x 3024)
   --feed uniform  every image 1920 x 1080, where B is at its best
-After the timed legs one profiled pass of B and of C gives the kernel ms (llfe_kernel_stats):
-k_jpeg_idct + k_jpeg_color against k_jpeg_images on the same coefficients.  One JSON line on
-stdout.
+After the timed legs one profiled pass of B, of C and of D gives the kernel ms (llfe_kernel_stats):
+k_jpeg_idct + k_jpeg_color against k_jpeg_images on the same coefficients, and D's k_huff_*
+kernels (k_huff_sync: one launch per pass and kind).  One JSON line on stdout.
 """
 from __future__ import annotations
 
@@ -98,13 +101,16 @@ def main():
     def route_c():
         return decode.decode_images_device(blobs)
 
-    routes = {"A": route_a, "B": route_b, "C": route_c}
+    def route_d():
+        return decode.decode_images_device(blobs, entropy="device")
+
+    routes = {"A": route_a, "B": route_b, "C": route_c, "D": route_d}
     # warm-up: three passes each, so that every buffer of the pinned staging rings of three exists
-    # (allocations, code objects), and the three routes give the same bytes
+    # (allocations, code objects), and the four routes give the same bytes
     for _ in range(3):
-        ra, rb, rc = route_a(), route_b(), route_c()
-    same = all(torch.equal(a, b) and torch.equal(a, c) for a, b, c in zip(ra, rb, rc))
-    del ra, rb, rc
+        ra, rb, rc, rd = route_a(), route_b(), route_c(), route_d()
+    same = all(torch.equal(a, b) and torch.equal(a, c) and torch.equal(a, d) for a, b, c, d in zip(ra, rb, rc, rd))
+    del ra, rb, rc, rd
 
     def leg(fn):
         torch.cuda.synchronize()
@@ -127,9 +133,9 @@ def main():
         finally:
             be.set_profiling(False)
         return {k: {"launches": v["launches"], "ms": round(v["total_ms"], 3)} for k, v in st.items()
-                if k.startswith("k_jpeg")}
+                if k.startswith(("k_jpeg", "k_huff"))}
 
-    kb, kc = profiled(route_b), profiled(route_c)
+    kb, kc, kd = profiled(route_b), profiled(route_c), profiled(route_d)
     summary = {k: {"median": statistics.median(v), "min": min(v), "max": max(v)} for k, v in legs.items()}
     spread = max(summary[k]["max"] - summary[k]["min"] for k in ("A", "B"))
     out = {
@@ -139,8 +145,9 @@ def main():
         "images_per_s": legs, "summary": summary,
         # a speed claim needs the medians further apart than three times the base routes' spread
         "C_minus_best_base_median": round(summary["C"]["median"] - max(summary["A"]["median"], summary["B"]["median"]), 1),
+        "D_minus_C_median": round(summary["D"]["median"] - summary["C"]["median"], 1),
         "three_times_base_spread": round(3 * spread, 1),
-        "kernels_ms_per_pass": {"B": kb, "C": kc},
+        "kernels_ms_per_pass": {"B": kb, "C": kc, "D": kd},
         "device": torch.cuda.get_device_name(0),
     }
     print(json.dumps(out))
