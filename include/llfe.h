@@ -374,6 +374,13 @@ int llfe_palette_rules(const uint8_t *centers_rgb, const int32_t *counts, int32_
  * or without cube tables), into out[n * 10] (host).  Replaces nothing in the
  * reference: cv2.kmeans only returns the best attempt (color_extractor.py:194). */
 int llfe_kmeans_attempts(llfe_ctx *ctx, int32_t n, llfe_kmeans_attempt *out);
+/* The same diagnostics for any n_colors up to LLFE_MAX_COLORS (k_kmeans and k_kmeans_big), as
+ * arrays with k_cap >= n_colors rows per attempt (host): pp_centers and centers
+ * [n][10][k_cap][3], counts [n][10][k_cap], iters and compactness [n][10].  Rows past an
+ * image's K = min(n_colors, n_unique) are zero.  The same refusals as llfe_kmeans_attempts;
+ * k_cap below the launch's n_colors is LLFE_ERR_INVALID. */
+int llfe_kmeans_attempts_k(llfe_ctx *ctx, int32_t n, int32_t k_cap, float *pp_centers, float *centers,
+                           int32_t *counts, int32_t *iters, double *compactness);
 /* Pillow Image.resize(size, LANCZOS, box) on u8 HWC (image_processor.py:221-224).
  * box = (x0, y0, x1, y1) in source pixels, or NULL (whole image); its values are taken at
  * float32 precision, as Pillow takes them. src/dst device. */

@@ -857,13 +857,26 @@ class Backend:
             out.append((centers, np.array([r.counts[j] for j in range(k)], np.int64), float(r.compactness)))
         return out
 
-    def kmeans_attempts(self, n):
+    def kmeans_attempts(self, n, k=5):
         """Diagnostics (llfe_kmeans_attempts): the 10 k-means attempts of each of the first n
         images of the last k-means launch on this context -- the last chunk of process() /
         process_images(), a kmeans() call on caller keys, or the ticket submit() / submit_images()
         issued last (refused until every ticket is collected) -- for n_colors <= 5
         -> list of n lists of dicts (pp_centers, centers float32 5 x 3 before the uint8
-        truncation, counts, iters, compactness; rows past K unused)."""
+        truncation, counts, iters, compactness; rows past K unused).
+        k > 5 (llfe_kmeans_attempts_k): the same for a launch with n_colors <= k, k rows each
+        (rows past an image's K zero)."""
+        if k > 5:
+            pp = np.zeros((n, 10, k, 3), np.float32)
+            cen = np.zeros((n, 10, k, 3), np.float32)
+            cnt = np.zeros((n, 10, k), np.int32)
+            it = np.zeros((n, 10), np.int32)
+            comp = np.zeros((n, 10), np.float64)
+            self._call("llfe_kmeans_attempts_k", n, k, pp.ctypes.data, cen.ctypes.data, cnt.ctypes.data,
+                       it.ctypes.data, comp.ctypes.data)
+            return [[{"pp_centers": pp[i, a], "centers": cen[i, a], "counts": cnt[i, a].astype(np.int64),
+                      "iters": int(it[i, a]), "compactness": float(comp[i, a])} for a in range(10)]
+                    for i in range(n)]
         out = (L.LlfeKmeansAttempt * max(n * 10, 1))()
         self._call("llfe_kmeans_attempts", n, out)
         recs = []

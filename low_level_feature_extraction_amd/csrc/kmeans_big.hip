@@ -474,8 +474,15 @@ __global__ __launch_bounds__(BT) void k_kmeans_big(const uint32_t *__restrict__ 
         o->t_sw = 0;
         o->drift_hist = 0;
         for (int k = 0; k < K; k++) {
-            for (int j = 0; j < 3; j++) o->centers[k][j] = sm.c[k][j];
+            for (int j = 0; j < 3; j++) {
+                o->centers[k][j] = sm.c[k][j];
+                o->pp_centers_big[k][j] = (float)sm.icc[k][j];  // (diagnostics, llfe_kmeans_attempts_k)
+            }
             o->counts[k] = sm.counts[k];
+        }
+        for (int k = K; k < n_colors; k++) {  // (U < n_colors: no stale rows of an earlier launch)
+            for (int j = 0; j < 3; j++) o->centers[k][j] = o->pp_centers_big[k][j] = 0.f;
+            o->counts[k] = 0;
         }
     }
 }

@@ -209,6 +209,7 @@ struct KmeansAttemptOut {
     uint32_t pp_walks, pp_walk_lanes;     // 64-lane passes that walked k-means++'s split cubes; their live lanes summed
     uint32_t pp_walk_mixed;               // ... and the list drains whose cubes lay in more than one partition
     float pp_centers[kMaxK][3];  // the k-means++ centres (cube-table path; llfe_kmeans_attempts)
+    float pp_centers_big[kMaxColors][3];  // ... of k_kmeans_big (llfe_kmeans_attempts_k)
 };
 
 struct KmeansImageOut {

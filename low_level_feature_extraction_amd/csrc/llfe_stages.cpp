@@ -299,20 +299,55 @@ int llfe_palette_rules(const uint8_t *centers_rgb, const int32_t *counts, int32_
     return LLFE_OK;
 }
 
-int llfe_kmeans_attempts(llfe_ctx *ctx, int32_t n, llfe_kmeans_attempt *out) {
-    if (!ctx || !out || n < 0) return LLFE_ERR_INVALID;
+// The attempt records of the first n images of the last k-means launch (km_last: lane 0 for the
+// synchronous entry points, the ticket's lane for llfe_submit_batch / llfe_submit_images)
+static int read_attempts(llfe_ctx *ctx, int32_t n, const char *who, std::vector<KmeansAttemptOut> &a,
+                         int *n_colors) {
     if (ctx->any_inflight())
-        return ctx->fail(LLFE_ERR_INVALID, "llfe_kmeans_attempts with submitted batches not yet collected");
-    // the workspace the last k-means launch ran on (lane 0 for the synchronous entry points,
-    // the ticket's lane for llfe_submit_batch / llfe_submit_images)
+        return ctx->fail(LLFE_ERR_INVALID, "%s with submitted batches not yet collected", who);
     if (!ctx->km_last) return ctx->fail(LLFE_ERR_INVALID, "no k-means launch yet");
     Work &W = *ctx->km_last;
     if (n > W.km_n) return ctx->fail(LLFE_ERR_INVALID, "the last k-means launch had %d images", W.km_n);
-    if (W.km_colors > kMaxK) return ctx->fail(LLFE_ERR_UNSUPPORTED, "attempt records only for n_colors <= %d", kMaxK);
+    *n_colors = W.km_colors;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    std::vector<KmeansAttemptOut> a((size_t)n * kAttempts);
+    a.resize((size_t)n * kAttempts);
     HIPCHK(ctx, hipDeviceSynchronize());
     HIPCHK(ctx, hipMemcpy(a.data(), W.d_att.p, sizeof(KmeansAttemptOut) * a.size(), hipMemcpyDeviceToHost));
+    return LLFE_OK;
+}
+
+int llfe_kmeans_attempts_k(llfe_ctx *ctx, int32_t n, int32_t k_cap, float *pp_centers, float *centers,
+                           int32_t *counts, int32_t *iters, double *compactness) {
+    if (!ctx || !pp_centers || !centers || !counts || !iters || !compactness || n < 0 || k_cap < 1)
+        return LLFE_ERR_INVALID;
+    std::vector<KmeansAttemptOut> a;
+    int colors = 0;
+    if (int rc = read_attempts(ctx, n, __func__, a, &colors)) return rc;
+    if (colors > k_cap) return ctx->fail(LLFE_ERR_INVALID, "the last k-means launch had n_colors %d > k_cap", colors);
+    const bool big = colors > kMaxK;  // k_kmeans_big keeps its k-means++ centres in a field of its own
+    for (size_t i = 0; i < a.size(); i++) {
+        for (int k = 0; k < k_cap; k++) {
+            // an image's K = min(n_colors, U) rows: after Lloyd every cluster holds a point, and
+            // the kernels write zero counts past K; K <= 1 runs no attempt (iters 0)
+            const bool in = k < colors && a[i].iters > 0 && a[i].counts[k] > 0;
+            for (int j = 0; j < 3; j++) {
+                pp_centers[(i * k_cap + k) * 3 + j] = !in ? 0.f : big ? a[i].pp_centers_big[k][j] : a[i].pp_centers[k][j];
+                centers[(i * k_cap + k) * 3 + j] = in ? a[i].centers[k][j] : 0.f;
+            }
+            counts[i * k_cap + k] = in ? a[i].counts[k] : 0;
+        }
+        iters[i] = a[i].iters;
+        compactness[i] = a[i].compactness;
+    }
+    return LLFE_OK;
+}
+
+int llfe_kmeans_attempts(llfe_ctx *ctx, int32_t n, llfe_kmeans_attempt *out) {
+    if (!ctx || !out || n < 0) return LLFE_ERR_INVALID;
+    std::vector<KmeansAttemptOut> a;
+    int colors = 0;
+    if (int rc = read_attempts(ctx, n, __func__, a, &colors)) return rc;
+    if (colors > kMaxK) return ctx->fail(LLFE_ERR_UNSUPPORTED, "attempt records only for n_colors <= %d", kMaxK);
     for (size_t i = 0; i < a.size(); i++) {
         llfe_kmeans_attempt &r = out[i];
         std::memset(&r, 0, sizeof r);

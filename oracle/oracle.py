@@ -332,7 +332,9 @@ def kmeans_attempts(keys, K, rng_state, exact_sums=False, attempts=10):
     order; llfe_oracle.c orc_kmeans_ex): per attempt its k-means++ centres, final centres
     (float32, before astype(uint8)), counters, compactness, iterations and the centres after
     each Lloyd update.  exact_sums: the device's exact int64 cluster sums instead of
-    OpenCV's sequential float32 ones (kmeans.hip / DESIGN.md §5)."""
+    OpenCV's sequential float32 ones (kmeans.hip / DESIGN.md §5).  relocations,
+    relocations_max, relocation_ties: per attempt the points moved into empty clusters, the
+    most moves inside one Lloyd update, and the moves decided among equally far points."""
     keys = np.asarray(keys, np.uint32)
     data = np.ascontiguousarray(np.stack([(keys >> 16) & 255, (keys >> 8) & 255, keys & 255], -1), np.float32)
     N = data.shape[0]
@@ -345,10 +347,38 @@ def kmeans_attempts(keys, K, rng_state, exact_sums=False, attempts=10):
     cnt = np.zeros((attempts, K), np.int32)
     comp = np.zeros(attempts, np.float64)
     it = np.full((attempts, 100, K, 3), np.nan, np.float32)
+    reloc = np.zeros(attempts, np.int32)
+    rmax = np.zeros(attempts, np.int32)
+    ties = np.zeros(attempts, np.int32)
     c = lib().orc_kmeans_ex(_p(data), N, K, 200, C.c_double(0.2), attempts, C.c_uint64(rng_state), int(exact_sums),
-                            _p(labels), _p(best), _p(bcnt), _p(iters), _p(pp), _p(cen), _p(cnt), _p(comp), _p(it))
+                            _p(labels), _p(best), _p(bcnt), _p(iters), _p(pp), _p(cen), _p(cnt), _p(comp), _p(it),
+                            _p(reloc), _p(rmax), _p(ties))
     return {"compactness": c, "labels": labels, "centers": best, "counts": bcnt, "iters": iters, "pp": pp,
-            "att_centers": cen, "att_counts": cnt, "att_compactness": comp, "iter_centers": it}
+            "att_centers": cen, "att_counts": cnt, "att_compactness": comp, "iter_centers": it,
+            "relocations": reloc, "relocations_max": rmax, "relocation_ties": ties}
+
+
+def search_empty_cluster(gen, K, stream, runs, max_hits=64):
+    """The draw-and-run loop of tools/find_empty_cluster_cases.py (llfe_oracle.c
+    orc_search_empty_cluster): `runs` key sets of generator `gen` with K clusters, drawn from
+    the splitmix64 stream `stream`, through orc_kmeans_ex(exact_sums=1)
+    -> (list of hits, runs made); a hit is a dict with K, keys (uint32), s (the cv::RNG state
+    is image_rng_state(s, 0)), winner, and per attempt relocations, relocations_max,
+    relocation_ties, iters."""
+    info = np.zeros((max_hits, 64), np.int32)
+    keys = np.zeros((max_hits, 768), np.uint32)
+    done = C.c_int64(0)
+    n = lib().orc_search_empty_cluster(int(gen), int(K), C.c_uint64(int(stream) & MASK64), C.c_int64(int(runs)),
+                                       int(max_hits), _p(info), _p(keys), C.byref(done))
+    if n < 0:
+        raise ValueError("search_empty_cluster: gen in 0..3 and K in 2..32")
+    hits = []
+    for i in range(n):
+        o = info[i]
+        hits.append({"K": int(o[0]), "keys": keys[i, : o[1]].copy(), "s": int(o[2]), "winner": int(o[3]),
+                     "relocations": o[4:14].tolist(), "relocations_max": o[14:24].tolist(),
+                     "relocation_ties": o[24:34].tolist(), "iters": o[34:44].tolist()})
+    return hits, int(done.value)
 
 
 def dominant_colors(bgr, noise=None, n_colors=5, rng_state=0xFFFFFFFF):

@@ -11,7 +11,7 @@ Sections (the letters are the ones the tests use):
   A  keys of the production noise (and of caller noise) at the seams of k_uq_noise / k_uq_scatter
   B  every k-means attempt for K <= 5 through process(): cube and cell tables, batches of three
   C  every attempt of the plain-sweep path (llfe_kmeans on caller keys)
-  D  k_kmeans_big (K > 5): final record, through process() and llfe_kmeans
+  D  k_kmeans_big (K > 5): every attempt and the final record, through process() and llfe_kmeans
   E  image tables (llfe_submit_images), read in place and gathered
 
 What each row reaches (path: field / caller = k_uq_noise + k_uq_scatter with the noise field /
@@ -427,11 +427,14 @@ def e_expected(h, w, exact_sums=True):
 
 # ------------------------------------------------------------------------------- comparisons
 def attempts_equal(got, ex, K):
-    """Assert that the device's attempt records `got` (Backend.kmeans_attempts, one image)
-    equal the oracle's `ex`: k-means++ centres, Lloyd iterations, float32 centres and counts
-    exactly, compactness within 1e-6 relative."""
+    """Assert that the device's attempt records `got` (Backend.kmeans_attempts, one image; 5
+    rows, or k rows with k > 5) equal the oracle's `ex`: k-means++ centres, Lloyd iterations,
+    float32 centres and counts exactly, compactness within 1e-6 relative; centres and counts
+    past row K are zero."""
+    assert len(got) == ATTEMPTS
     for a in range(ATTEMPTS):
         g = got[a]
+        assert len(g["centers"]) >= K and not np.any(g["centers"][K:]) and not np.any(g["counts"][K:]), ("rows", a)
         assert np.array_equal(g["pp_centers"][:K], ex["pp"][a]), ("pp", a, g["pp_centers"][:K], ex["pp"][a])
         assert g["iters"] == int(ex["iters"][a]), ("iters", a, g["iters"], int(ex["iters"][a]))
         assert np.array_equal(g["centers"][:K], ex["att_centers"][a]), ("centers", a, g["centers"][:K],
@@ -444,7 +447,8 @@ def attempts_equal(got, ex, K):
 
 def final_is_best_attempt(centers_rgb, counts, got, K):
     """Assert that a final record is the device's own best attempt (k_kmeans_finalize): the
-    first attempt with the smallest compactness, its centres truncated to uint8."""
+    first attempt with the smallest compactness, its first K centres truncated to uint8."""
+    assert len(np.asarray(centers_rgb).reshape(-1, 3)) == K == len(counts)
     comp = [g["compactness"] for g in got]
     b = comp.index(min(comp))
     assert np.array_equal(np.asarray(centers_rgb), got[b]["centers"][:K].astype(np.uint8)), (b, centers_rgb)

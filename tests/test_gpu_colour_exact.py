@@ -17,7 +17,8 @@ choice, tie rule or prefix walk is a failure, not "another optimum".
      and the wave-range seams, with and without the key the kernel pads with
      (B and C also on "lattice" colours, channels below 32: colours at exactly the same distance
      from two centres, which only the first-minimum rule of the labelling orders)
-  D  k_kmeans_big (K = 6, 8, 32): the final record as a multiset, through both entry points
+  D  k_kmeans_big (K = 6, 8, 32): all 10 attempts (llfe_kmeans_attempts_k) and the final record
+     as a multiset, through both entry points
   E  llfe_submit_images on separately allocated device tensors, read in place and gathered
 """
 import ctypes as C
@@ -130,18 +131,24 @@ def test_d_big_k_process(backend, K, N):
     seed = cc.d_process_seed(K, N)
     x = cc.d_images(N)
     res = backend.process(x, ("colors",), seed=seed, index_base=cc.D_BASE, n_colors=K)
+    att = backend.kmeans_attempts(len(x), k=K)
     keys = cc.d_process_keys(N, seed)
     for i, ex in enumerate(cc.d_process_expected(K, N, seed)):
         assert res[i].n_unique == len(keys[i]), i
         _final_in(res[i].centers_rgb, res[i].counts, ex, K)
+        cc.attempts_equal(att[i], ex, K)
+        cc.final_is_best_attempt(res[i].centers_rgb, res[i].counts, att[i], K)
 
 
 @pytest.mark.parametrize("K,g", cc.D_KEYS)
 def test_d_big_k_caller_keys(backend, K, g):
     seed = cc.d_keys_seed(K, g)
     got = _kmeans_on_keys(backend, cc.d_caller_keys(K, g), K, seed, cc.D_BASE)
+    att = backend.kmeans_attempts(len(got), k=K)
     for i, ex in enumerate(cc.d_keys_expected(K, g, seed)):
         _final_in(got[i][0], got[i][1], ex, K)
+        cc.attempts_equal(att[i], ex, K)
+        cc.final_is_best_attempt(got[i][0], got[i][1], att[i], K)
 
 
 # ------------------------------------------------------------------------------------- E
