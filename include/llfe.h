@@ -532,7 +532,8 @@ int64_t llfe_jpeg_coef_slot_bytes(int32_t height, int32_t width);
  * holds every eligible image; with a smaller one (a 4:2:0 feed needs half) an image that
  * does not fit is LLFE_ERR_UNSUPPORTED like any other this path hands back.
  * status[i] per image; returns the first non-OK status, like llfe_decode_batch.  Eligible:
- * 8-bit, greyscale or YCbCr with chroma 1x1 and luma 1x1 / 2x1 / 2x2, EXIF orientation 1,
+ * 8-bit, greyscale or YCbCr with chroma 1x1 and luma 1x1 / 2x1 / 2x2, EXIF orientation 1 (or
+ * 2 .. 8 under LLFE_JPEG_ORIENT, which only the mixed-size entry points below take),
  * no libjpeg warning (a truncated scan is one), every progressive scan present; baseline,
  * progressive, optimised-Huffman, restart-interval and arithmetic files alike.  Anything
  * else (other formats included) is LLFE_ERR_UNSUPPORTED, or when this libjpeg lacks
@@ -567,14 +568,35 @@ typedef struct {
  * slot_bytes (the end of its last component as llfe_jpeg_read_coefs_batch lays a slot out,
  * rounded up to 16: a 4:2:0 file takes half a 4:4:4 slot) and slot_offset, the running sum;
  * *slots_bytes receives the total.  Any other image keeps slot_bytes = 0 and gets
- * LLFE_ERR_UNSUPPORTED (PNG, CMYK, an EXIF orientation other than 1, other samplings, 12-bit
- * files, other formats), LLFE_ERR_INVALID (corrupt data, a NULL blob) or LLFE_ERR_CAPACITY (a
+ * LLFE_ERR_UNSUPPORTED (PNG, CMYK, an EXIF orientation other than 1 unless LLFE_JPEG_ORIENT, other
+ * samplings, 12-bit files, other formats), LLFE_ERR_INVALID (corrupt data, a NULL blob) or LLFE_ERR_CAPACITY (a
  * size above LLFE_MAX_PIXELS, as llfe_image_info); its size is still written when the header
  * gave one, else 0 x 0.  out_offset is not touched: the caller lays out the output, because it
  * knows the sizes of the images its other decoder takes.  status[i] per image; returns the
  * first non-OK status. */
 int llfe_jpeg_images_layout(const uint8_t *const *data, const uint64_t *sizes, int32_t n, llfe_jpeg_image *images,
                             int64_t *slots_bytes, int32_t *status, int32_t threads);
+/* EXIF orientation on the device (opt-in).  The flag is the same bit in every flags word of the
+ * mixed-size entry points; any other bit there is LLFE_ERR_INVALID, and so is this one in the
+ * same-size entry points (llfe_jpeg_parse_batch_flags).  With it a JPEG whose EXIF orientation
+ * (tag 0x0112 of IFD0) is 2 .. 8 is eligible like the same file without EXIF: its slot, its
+ * descriptor and its record are byte for byte that file's, llfe_jpeg_image.height / width stay
+ * the coded size, and the orientation travels beside the records as one byte per image.
+ * llfe_jpeg_reconstruct_images_oriented then writes the result Pillow's
+ * ImageOps.exif_transpose gives (csrc/jpeg_orient.h holds the map): height x width for 1 .. 4,
+ * width x height for 5 .. 8.  A tag value outside 1 .. 8 keeps LLFE_ERR_UNSUPPORTED. */
+#define LLFE_JPEG_ORIENT 4u
+/* llfe_jpeg_images_layout with flags.  orientation (n bytes; may be NULL without
+ * LLFE_JPEG_ORIENT) receives 1 for every image, and with LLFE_JPEG_ORIENT the EXIF orientation
+ * 2 .. 8 of an eligible JPEG that has one.  flags = 0 is llfe_jpeg_images_layout. */
+int llfe_jpeg_images_layout_flags(const uint8_t *const *data, const uint64_t *sizes, int32_t n, llfe_jpeg_image *images,
+                                  int64_t *slots_bytes, int32_t *status, int32_t threads, uint8_t *orientation,
+                                  uint32_t flags);
+/* host only: the CPU twin of the orientation store of csrc/jpeg_images.hip.  src_bgr (h x w x 3)
+ * -> dst_bgr (h x w x 3 for orientation 1 .. 4, w x h x 3 for 5 .. 8) through the map of
+ * csrc/jpeg_orient.h; LLFE_ERR_INVALID for an orientation outside 1 .. 8, a NULL pointer or a
+ * size below 1. */
+int llfe_jpeg_orient_reference(const uint8_t *src_bgr, int32_t h, int32_t w, int32_t orientation, uint8_t *dst_bgr);
 /* host only, no ctx: llfe_jpeg_read_coefs_batch with each image's own height, width and slot
  * (images[i], as laid out above) in slots (host, slots_bytes bytes).  The llfe_jpeg_desc offsets
  * stay relative to the image's slot.  status[i] as llfe_jpeg_read_coefs_batch's: an image that
@@ -585,6 +607,11 @@ int llfe_jpeg_images_layout(const uint8_t *const *data, const uint64_t *sizes, i
 int llfe_jpeg_read_coefs_images(const uint8_t *const *data, const uint64_t *sizes, int32_t n,
                                 const llfe_jpeg_image *images, uint8_t *slots, int64_t slots_bytes,
                                 llfe_jpeg_desc *descs, int32_t *status, int32_t threads);
+/* the same with flags: LLFE_JPEG_ORIENT takes files with an EXIF orientation 2 .. 8 as well and
+ * changes nothing else; any other bit is LLFE_ERR_INVALID */
+int llfe_jpeg_read_coefs_images_flags(const uint8_t *const *data, const uint64_t *sizes, int32_t n,
+                                      const llfe_jpeg_image *images, uint8_t *slots, int64_t slots_bytes,
+                                      llfe_jpeg_desc *descs, int32_t *status, int32_t threads, uint32_t flags);
 /* the device half: coefs (device, coefs_bytes bytes, 16-byte aligned, as staged above) -> out
  * (device, out_capacity bytes), image i packed height x width x 3 at images[i].out_offset.
  * images and descs are host arrays, validated on the host before anything is launched; for
@@ -597,6 +624,17 @@ int llfe_jpeg_read_coefs_images(const uint8_t *const *data, const uint64_t *size
 int llfe_jpeg_reconstruct_images(llfe_ctx *ctx, const uint8_t *coefs, int64_t coefs_bytes, const llfe_jpeg_image *images,
                                  const llfe_jpeg_desc *descs, int32_t n, uint8_t *out, int64_t out_capacity,
                                  llfe_stream stream);
+/* the same with an EXIF orientation per image (host array of n bytes, 1 .. 8; NULL: all 1, which
+ * is llfe_jpeg_reconstruct_images): image i's result at images[i].out_offset is the coded
+ * height x width raster re-indexed as csrc/jpeg_orient.h says, packed height x width x 3 for
+ * 1 .. 4 and width x height x 3 for 5 .. 8 -- the same height * width * 3 bytes, which is what the
+ * overlap and capacity checks count.  An orientation outside 1 .. 8 of an image with n_comp != 0
+ * is LLFE_ERR_INVALID with out untouched.  The images are reconstructed by orientation group
+ * (1; 2 .. 4; 5 .. 8), at most three launches. */
+int llfe_jpeg_reconstruct_images_oriented(llfe_ctx *ctx, const uint8_t *coefs, int64_t coefs_bytes,
+                                          const llfe_jpeg_image *images, const llfe_jpeg_desc *descs,
+                                          const uint8_t *orientation, int32_t n, uint8_t *out, int64_t out_capacity,
+                                          llfe_stream stream);
 /* host only: the output tile of csrc/jpeg_images.hip for a sampling class (LLFE_JPEG_*), a
  * multiple of the class's MCU, so that tests can stand on its seams; LLFE_ERR_INVALID for an
  * unknown class */
@@ -639,7 +677,8 @@ typedef struct {
  * Se = 63, Ah = Al = 0, table ids 0 or 1, no restart interval, every referenced DHT present
  * and a valid prefix code, and the scan ending at an FF D9 that is the first marker after it.
  * Anything else is LLFE_ERR_UNSUPPORTED (progressive, arithmetic, restart intervals,
- * multi-scan, EXIF orientation != 1, CMYK, other formats): nothing is written for it,
+ * multi-scan, EXIF orientation != 1 unless LLFE_JPEG_ORIENT (llfe_jpeg_parse_images only), CMYK,
+ * other formats): nothing is written for it,
  * descs[i].n_comp and scans[i].blocks_in_mcu are 0, and it takes llfe_jpeg_read_coefs_batch
  * or llfe_decode_batch.  status[i] per image; returns the first non-OK status.  This is
  * llfe_jpeg_parse_batch_flags with flags = 0: every record it stages has restart_interval 0. */
@@ -705,7 +744,8 @@ int llfe_jpeg_records_layout(const uint64_t *sizes, const llfe_jpeg_image *image
  * slot_bytes (images[i]) and its record at record_offsets[i] in staging (host, staging_bytes
  * bytes).  The llfe_jpeg_desc offsets are relative to the image's tight slot: byte for byte the
  * descriptor llfe_jpeg_read_coefs_images produces for the file.  The same eligibility rules and
- * the same flags.  status[i] as llfe_jpeg_parse_batch's: a file that does not fit its slot_bytes
+ * the same flags, and LLFE_JPEG_ORIENT on top (files with an EXIF orientation 2 .. 8 are taken
+ * and staged as the same file without EXIF).  status[i] as llfe_jpeg_parse_batch's: a file that does not fit its slot_bytes
  * is LLFE_ERR_UNSUPPORTED, another size than its record says LLFE_ERR_CAPACITY; slot_bytes == 0
  * is LLFE_ERR_UNSUPPORTED and nothing is read.  A record (as llfe_jpeg_records_layout sizes it)
  * outside staging_bytes, or one not 16-byte aligned, is LLFE_ERR_INVALID for the whole call,

@@ -207,6 +207,7 @@ JPEG_GRAY, JPEG_444, JPEG_422, JPEG_420 = 1, 2, 3, 4  # LLFE_JPEG_*
 JPEG_HUFF_TABLE_BYTES, JPEG_RECORD_HEADER = 400, 2048  # LLFE_JPEG_HUFF_TABLE_BYTES, LLFE_JPEG_RECORD_HEADER
 JPEG_SUBSEQUENCE_BYTES = 128  # csrc/jpeg_huff_core.h kSub
 JPEG_PARSE_RESTARTS = 1  # LLFE_JPEG_PARSE_RESTARTS
+JPEG_ORIENT = 4  # LLFE_JPEG_ORIENT
 
 # every symbol declared in include/llfe.h, with its ctypes signature
 _vp, _i32, _i64, _u32, _u64 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_uint64
@@ -285,6 +286,13 @@ SIGNATURES = {
                                               C.POINTER(LlfeJpegDesc), _vp, _i32]),
     "llfe_jpeg_reconstruct_images": (C.c_int, [_vp, _vp, _i64, C.POINTER(LlfeJpegImage), C.POINTER(LlfeJpegDesc), _i32,
                                                _vp, _i64, _vp]),
+    "llfe_jpeg_images_layout_flags": (C.c_int, [_vp, _vp, _i32, C.POINTER(LlfeJpegImage), C.POINTER(_i64), _vp, _i32,
+                                                _vp, _u32]),
+    "llfe_jpeg_orient_reference": (C.c_int, [_vp, _i32, _i32, _i32, _vp]),
+    "llfe_jpeg_read_coefs_images_flags": (C.c_int, [_vp, _vp, _i32, C.POINTER(LlfeJpegImage), _vp, _i64,
+                                                    C.POINTER(LlfeJpegDesc), _vp, _i32, _u32]),
+    "llfe_jpeg_reconstruct_images_oriented": (C.c_int, [_vp, _vp, _i64, C.POINTER(LlfeJpegImage),
+                                                        C.POINTER(LlfeJpegDesc), _vp, _i32, _vp, _i64, _vp]),
     "llfe_jpeg_images_tiling": (C.c_int, [_i32, C.POINTER(_i32), C.POINTER(_i32)]),
     "llfe_jpeg_parse_batch": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _i64, _i64, C.POINTER(LlfeJpegDesc),
                                         C.POINTER(LlfeJpegScan), _vp, _i32]),

@@ -586,7 +586,7 @@ class Backend:
                    self._stream(coefs))
         return out
 
-    def jpeg_reconstruct_images(self, coefs, images, descs, out):
+    def jpeg_reconstruct_images(self, coefs, images, descs, out, orientation=None):
         """The device half of a JPEG decode of images of any sizes (llfe_jpeg_reconstruct_images):
         ``coefs`` a 1-d uint8 device tensor of staged coefficient slots, ``images`` / ``descs`` the n
         llfe_jpeg_image / llfe_jpeg_desc records (decode.stage_coefs_images, with every
@@ -594,7 +594,10 @@ class Backend:
         height x width x 3 BGR at its out_offset, on the current stream.  Images whose descriptor
         has n_comp == 0 are left untouched in ``out``.  A record that points outside its slot,
         ``coefs`` or ``out``, or into another image's result, raises LlfeError (LLFE_ERR_INVALID,
-        or LLFE_ERR_CAPACITY when only ``out`` is short) before any launch.  -> ``out``."""
+        or LLFE_ERR_CAPACITY when only ``out`` is short) before any launch.  ``orientation``: the
+        EXIF orientation 1 .. 8 of every image (llfe_jpeg_reconstruct_images_oriented): image i is
+        written as decode_bgr returns it, width x height x 3 for 5 .. 8; a value outside 1 .. 8 is
+        refused the same way.  -> ``out``."""
         torch = _torch()
         for name, t in (("coefs", coefs), ("out", out)):
             if not (_is_torch(t) and t.is_cuda and t.dtype == torch.uint8 and t.dim() == 1 and t.is_contiguous()):
@@ -605,8 +608,17 @@ class Backend:
         n = len(images)
         if len(descs) != n:
             raise ValueError(f"jpeg_reconstruct_images: {len(descs)} descriptors for {n} image records")
-        self._call("llfe_jpeg_reconstruct_images", coefs.data_ptr(), coefs.numel(), images, descs, n, out.data_ptr(),
-                   out.numel(), self._stream(coefs))
+        if orientation is None:
+            self._call("llfe_jpeg_reconstruct_images", coefs.data_ptr(), coefs.numel(), images, descs, n, out.data_ptr(),
+                       out.numel(), self._stream(coefs))
+            return out
+        if len(orientation) != n:
+            raise ValueError(f"jpeg_reconstruct_images: {len(orientation)} orientations for {n} image records")
+        if any(not 0 <= int(o) <= 255 for o in orientation):
+            raise ValueError("jpeg_reconstruct_images: an orientation is one byte")
+        orient = (C.c_uint8 * n)(*[int(o) for o in orientation])
+        self._call("llfe_jpeg_reconstruct_images_oriented", coefs.data_ptr(), coefs.numel(), images, descs, orient, n,
+                   out.data_ptr(), out.numel(), self._stream(coefs))
         return out
 
     def jpeg_entropy_decode(self, records, scans, descs, h: int, w: int, slots) -> list:

@@ -37,6 +37,7 @@
 
 #include "jpeg_desc_check.h"
 #include "jpeg_huff_core.h"
+#include "jpeg_orient.h"
 #include "llfe.h"
 
 namespace llfe_jpeg {
@@ -255,6 +256,14 @@ int exif_orientation(const uint8_t *d, size_t n) {
     return 1;
 }
 
+// what the coefficient and record paths take: no rotation, or (orient: LLFE_JPEG_ORIENT) one the
+// device applies (jpeg_orient.h); *o receives the value, 1 where the file has none
+bool orientation_taken(const uint8_t *d, size_t n, bool orient, int *o = nullptr) {
+    const int v = exif_orientation(d, n);
+    if (o) *o = v;
+    return v == 1 || (orient && llfe::jpeg_orient_valid(v));
+}
+
 // header only (sizes); returns LLFE_OK / error code
 int info(const uint8_t *data, size_t size, int32_t *w, int32_t *h, int *ncomp) {
     const Api &A = api();
@@ -389,11 +398,11 @@ int geometry(const ComponentInfo *comp, int nc, int sampling, int32_t h, int32_t
 // entropy-decode one image and copy its quantised coefficients and tables into `slot`.
 // Every eligibility check comes before the first byte is written.
 int read_coefs(const uint8_t *data, size_t size, int32_t h, int32_t w, uint8_t *slot, int64_t slot_bytes,
-               llfe_jpeg_desc *desc) {
+               llfe_jpeg_desc *desc, bool orient = false) {
     const Api &A = api();
     if (!A.ok || !A.read_coefficients) return LLFE_ERR_UNSUPPORTED;
     if (size < 3 || data[0] != 0xFF || data[1] != 0xD8 || data[2] != 0xFF) return LLFE_ERR_UNSUPPORTED;
-    if (exif_orientation(data, size) != 1) return LLFE_ERR_UNSUPPORTED;
+    if (!orientation_taken(data, size, orient)) return LLFE_ERR_UNSUPPORTED;
     Decompress ci;
     Err err;
     memset(&ci, 0, sizeof ci);
@@ -452,10 +461,12 @@ int read_coefs(const uint8_t *data, size_t size, int32_t h, int32_t w, uint8_t *
 
 // llfe_jpeg_images_layout for one JPEG, headers only: its size (written once the header gave
 // one, else 0 x 0) and, for a file read_coefs would take as far as its header tells, the tight
-// bytes of its slot -- the end of its last component as geometry() lays a slot out, up to 16
-int layout_one(const uint8_t *data, size_t size, int32_t *h, int32_t *w, int64_t *slot_bytes) {
+// bytes of its slot -- the end of its last component as geometry() lays a slot out, up to 16.
+// orientation: NULL, or (LLFE_JPEG_ORIENT) where the EXIF orientation of a file that is taken goes
+int layout_one(const uint8_t *data, size_t size, int32_t *h, int32_t *w, int64_t *slot_bytes, uint8_t *orientation) {
     *h = *w = 0;
     *slot_bytes = 0;
+    if (orientation) *orientation = 1;
     const Api &A = api();
     if (!A.ok || !A.read_coefficients) return LLFE_ERR_UNSUPPORTED;
     if (size < 3 || data[0] != 0xFF || data[1] != 0xD8 || data[2] != 0xFF) return LLFE_ERR_UNSUPPORTED;
@@ -479,11 +490,14 @@ int layout_one(const uint8_t *data, size_t size, int32_t *h, int32_t *w, int64_t
     llfe_jpeg_desc d;
     memset(&d, 0, sizeof d);
     const ComponentInfo *comp = (const ComponentInfo *)ci.comp_info;
-    volatile int rc = exif_orientation(data, size) != 1 ? LLFE_ERR_UNSUPPORTED : classify(ci, comp, *h, *w, &sampling);
+    int o = 1;
+    volatile int rc = !orientation_taken(data, size, orientation != nullptr, &o) ? LLFE_ERR_UNSUPPORTED
+                                                                                   : classify(ci, comp, *h, *w, &sampling);
     if (rc == LLFE_OK) rc = geometry(comp, ci.num_components, sampling, *h, *w, INT64_MAX, false, &d);
     if (rc == LLFE_OK) {
         const auto &k = d.comp[d.n_comp - 1];
         *slot_bytes = (k.coef_offset + (int64_t)k.blocks_w * k.blocks_h * 128 + 15) & ~(int64_t)15;
+        if (orientation) *orientation = (uint8_t)o;
     }
     A.destroy(&ci);
     return rc;
@@ -603,11 +617,12 @@ int walk(const uint8_t *d, size_t n, Dht (&dht)[4], Walk &W, bool restarts) {
 // parse one image and stage its record; every eligibility check comes before the first byte is
 // written
 int parse_one(const uint8_t *data, size_t size, int32_t h, int32_t w, uint8_t *rec, int64_t record_offset,
-              int64_t record_stride, int64_t slot_bytes, llfe_jpeg_desc *desc, llfe_jpeg_scan *scan, bool restarts) {
+              int64_t record_stride, int64_t slot_bytes, llfe_jpeg_desc *desc, llfe_jpeg_scan *scan, bool restarts,
+              bool orient = false) {
     const Api &A = api();
     if (!A.ok) return LLFE_ERR_UNSUPPORTED;
     if (size < 3 || data[0] != 0xFF || data[1] != 0xD8 || data[2] != 0xFF) return LLFE_ERR_UNSUPPORTED;
-    if (exif_orientation(data, size) != 1) return LLFE_ERR_UNSUPPORTED;
+    if (!orientation_taken(data, size, orient)) return LLFE_ERR_UNSUPPORTED;
     Decompress ci;
     Err err;
     memset(&ci, 0, sizeof ci);
@@ -818,13 +833,39 @@ extern "C" int llfe_jpeg_read_coefs_batch(const uint8_t *const *data, const uint
 
 // used by png_decode.cpp's llfe_jpeg_images_layout (which owns the format dispatch and the pixel limit)
 int llfe_jpeg_layout_one(const uint8_t *data, size_t size, int32_t *h, int32_t *w, int64_t *slot_bytes) {
-    return llfe_jpeg::layout_one(data, size, h, w, slot_bytes);
+    return llfe_jpeg::layout_one(data, size, h, w, slot_bytes, nullptr);
+}
+// the same with LLFE_JPEG_ORIENT (orientation not NULL: files with an EXIF orientation 2 .. 8 too)
+int llfe_jpeg_layout_one_oriented(const uint8_t *data, size_t size, int32_t *h, int32_t *w, int64_t *slot_bytes,
+                                  uint8_t *orientation) {
+    return llfe_jpeg::layout_one(data, size, h, w, slot_bytes, orientation);
+}
+
+extern "C" int llfe_jpeg_orient_reference(const uint8_t *src_bgr, int32_t h, int32_t w, int32_t orientation,
+                                          uint8_t *dst_bgr) {
+    if (!src_bgr || !dst_bgr || h <= 0 || w <= 0 || !llfe::jpeg_orient_valid(orientation)) return LLFE_ERR_INVALID;
+    const int64_t row = llfe::jpeg_orient_row(orientation, h, w);
+    for (int32_t y = 0; y < h; y++)
+        for (int32_t x = 0; x < w; x++) {
+            int yr, xr;
+            llfe::jpeg_orient_map(orientation, h, w, y, x, &yr, &xr);
+            memcpy(dst_bgr + (yr * row + xr) * 3, src_bgr + ((int64_t)y * w + x) * 3, 3);
+        }
+    return LLFE_OK;
 }
 
 extern "C" int llfe_jpeg_read_coefs_images(const uint8_t *const *data, const uint64_t *sizes, int32_t n,
                                            const llfe_jpeg_image *images, uint8_t *slots, int64_t slots_bytes,
                                            llfe_jpeg_desc *descs, int32_t *status, int32_t threads) {
-    if (n < 0 || (n && (!data || !sizes || !images || !slots || !descs || !status)) || slots_bytes < 0)
+    return llfe_jpeg_read_coefs_images_flags(data, sizes, n, images, slots, slots_bytes, descs, status, threads, 0);
+}
+
+extern "C" int llfe_jpeg_read_coefs_images_flags(const uint8_t *const *data, const uint64_t *sizes, int32_t n,
+                                                 const llfe_jpeg_image *images, uint8_t *slots, int64_t slots_bytes,
+                                                 llfe_jpeg_desc *descs, int32_t *status, int32_t threads,
+                                                 uint32_t flags) {
+    if ((flags & ~LLFE_JPEG_ORIENT) || n < 0 || (n && (!data || !sizes || !images || !slots || !descs || !status)) ||
+        slots_bytes < 0)
         return LLFE_ERR_INVALID;
     for (int i = 0; i < n; i++) {  // every slot inside the buffer, before the first byte is written
         const llfe_jpeg_image &m = images[i];
@@ -846,7 +887,7 @@ extern "C" int llfe_jpeg_read_coefs_images(const uint8_t *const *data, const uin
                      : m.height <= 0 || m.width <= 0 || m.height > 65535 || m.width > 65535
                          ? LLFE_ERR_CAPACITY  // (no JPEG has that size)
                          : llfe_jpeg::read_coefs(data[i], (size_t)sizes[i], m.height, m.width, slots + m.slot_offset,
-                                                 m.slot_bytes, &descs[i]);
+                                                 m.slot_bytes, &descs[i], (flags & LLFE_JPEG_ORIENT) != 0);
             } catch (const std::bad_alloc &) {
                 rc = LLFE_ERR_OOM;
             }
@@ -970,7 +1011,7 @@ extern "C" int llfe_jpeg_parse_images(const uint8_t *const *data, const uint64_t
                                       const llfe_jpeg_image *images, const int64_t *record_offsets, uint8_t *staging,
                                       int64_t staging_bytes, llfe_jpeg_desc *descs, llfe_jpeg_scan *scans, int32_t *status,
                                       int32_t threads, uint32_t flags) {
-    if ((flags & ~LLFE_JPEG_PARSE_RESTARTS) || n < 0 ||
+    if ((flags & ~(LLFE_JPEG_PARSE_RESTARTS | LLFE_JPEG_ORIENT)) || n < 0 ||
         (n && (!data || !sizes || !images || !record_offsets || !staging || !descs || !scans || !status)) ||
         staging_bytes < 0)
         return LLFE_ERR_INVALID;
@@ -996,7 +1037,8 @@ extern "C" int llfe_jpeg_parse_images(const uint8_t *const *data, const uint64_t
                          ? LLFE_ERR_CAPACITY  // (no JPEG has that size)
                          : llfe_jpeg::parse_one(data[i], (size_t)sizes[i], m.height, m.width, staging + record_offsets[i],
                                                 record_offsets[i], llfe_jpeg::record_bytes(sizes[i]), m.slot_bytes,
-                                                &descs[i], &scans[i], (flags & LLFE_JPEG_PARSE_RESTARTS) != 0);
+                                                &descs[i], &scans[i], (flags & LLFE_JPEG_PARSE_RESTARTS) != 0,
+                                                (flags & LLFE_JPEG_ORIENT) != 0);
             } catch (const std::bad_alloc &) {
                 rc = LLFE_ERR_OOM;
             }

@@ -25,6 +25,9 @@ struct JpegTiling {
 };
 constexpr int kJpegImgYBytes = 144 * 64;  // the largest luma plane (4:2:0: 128 x 64 at pitch 144)
 constexpr int kJpegImgCBytes = 80 * 48;   // the largest chroma plane (4:2:0: 80 x 48 at pitch 80)
+// orientations 5 .. 8 stage a tile in result order, a dword per pixel, tw rows at a pitch of
+// th + 3 dwords, in the kernel's IDCT scratch of [8][9]-int tiles: the largest is 4:2:0's
+constexpr int kJpegOrientStageTiles = (128 * (64 + 3) + 71) / 72;
 
 LLFE_DESC_HD bool jpeg_tiling(int sampling, JpegTiling *t) {
     switch (sampling) {
@@ -42,7 +45,8 @@ struct JpegImageRec {
     int64_t slot_offset, out_offset;  // bytes from coefs / out
     int32_t h, w;
     int32_t tiles_x;  // tiles per row of tiles
-    int32_t vec;      // rows are 4-byte aligned: dword stores
+    int32_t vec;      // the result's rows are 4-byte aligned: dword stores
+    int32_t orient;   // EXIF orientation 1 .. 8 (jpeg_orient.h); h, w stay the coded size
 };
 struct JpegWork {
     int32_t image, tile;

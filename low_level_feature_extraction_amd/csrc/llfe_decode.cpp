@@ -8,6 +8,7 @@
 
 #include "jpeg_huff_core.h"
 #include "jpeg_images.h"
+#include "jpeg_orient.h"
 #include "llfe_ctx.h"
 #include "png_inflate_core.h"
 
@@ -199,6 +200,14 @@ int llfe_jpeg_images_tiling(int32_t sampling, int32_t *tile_w, int32_t *tile_h) 
 int llfe_jpeg_reconstruct_images(llfe_ctx *ctx, const uint8_t *coefs, int64_t coefs_bytes, const llfe_jpeg_image *images,
                                  const llfe_jpeg_desc *descs, int32_t n, uint8_t *out, int64_t out_capacity,
                                  llfe_stream stream) {
+    return llfe_jpeg_reconstruct_images_oriented(ctx, coefs, coefs_bytes, images, descs, nullptr, n, out, out_capacity,
+                                                 stream);
+}
+
+int llfe_jpeg_reconstruct_images_oriented(llfe_ctx *ctx, const uint8_t *coefs, int64_t coefs_bytes,
+                                          const llfe_jpeg_image *images, const llfe_jpeg_desc *descs,
+                                          const uint8_t *orientation, int32_t n, uint8_t *out, int64_t out_capacity,
+                                          llfe_stream stream) {
     using llfe::JpegImageRec;
     using llfe::JpegWork;
     if (!ctx) return LLFE_ERR_INVALID;
@@ -210,7 +219,8 @@ int llfe_jpeg_reconstruct_images(llfe_ctx *ctx, const uint8_t *coefs, int64_t co
     std::vector<JpegImageRec> recs;
     std::vector<std::pair<int64_t, int64_t>> ranges;  // [begin, end) of every result
     int64_t n_work = 0, out_end = 0;
-    double bytes = 0;
+    int64_t group_work[llfe::kJpegOrientGroups] = {0, 0, 0};  // tiles per orientation group
+    double group_bytes[llfe::kJpegOrientGroups] = {0, 0, 0};
     try {
         recs.reserve((size_t)n);
         ranges.reserve((size_t)n);
@@ -218,6 +228,7 @@ int llfe_jpeg_reconstruct_images(llfe_ctx *ctx, const uint8_t *coefs, int64_t co
             const llfe_jpeg_desc &d = descs[i];
             if (d.n_comp == 0) continue;  // staged elsewhere: its place in out stays as it is
             const llfe_jpeg_image &m = images[i];
+            const int o = orientation ? orientation[i] : 1;
             int64_t blocks = 0;
             llfe::JpegTiling t;
             if (m.height <= 0 || m.width <= 0 || m.height > 65535 || m.width > 65535 || m.slot_offset < 0 ||
@@ -227,6 +238,8 @@ int llfe_jpeg_reconstruct_images(llfe_ctx *ctx, const uint8_t *coefs, int64_t co
                 return ctx->fail(LLFE_ERR_INVALID, "llfe_jpeg_reconstruct_images: image %d: a record or descriptor "
                                                    "points outside its slot, the coefficient buffer or does not "
                                                    "cover %dx%d", i, m.width, m.height);
+            if (!llfe::jpeg_orient_valid(o))
+                return ctx->fail(LLFE_ERR_INVALID, "llfe_jpeg_reconstruct_images: image %d: orientation %d", i, o);
             JpegImageRec r;
             r.d = d;
             r.slot_offset = m.slot_offset;
@@ -234,14 +247,20 @@ int llfe_jpeg_reconstruct_images(llfe_ctx *ctx, const uint8_t *coefs, int64_t co
             r.h = m.height;
             r.w = m.width;
             r.tiles_x = (m.width + t.tw - 1) / t.tw;
-            r.vec = (m.width % 4 == 0 && ((uintptr_t)out & 3) == 0) ? 1 : 0;
+            // (the result's row length: the coded height for a transposed result)
+            r.vec = (llfe::jpeg_orient_row(o, m.height, m.width) % 4 == 0 && ((uintptr_t)out & 3) == 0) ? 1 : 0;
+            r.orient = o;
             recs.push_back(r);
-            const int64_t px_bytes = (int64_t)m.height * m.width * 3;
+            const int64_t px_bytes = (int64_t)m.height * m.width * 3;  // (the same for both shapes)
             ranges.emplace_back(m.out_offset, m.out_offset + px_bytes);
             out_end = std::max(out_end, m.out_offset + px_bytes);
-            n_work += (int64_t)r.tiles_x * ((m.height + t.th - 1) / t.th);
-            for (int c = 0; c < d.n_comp; c++) bytes += (double)d.comp[c].blocks_w * d.comp[c].blocks_h * 128 + 128;
-            bytes += (double)px_bytes;
+            const int64_t tiles = (int64_t)r.tiles_x * ((m.height + t.th - 1) / t.th);
+            n_work += tiles;
+            const int g = llfe::jpeg_orient_group(o);
+            group_work[g] += tiles;
+            for (int c = 0; c < d.n_comp; c++)
+                group_bytes[g] += (double)d.comp[c].blocks_w * d.comp[c].blocks_h * 128 + 128;
+            group_bytes[g] += (double)px_bytes;
         }
         std::sort(ranges.begin(), ranges.end());
         for (size_t k = 1; k < ranges.size(); k++)
@@ -256,26 +275,38 @@ int llfe_jpeg_reconstruct_images(llfe_ctx *ctx, const uint8_t *coefs, int64_t co
         if (recs.empty()) return LLFE_OK;
         HIPCHK(ctx, hipSetDevice(ctx->device));
         hipStream_t s = (hipStream_t)stream;
-        // the records, then the work table, through one pinned buffer
+        // the records, then the work table (one part per orientation group: a launch is uniform),
+        // through one pinned buffer
         const size_t rec_bytes = (recs.size() * sizeof(JpegImageRec) + 15) & ~(size_t)15;
         const size_t tab_bytes = rec_bytes + (size_t)n_work * sizeof(JpegWork);
         HIPCHK(ctx, ctx->h_jpeg_img_tab.ensure(tab_bytes));
         HIPCHK(ctx, ctx->d_jpeg_img_tab.ensure(tab_bytes));
         std::memcpy(ctx->h_jpeg_img_tab.p, recs.data(), recs.size() * sizeof(JpegImageRec));
         JpegWork *wk = (JpegWork *)(ctx->h_jpeg_img_tab.p + rec_bytes);
-        for (size_t k = 0; k < recs.size(); k++) {
-            llfe::JpegTiling t;
-            llfe::jpeg_tiling(recs[k].d.sampling, &t);
-            const int tiles = recs[k].tiles_x * ((recs[k].h + t.th - 1) / t.th);
-            for (int q = 0; q < tiles; q++) *wk++ = JpegWork{(int32_t)k, q};
+        for (int g = 0; g < llfe::kJpegOrientGroups; g++) {
+            if (group_work[g] == 0) continue;
+            for (size_t k = 0; k < recs.size(); k++) {
+                if (llfe::jpeg_orient_group(recs[k].orient) != g) continue;
+                llfe::JpegTiling t;
+                llfe::jpeg_tiling(recs[k].d.sampling, &t);
+                const int tiles = recs[k].tiles_x * ((recs[k].h + t.th - 1) / t.th);
+                for (int q = 0; q < tiles; q++) *wk++ = JpegWork{(int32_t)k, q};
+            }
         }
         HIPCHK(ctx, hipMemcpyAsync(ctx->d_jpeg_img_tab.p, ctx->h_jpeg_img_tab.p, tab_bytes, hipMemcpyHostToDevice, s));
         {
             StageSlotScope tag(ctx->prof);
             // coefficients and tables in, BGR out: no plane goes through memory
-            TIMED(ctx, s, "k_jpeg_images", bytes,
-                  llfe::launch_jpeg_images(coefs, (const JpegImageRec *)ctx->d_jpeg_img_tab.p,
-                                           (const JpegWork *)(ctx->d_jpeg_img_tab.p + rec_bytes), (int)n_work, out, s));
+            static const char *const names[llfe::kJpegOrientGroups] = {"k_jpeg_images", "k_jpeg_images_mirrored",
+                                                                       "k_jpeg_images_transposed"};
+            const JpegWork *d_work = (const JpegWork *)(ctx->d_jpeg_img_tab.p + rec_bytes);
+            for (int g = 0; g < llfe::kJpegOrientGroups; g++) {
+                if (group_work[g] == 0) continue;
+                TIMED(ctx, s, names[g], group_bytes[g],
+                      llfe::launch_jpeg_images(coefs, (const JpegImageRec *)ctx->d_jpeg_img_tab.p, d_work,
+                                               (int)group_work[g], out, g, s));
+                d_work += group_work[g];
+            }
         }
         HIPCHK(ctx, hipStreamSynchronize(s));  // (the pinned table is free again)
         ctx->prof.collect(Profiler::kStageSlot);

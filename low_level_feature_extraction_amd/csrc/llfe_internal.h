@@ -416,11 +416,12 @@ hipError_t launch_jpeg_reconstruct(const uint8_t *coefs, int64_t slot_stride, co
 
 // llfe_jpeg_reconstruct_images (jpeg_images.hip; records and tiling in jpeg_images.h): one
 // launch over n_work (image, tile) entries; d_recs holds the validated records of the call's
-// images, coefs / out are the bases their slot / result offsets count from.
+// images, coefs / out are the bases their slot / result offsets count from.  group: the
+// orientation group (jpeg_orient.h jpeg_orient_group) of every image the entries name.
 struct JpegImageRec;
 struct JpegWork;
 hipError_t launch_jpeg_images(const uint8_t *coefs, const JpegImageRec *d_recs, const JpegWork *d_work, int n_work,
-                              uint8_t *out, hipStream_t s);
+                              uint8_t *out, int group, hipStream_t s);
 
 // llfe_jpeg_entropy_decode and llfe_jpeg_entropy_decode_images (jpeg_huff.hip).  The scans and
 // descriptors are validated on the host first (jpeg_huff_core.h validate_scans,

@@ -592,10 +592,22 @@ extern "C" int llfe_image_info(const uint8_t *data, uint64_t size, int32_t *widt
 }
 
 int llfe_jpeg_layout_one(const uint8_t *data, size_t size, int32_t *h, int32_t *w, int64_t *slot_bytes);
+int llfe_jpeg_layout_one_oriented(const uint8_t *data, size_t size, int32_t *h, int32_t *w, int64_t *slot_bytes,
+                                  uint8_t *orientation);
 
 extern "C" int llfe_jpeg_images_layout(const uint8_t *const *data, const uint64_t *sizes, int32_t n,
                                        llfe_jpeg_image *images, int64_t *slots_bytes, int32_t *status, int32_t threads) {
-    if (n < 0 || !slots_bytes || (n && (!data || !sizes || !images || !status))) return LLFE_ERR_INVALID;
+    return llfe_jpeg_images_layout_flags(data, sizes, n, images, slots_bytes, status, threads, nullptr, 0);
+}
+
+extern "C" int llfe_jpeg_images_layout_flags(const uint8_t *const *data, const uint64_t *sizes, int32_t n,
+                                             llfe_jpeg_image *images, int64_t *slots_bytes, int32_t *status,
+                                             int32_t threads, uint8_t *orientation, uint32_t flags) {
+    if ((flags & ~LLFE_JPEG_ORIENT) || n < 0 || !slots_bytes || (n && (!data || !sizes || !images || !status)) ||
+        ((flags & LLFE_JPEG_ORIENT) && n && !orientation))
+        return LLFE_ERR_INVALID;
+    const bool orient = (flags & LLFE_JPEG_ORIENT) != 0;
+    for (int i = 0; orientation && i < n; i++) orientation[i] = 1;
     const int nt = std::max(1, std::min<int>(threads > 0 ? threads : 1, n));
     std::atomic<int> next{0};
     auto work = [&]() {
@@ -607,9 +619,12 @@ extern "C" int llfe_jpeg_images_layout(const uint8_t *const *data, const uint64_
             if (!data[i]) {
                 rc = LLFE_ERR_INVALID;
             } else if (is_jpeg(data[i], (size_t)sizes[i])) {
-                rc = llfe_jpeg_layout_one(data[i], (size_t)sizes[i], &m.height, &m.width, &m.slot_bytes);
+                rc = orient ? llfe_jpeg_layout_one_oriented(data[i], (size_t)sizes[i], &m.height, &m.width, &m.slot_bytes,
+                                                            &orientation[i])
+                            : llfe_jpeg_layout_one(data[i], (size_t)sizes[i], &m.height, &m.width, &m.slot_bytes);
                 if ((uint64_t)(uint32_t)m.width * (uint32_t)m.height > max_pixels()) rc = LLFE_ERR_CAPACITY;
                 if (rc) m.slot_bytes = 0;
+                if (rc && orient) orientation[i] = 1;
             } else {  // another format: its size when its header gives one
                 rc = llfe_image_info(data[i], sizes[i], &m.width, &m.height);
                 if (rc == LLFE_OK) rc = LLFE_ERR_UNSUPPORTED;

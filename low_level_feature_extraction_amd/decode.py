@@ -491,12 +491,15 @@ class StagedImages:
     uint8, pinned when a GPU is present; its first ``used_bytes`` bytes hold the slots),
     ``layout_status`` / ``status`` per image (the header stage's, and the final one: the header
     stage's where that is not 0, else the extraction's) and the blobs (for the images handed back
-    to the host decoders)."""
+    to the host decoders).  ``orientation``: per image, the EXIF orientation the reconstruction
+    has to apply (2 .. 8 only for files staged with ``orient=True``, else 1); the records keep the
+    coded size."""
 
-    def __init__(self, blobs, images, descs, layout_status, status, slots, used_bytes, tensor=None):
+    def __init__(self, blobs, images, descs, layout_status, status, slots, used_bytes, tensor=None, orientation=None):
         self.blobs, self.images, self.descs = blobs, images, descs
         self.layout_status, self.status = layout_status, status
         self.slots, self.used_bytes, self.tensor = slots, used_bytes, tensor
+        self.orientation = [1] * len(blobs) if orientation is None else list(orientation)
 
 
 def _stage_cap() -> int:
@@ -514,9 +517,12 @@ def _stage_bucket(nbytes: int) -> int:
     return (nbytes + (1 << 24) - 1) >> 24 << 24
 
 
-def images_layout(blobs, workers=None):
+def images_layout(blobs, workers=None, orient=False):
     """llfe_jpeg_images_layout: -> (the llfe_jpeg_image array, status list, total slot bytes).
-    Host only, headers only; out_offset is left 0."""
+    Host only, headers only; out_offset is left 0.  ``orient=True``
+    (llfe_jpeg_images_layout_flags, LLFE_JPEG_ORIENT): JPEGs with an EXIF orientation 2 .. 8 are
+    eligible too, and a fourth element follows: the orientation of every image (1 where it has
+    none or is not taken); the records hold the coded size."""
     import ctypes as C
 
     from . import _lib
@@ -525,15 +531,22 @@ def images_layout(blobs, workers=None):
     images = (_lib.LlfeJpegImage * n)()
     total = C.c_int64(0)
     ptrs, sizes, status, keep = _blob_table(blobs)
-    _lib.lib().llfe_jpeg_images_layout(ptrs, sizes, n, images, C.byref(total), status,
-                                       int(workers or default_decode_threads()))
+    if not orient:
+        _lib.lib().llfe_jpeg_images_layout(ptrs, sizes, n, images, C.byref(total), status,
+                                           int(workers or default_decode_threads()))
+        del keep
+        return images, list(status), int(total.value)
+    orientation = (C.c_uint8 * n)()
+    _lib.lib().llfe_jpeg_images_layout_flags(ptrs, sizes, n, images, C.byref(total), status,
+                                             int(workers or default_decode_threads()), orientation, _lib.JPEG_ORIENT)
     del keep
-    return images, list(status), int(total.value)
+    return images, list(status), int(total.value), list(orientation)
 
 
-def _stage_images(blobs, images, layout_status, workers) -> StagedImages:
+def _stage_images(blobs, images, layout_status, workers, orientation=None) -> StagedImages:
     """llfe_jpeg_read_coefs_images of ``blobs`` into the next staging buffer of the ring, the
-    slots of ``images`` (laid one behind the other here) in it."""
+    slots of ``images`` (laid one behind the other here) in it.  ``orientation`` (the layout's,
+    under ``orient=True``): files with an EXIF orientation are taken (LLFE_JPEG_ORIENT)."""
     from . import _lib
 
     n, total = len(blobs), 0
@@ -545,23 +558,26 @@ def _stage_images(blobs, images, layout_status, workers) -> StagedImages:
     status = [-5] * n  # (LLFE_ERR_UNSUPPORTED: nothing staged)
     if total:
         ptrs, sizes, st, keep = _blob_table(blobs)
-        _lib.lib().llfe_jpeg_read_coefs_images(ptrs, sizes, n, images, slots.ctypes.data, total, descs, st,
-                                               int(workers or default_decode_threads()))
+        _lib.lib().llfe_jpeg_read_coefs_images_flags(ptrs, sizes, n, images, slots.ctypes.data, total, descs, st,
+                                                     int(workers or default_decode_threads()),
+                                                     0 if orientation is None else _lib.JPEG_ORIENT)
         del keep
         status = list(st)
     status = [a if a != 0 else b for a, b in zip(layout_status, status)]
-    return StagedImages(blobs, images, descs, list(layout_status), status, slots[0], total, tensor)
+    return StagedImages(blobs, images, descs, list(layout_status), status, slots[0], total, tensor, orientation)
 
 
-def stage_coefs_images(blobs, workers=None) -> StagedImages:
+def stage_coefs_images(blobs, workers=None, orient=False) -> StagedImages:
     """The host half of decode_images_device for one staging buffer: the headers of every blob
     (images_layout), then the entropy decode of every eligible JPEG, whatever its size and
     sampling class, into tight slots in the next staging buffer of a ring of three, keyed by a
     bucket of the total bytes.  Host only.  An image this path does not take has a non-zero
-    status and slot_bytes 0."""
+    status and slot_bytes 0.  ``orient=True``: files with an EXIF orientation 2 .. 8 are staged
+    too, byte for byte as the same file without EXIF, and ``orientation`` carries the value for
+    the reconstruction."""
     blobs = [bytes(b) for b in blobs]
-    images, layout_status, _ = images_layout(blobs, workers)
-    return _stage_images(blobs, images, layout_status, workers)
+    images, layout_status, _, *orientation = images_layout(blobs, workers, orient)
+    return _stage_images(blobs, images, layout_status, workers, orientation[0] if orient else None)
 
 
 def _decode_or_error(b):
@@ -574,21 +590,23 @@ def _decode_or_error(b):
 class _Chunk:
     """What one chunk of decode_images_device holds after its staging: ``status`` per image
     (non-zero: the host decoders take it) and ``parts``, each (places in the chunk, llfe_jpeg_image
-    records, llfe_jpeg_desc records, coefficients): a StagedImages whose used prefix has yet to
-    cross, or a device tensor of slots."""
+    records, llfe_jpeg_desc records, coefficients, orientations): a StagedImages whose used prefix
+    has yet to cross, or a device tensor of slots; the orientations are None (all 1) or one per
+    record."""
 
     def __init__(self, status, parts):
         self.status, self.parts = status, parts
 
 
 def _host_chunk(st: StagedImages) -> _Chunk:
-    return _Chunk(st.status, [(list(range(len(st.blobs))), st.images, st.descs, st)])
+    return _Chunk(st.status, [(list(range(len(st.blobs))), st.images, st.descs, st, st.orientation)])
 
 
-def _run_images(blobs, images, layout_status, chunks, first, device, workers, stage) -> list:
+def _run_images(blobs, images, layout_status, chunks, first, device, workers, stage, orientation=None) -> list:
     """decode_images_device after the header stage: ``chunks`` (lists of image indices, in order,
     together all of them) are staged (``stage(idx)`` -> _Chunk) and reconstructed one after the
-    other into one packed tensor; ``first`` is chunk 0 already staged."""
+    other into one packed tensor; ``first`` is chunk 0 already staged.  ``orientation``: the
+    layout's per image (None: all 1); the place of an image with 5 .. 8 is width x height."""
     import torch
 
     from .backend import Backend
@@ -607,6 +625,8 @@ def _run_images(blobs, images, layout_status, chunks, first, device, workers, st
     for i in range(n):
         r = host.get(i)
         hw = (0, 0) if isinstance(r, Exception) else r.shape[:2] if r is not None else (images[i].height, images[i].width)
+        if r is None and orientation is not None and orientation[i] >= 5:
+            hw = hw[::-1]
         shape.append(hw)
         offset.append(total)
         total = (total + hw[0] * hw[1] * 3 + 15) & ~15
@@ -618,7 +638,7 @@ def _run_images(blobs, images, layout_status, chunks, first, device, workers, st
     out = [host[i] if isinstance(host.get(i), Exception) else place(i) for i in range(n)]
     for k, idx in enumerate(chunks):
         ch = first if k == 0 else stage(idx)
-        for sub, recs, descs, coefs in ch.parts:
+        for sub, recs, descs, coefs, orient in ch.parts:
             for m, j in zip(recs, sub):
                 m.out_offset = offset[idx[j]]
             if not any(d.n_comp for d in descs):
@@ -629,7 +649,9 @@ def _run_images(blobs, images, layout_status, chunks, first, device, workers, st
                     src = st.tensor[0] if st.tensor is not None else torch.from_numpy(st.slots)
                     coefs = torch.empty(st.used_bytes, dtype=torch.uint8, device=dev)
                     coefs.copy_(src[:st.used_bytes], non_blocking=True)
-                Backend.get(dev.index).jpeg_reconstruct_images(coefs, recs, descs, packed)
+                if orient is not None and all(o == 1 for o in orient):
+                    orient = None
+                Backend.get(dev.index).jpeg_reconstruct_images(coefs, recs, descs, packed, orient)
         # a later chunk's extraction handed an image back: its place is laid out by its header
         late = [i for j, i in enumerate(idx) if ch.status[j] != 0 and i not in known]
         for i, r in zip(late, pool.map(_decode_or_error, [blobs[i] for i in late])):
@@ -661,10 +683,10 @@ def reconstruct_staged_images(st: StagedImages, device=0, workers=None) -> list:
     if not st.blobs:
         return []
     return _run_images(st.blobs, st.images, st.layout_status, [list(range(len(st.blobs)))], _host_chunk(st), device,
-                       workers, None)
+                       workers, None, st.orientation)
 
 
-def decode_images_device(blobs, device=0, workers=None, entropy="host", restarts=False) -> list:
+def decode_images_device(blobs, device=0, workers=None, entropy="host", restarts=False, orient="host") -> list:
     """decode_many with the JPEG reconstruction on the GPU, for images of any sizes: -> a list in
     input order of H x W x 3 BGR uint8 device tensors, the same bytes decode_bgr returns, each a
     view into one packed tensor and starting at a multiple of 16; a DecodeError instance stands
@@ -684,13 +706,22 @@ def decode_images_device(blobs, device=0, workers=None, entropy="host", restarts
     headers, the file bytes cross PCIe in one copy and the kernels fill a device tensor of the
     chunk's tight slots, so LLFE_JPEG_STAGE_BYTES then bounds coefficient bytes that live in
     device memory only.  What the device hands back takes the host coefficient path above, what
-    that hands back decode_bgr; the result is the same bytes in every case."""
+    that hands back decode_bgr; the result is the same bytes in every case.
+
+    ``orient="device"`` keeps JPEGs with an EXIF orientation 2 .. 8 (a phone's portrait shot is a
+    6 or an 8) on these routes instead of handing them to decode_bgr: they are staged as the same
+    file without EXIF and the reconstruction stores every pixel where ImageOps.exif_transpose
+    puts it, so the place of a 5 .. 8 image is width x height x 3.  The bytes are decode_bgr's.
+    ``orient="host"`` is the route above."""
     if entropy not in ("host", "device"):
         raise ValueError('entropy must be "host" or "device"')
+    if orient not in ("host", "device"):
+        raise ValueError('orient must be "host" or "device"')
     blobs = [bytes(b) for b in blobs]
     if not blobs:
         return []
-    images, layout_status, _ = images_layout(blobs, workers)
+    images, layout_status, _, *orientation = images_layout(blobs, workers, orient == "device")
+    orientation = orientation[0] if orient == "device" else None
     cap, chunks, room = _stage_cap(), [[]], 0
     for i, m in enumerate(images):
         if m.slot_bytes > cap:
@@ -703,11 +734,12 @@ def decode_images_device(blobs, device=0, workers=None, entropy="host", restarts
 
     def stage(idx):
         sub, status = [blobs[i] for i in idx], [layout_status[i] for i in idx]
+        ori = None if orientation is None else [orientation[i] for i in idx]
         if entropy == "host":
-            return _host_chunk(_stage_images(sub, _sub_images(images, idx), status, workers))
-        return _device_chunk(sub, _sub_images(images, idx), status, device, workers, restarts)
+            return _host_chunk(_stage_images(sub, _sub_images(images, idx), status, workers, ori))
+        return _device_chunk(sub, _sub_images(images, idx), status, device, workers, restarts, ori)
 
-    return _run_images(blobs, images, layout_status, chunks, stage(chunks[0]), device, workers, stage)
+    return _run_images(blobs, images, layout_status, chunks, stage(chunks[0]), device, workers, stage, orientation)
 
 
 # ------------------------------------------------------------ JPEG entropy decode on the device
@@ -845,18 +877,21 @@ class StagedByteImages:
     records: size and tight slot of every image), ``descs`` / ``scans`` (the llfe_jpeg_desc /
     llfe_jpeg_scan arrays), ``records`` (1-d uint8, pinned when a GPU is present; its first
     ``used_bytes`` bytes hold the records), ``slot_bytes`` (the bytes of all slots),
-    ``layout_status`` / ``status`` per image (the header stage's, and the final one) and the
-    blobs."""
+    ``layout_status`` / ``status`` per image (the header stage's, and the final one), the
+    blobs and ``orientation`` (as StagedImages')."""
 
-    def __init__(self, blobs, images, descs, scans, layout_status, status, records, used_bytes, slot_bytes, tensor=None):
+    def __init__(self, blobs, images, descs, scans, layout_status, status, records, used_bytes, slot_bytes, tensor=None,
+                 orientation=None):
         self.blobs, self.images, self.descs, self.scans = blobs, images, descs, scans
         self.layout_status, self.status = layout_status, status
         self.records, self.used_bytes, self.slot_bytes, self.tensor = records, used_bytes, slot_bytes, tensor
+        self.orientation = [1] * len(blobs) if orientation is None else list(orientation)
 
 
-def _stage_bytes_images(blobs, images, layout_status, workers, restarts) -> StagedByteImages:
+def _stage_bytes_images(blobs, images, layout_status, workers, restarts, orientation=None) -> StagedByteImages:
     """llfe_jpeg_parse_images of ``blobs`` into the next staging buffer of the ring, the slots of
-    ``images`` and the records (llfe_jpeg_records_layout) laid one behind the other here."""
+    ``images`` and the records (llfe_jpeg_records_layout) laid one behind the other here.
+    ``orientation`` as in _stage_images."""
     import ctypes as C
 
     from . import _lib
@@ -874,25 +909,26 @@ def _stage_bytes_images(blobs, images, layout_status, workers, restarts) -> Stag
     if used.value:
         _lib.lib().llfe_jpeg_parse_images(ptrs, sizes, n, images, offsets, records.ctypes.data, used.value, descs, scans,
                                           st, int(workers or default_decode_threads()),
-                                          _lib.JPEG_PARSE_RESTARTS if restarts else 0)
+                                          (_lib.JPEG_PARSE_RESTARTS if restarts else 0) |
+                                          (0 if orientation is None else _lib.JPEG_ORIENT))
         status = list(st)
     del keep
     status = [a if a != 0 else b for a, b in zip(layout_status, status)]
     return StagedByteImages(blobs, images, descs, scans, list(layout_status), status, records[0], int(used.value), total,
-                            tensor)
+                            tensor, orientation)
 
 
-def stage_bytes_images(blobs, workers=None, restarts=False) -> StagedByteImages:
+def stage_bytes_images(blobs, workers=None, restarts=False, orient=False) -> StagedByteImages:
     """The host half of decode_images_device(entropy="device") for one staging buffer: the headers
     of every blob (images_layout), then llfe_jpeg_parse_images: quantisation tables, decode tables
     and the scan's bytes of every eligible JPEG (what stage_bytes takes), whatever its size and
     sampling class, one record behind the other in the next staging buffer of a ring of three,
     keyed by a bucket of the total bytes.  Host only; no entropy decoding happens here.  An image
     this path does not take has a non-zero status, n_comp 0 and blocks_in_mcu 0.  ``restarts`` as
-    in stage_bytes."""
+    in stage_bytes, ``orient`` as in stage_coefs_images."""
     blobs = [bytes(b) for b in blobs]
-    images, layout_status, _ = images_layout(blobs, workers)
-    return _stage_bytes_images(blobs, images, layout_status, workers, restarts)
+    images, layout_status, _, *orientation = images_layout(blobs, workers, orient)
+    return _stage_bytes_images(blobs, images, layout_status, workers, restarts, orientation[0] if orient else None)
 
 
 def entropy_reference_images(st: StagedByteImages, one_piece=False):
@@ -940,20 +976,21 @@ def entropy_decode_staged_images(st: StagedByteImages, device=0, slots=None):
     return slots, descs, status
 
 
-def _device_chunk(blobs, images, layout_status, device, workers, restarts) -> _Chunk:
+def _device_chunk(blobs, images, layout_status, device, workers, restarts, orientation=None) -> _Chunk:
     """One chunk of decode_images_device(entropy="device"): parse, copy, entropy kernels; the
     images the device hands back go through the host coefficient path (_stage_images)."""
     n = len(blobs)
-    sb = _stage_bytes_images(blobs, images, layout_status, workers, restarts)
+    sb = _stage_bytes_images(blobs, images, layout_status, workers, restarts, orientation)
     status, parts = [-5] * n, []
     if any(rc == 0 for rc in sb.status):
         d_slots, descs, status = entropy_decode_staged_images(sb, device)
-        parts.append((list(range(n)), sb.images, descs, d_slots))
+        parts.append((list(range(n)), sb.images, descs, d_slots, orientation))
     todo = [j for j, rc in enumerate(status) if rc != 0]
     status = list(status)
     if todo:
-        st = _stage_images([blobs[j] for j in todo], _sub_images(images, todo), [layout_status[j] for j in todo], workers)
-        parts.append((todo, st.images, st.descs, st))
+        st = _stage_images([blobs[j] for j in todo], _sub_images(images, todo), [layout_status[j] for j in todo], workers,
+                           None if orientation is None else [orientation[j] for j in todo])
+        parts.append((todo, st.images, st.descs, st, st.orientation))
         for j, rc in zip(todo, st.status):
             status[j] = rc
     return _Chunk(status, parts)

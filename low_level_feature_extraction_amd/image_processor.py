@@ -42,7 +42,8 @@ class ImageProcessor:
 
     @staticmethod
     def auto_process_images(images_bytes, max_width: int = 1920, max_height: int = 1080, device: bool = False,
-                            decode: str = "host", entropy: str = "host", restarts: bool = False) -> list:
+                            decode: str = "host", entropy: str = "host", restarts: bool = False,
+                            orient: str = "host") -> list:
         """Batched auto_process_image: host decode on the decode pool, then one GPU
         thumbnail launch sequence per group of equally sized images
         (llfe_thumbnail_pil_batch).  Returns arrays in input order; an input that fails
@@ -62,7 +63,11 @@ class ImageProcessor:
         baseline JPEGs among them to the GPU as well (decode_images_device(entropy="device"):
         the file bytes cross PCIe, not the coefficients), ``restarts=True`` (with
         ``entropy="device"`` only) lets it take files with restart intervals; the bytes are the
-        same in every case."""
+        same in every case.
+
+        ``orient="device"`` (with ``decode="device"`` only) keeps JPEGs with an EXIF orientation
+        on the device routes as well (decode_images_device(orient="device")): the reconstruction
+        stores a portrait shot rotated, instead of the host decoding and transposing it."""
         from .backend import Backend, thumbnail_size
         from .decode import decode_images_device, decode_many
 
@@ -76,8 +81,13 @@ class ImageProcessor:
             raise ValueError('entropy="device" needs decode="device"')
         if restarts and entropy != "device":
             raise ValueError('restarts=True needs entropy="device"')
+        if orient not in ("host", "device"):
+            raise ValueError('orient must be "host" or "device"')
+        if orient == "device" and decode != "device":
+            raise ValueError('orient="device" needs decode="device"')
         if decode == "device":
-            decoded = decode_images_device(list(images_bytes), Backend.get().device, entropy=entropy, restarts=restarts)
+            decoded = decode_images_device(list(images_bytes), Backend.get().device, entropy=entropy, restarts=restarts,
+                                           orient=orient)
         else:
             decoded = decode_many(list(images_bytes))
         out: list = [None] * len(decoded)

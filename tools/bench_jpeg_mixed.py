@@ -16,6 +16,13 @@ A seeded feed of --images quality-85 4:2:0 JPEGs, one process, one rank, a warm-
 --reps passes over the feed:
   --feed mixed    the 16 sizes of tools/bench_thumb.py --feed mixed (2000 x 1500 .. 4032 x 3024)
   --feed uniform  every image 1920 x 1080, where B is at its best
+  --feed phone    the mixed feed, pixel for pixel, with the EXIF orientation of half the files set
+                  to 6, of a quarter to 8 and of one to 3: a phone's portrait shots (DESIGN.md §3
+                  "EXIF orientation in the mixed-size decode"; figures in profiles/jpeg_orient/).
+                  Its legs are C and D as above (orient="host": those files take decode_bgr, the
+                  behaviour before the option) against Co and Do, the same two with
+                  orient="device"; A and B are not run.  The profiled passes give k_jpeg_images per
+                  orientation group (k_jpeg_images, _mirrored, _transposed).
 After the timed legs one profiled pass of B, of C and of D gives the kernel ms (llfe_kernel_stats):
 k_jpeg_idct + k_jpeg_color against k_jpeg_images on the same coefficients, and D's k_huff_*
 kernels (k_huff_sync: one launch per pass and kind).  One JSON line on stdout.
@@ -38,15 +45,22 @@ for p in (ROOT, os.path.join(ROOT, "tools")):
 import numpy as np  # noqa: E402
 
 
+def phone_orientation(i: int):
+    """The EXIF orientation of file i of the phone feed (None: no EXIF): 6 for every second file,
+    8 for every fourth, 3 for one."""
+    return 6 if i % 2 == 0 else 8 if i % 4 == 1 else 3 if i == 3 else None
+
+
 def make_feed(kind: str, n: int, seed: int):
     """-> (list of (h, w), list of JPEG blobs): smooth colour fields with some texture, so the
-    files are of a photo's length rather than noise's."""
+    files are of a photo's length rather than noise's.  (h, w) is the coded size."""
     from bench_thumb import feed_sizes
     from PIL import Image
 
     from concurrent.futures import ThreadPoolExecutor
 
     sizes = [(1080, 1920)] * n if kind == "uniform" else feed_sizes("mixed", n, seed)
+    orient = phone_orientation if kind == "phone" else lambda i: None
 
     def one(i):
         h, w = sizes[i]
@@ -56,16 +70,87 @@ def make_feed(kind: str, n: int, seed: int):
         img = np.stack([127 + 100 * np.sin(f[c, 0] * x + f[c, 1] * y + i + c) for c in range(3)], axis=-1)
         img += rng.normal(0, 6, (h, w, 1)).astype(np.float32)
         b = io.BytesIO()
-        Image.fromarray(np.clip(img, 0, 255).astype(np.uint8)).save(b, "JPEG", quality=85, subsampling=2)
+        kw = {}
+        if orient(i) is not None:
+            ex = Image.Exif()
+            ex[0x0112] = orient(i)
+            kw["exif"] = ex.tobytes()
+        Image.fromarray(np.clip(img, 0, 255).astype(np.uint8)).save(b, "JPEG", quality=85, subsampling=2, **kw)
         return b.getvalue()
 
     with ThreadPoolExecutor(8) as pool:
         return sizes, list(pool.map(one, range(n)))
 
 
+def run_legs(args, routes, n):
+    """Every route alternating, --legs legs each -> {route: [images/s per leg]}."""
+    import torch
+
+    def leg(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.reps):
+            fn()
+        torch.cuda.synchronize()
+        return args.reps * n / (time.perf_counter() - t0)
+
+    legs = {k: [] for k in routes}
+    for _ in range(args.legs):
+        for k, fn in routes.items():
+            legs[k].append(round(leg(fn), 1))
+    return legs
+
+
+def profiled(be, fn):
+    be.set_profiling(True)
+    try:
+        fn()
+        st = be.kernel_stats()
+    finally:
+        be.set_profiling(False)
+    return {k: {"launches": v["launches"], "ms": round(v["total_ms"], 3)} for k, v in st.items()
+            if k.startswith(("k_jpeg", "k_huff"))}
+
+
+def phone(args, be, sizes, blobs, route_c, route_d):
+    """The phone feed: orient="host" (C, D) against orient="device" (Co, Do)."""
+    import torch
+
+    from low_level_feature_extraction_amd import decode
+
+    routes = {"C": route_c, "Co": lambda: decode.decode_images_device(blobs, orient="device"),
+              "D": route_d, "Do": lambda: decode.decode_images_device(blobs, entropy="device", orient="device")}
+    for _ in range(3):  # (the warm-up of main)
+        res = [fn() for fn in routes.values()]
+    same = all(all(torch.equal(r[0], x) for x in r[1:]) for r in zip(*res))
+    del res
+    legs = run_legs(args, routes, len(blobs))
+    kernels = {k: profiled(be, fn) for k, fn in routes.items()}
+    summary = {k: {"median": statistics.median(v), "min": min(v), "max": max(v)} for k, v in legs.items()}
+    spread = max(summary[k]["max"] - summary[k]["min"] for k in ("C", "D"))
+    mp = {}
+    for i, (h, w) in enumerate(sizes):
+        o = phone_orientation(i) or 1
+        mp[o] = mp.get(o, 0) + h * w / 1e6
+    out = {
+        "tool": "bench_jpeg_mixed", "feed": args.feed, "images": len(blobs), "distinct_sizes": len(set(sizes)),
+        "megapixels": round(sum(h * w for h, w in sizes) / 1e6, 1), "file_mib": round(sum(map(len, blobs)) / 2**20, 1),
+        "megapixels_by_orientation": {str(o): round(v, 1) for o, v in sorted(mp.items())},
+        "reps_per_leg": args.reps, "same_bytes": same, "decode_threads": decode.default_decode_threads(),
+        "images_per_s": legs, "summary": summary,
+        # a speed claim needs the medians further apart than three times the host legs' spread
+        "Co_minus_C_median": round(summary["Co"]["median"] - summary["C"]["median"], 1),
+        "Do_minus_D_median": round(summary["Do"]["median"] - summary["D"]["median"], 1),
+        "three_times_host_spread": round(3 * spread, 1),
+        "kernels_ms_per_pass": kernels,
+        "device": torch.cuda.get_device_name(0),
+    }
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--feed", choices=("mixed", "uniform"), default="mixed")
+    ap.add_argument("--feed", choices=("mixed", "uniform", "phone"), default="mixed")
     ap.add_argument("--images", type=int, default=64)
     ap.add_argument("--legs", type=int, default=3)
     ap.add_argument("--reps", type=int, default=8)
@@ -105,6 +190,8 @@ def main():
         return decode.decode_images_device(blobs, entropy="device")
 
     routes = {"A": route_a, "B": route_b, "C": route_c, "D": route_d}
+    if args.feed == "phone":
+        return phone(args, be, sizes, blobs, route_c, route_d)
     # warm-up: three passes each, so that every buffer of the pinned staging rings of three exists
     # (allocations, code objects), and the four routes give the same bytes
     for _ in range(3):
@@ -112,30 +199,8 @@ def main():
     same = all(torch.equal(a, b) and torch.equal(a, c) and torch.equal(a, d) for a, b, c, d in zip(ra, rb, rc, rd))
     del ra, rb, rc, rd
 
-    def leg(fn):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(args.reps):
-            fn()
-        torch.cuda.synchronize()
-        return args.reps * len(blobs) / (time.perf_counter() - t0)
-
-    legs = {k: [] for k in routes}
-    for _ in range(args.legs):
-        for k, fn in routes.items():
-            legs[k].append(round(leg(fn), 1))
-
-    def profiled(fn):
-        be.set_profiling(True)
-        try:
-            fn()
-            st = be.kernel_stats()
-        finally:
-            be.set_profiling(False)
-        return {k: {"launches": v["launches"], "ms": round(v["total_ms"], 3)} for k, v in st.items()
-                if k.startswith(("k_jpeg", "k_huff"))}
-
-    kb, kc, kd = profiled(route_b), profiled(route_c), profiled(route_d)
+    legs = run_legs(args, routes, len(blobs))
+    kb, kc, kd = profiled(be, route_b), profiled(be, route_c), profiled(be, route_d)
     summary = {k: {"median": statistics.median(v), "min": min(v), "max": max(v)} for k, v in legs.items()}
     spread = max(summary[k]["max"] - summary[k]["min"] for k in ("A", "B"))
     out = {

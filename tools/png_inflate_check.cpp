@@ -22,6 +22,9 @@ int llfe_jpeg_info_one(const uint8_t *, size_t, int32_t *, int32_t *, int *) { r
 bool llfe_jpeg_available() { return false; }
 int llfe_jpeg_decode_one(const uint8_t *, size_t, int32_t, int32_t, uint8_t *) { return LLFE_ERR_UNSUPPORTED; }
 int llfe_jpeg_layout_one(const uint8_t *, size_t, int32_t *, int32_t *, int64_t *) { return LLFE_ERR_UNSUPPORTED; }
+int llfe_jpeg_layout_one_oriented(const uint8_t *, size_t, int32_t *, int32_t *, int64_t *, uint8_t *) {
+    return LLFE_ERR_UNSUPPORTED;
+}
 
 int main(int argc, char **argv) {
     for (int a = 1; a < argc; a++) {
