@@ -548,7 +548,10 @@ int llfe_jpeg_read_coefs_batch(const uint8_t *const *data, const uint64_t *sizes
  * host before anything is launched: every offset and extent inside the slot, the block
  * grids covering h x w at the sampling class; a bad descriptor is LLFE_ERR_INVALID with
  * out_bgr untouched.  Images with n_comp == 0 are left as they are in out_bgr (the caller
- * fills them from llfe_decode_batch).  Runs on `stream` and returns when it has finished. */
+ * fills them from llfe_decode_batch).  The same kernel as llfe_jpeg_reconstruct_images below,
+ * one launch over the (image, tile) pairs of the call: no workspace and no chunks; more than
+ * 2^31 tiles in one call are LLFE_ERR_CAPACITY.  Runs on `stream` and returns when it has
+ * finished. */
 int llfe_jpeg_reconstruct(llfe_ctx *ctx, const uint8_t *coefs, int64_t slot_stride, const llfe_jpeg_desc *descs,
                           int32_t n, int32_t h, int32_t w, uint8_t *out_bgr, llfe_stream stream);
 

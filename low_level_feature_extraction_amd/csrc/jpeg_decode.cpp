@@ -19,7 +19,7 @@
 //
 // The second entry point, llfe_jpeg_read_coefs_batch, stops the same decode after its entropy
 // half (jpeg_read_coefficients) and copies the quantised coefficients and quantisation tables
-// out for the device reconstruction (jpeg_recon.hip); it takes fewer files than the decoder
+// out for the device reconstruction (jpeg_images.hip); it takes fewer files than the decoder
 // above (no libjpeg warning, complete progressive scans, 4:4:4 / 4:2:2 / 4:2:0 / grey only)
 // and hands the rest back with LLFE_ERR_UNSUPPORTED.  llfe_jpeg_read_coefs_images is the same
 // extraction for images that each have their own size and tight slot (jpeg_images.hip), laid
@@ -28,13 +28,12 @@
 #include <setjmp.h>
 
 #include <algorithm>
-#include <atomic>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
-#include <thread>
 #include <vector>
 
+#include "host_fanout.h"
 #include "jpeg_desc_check.h"
 #include "jpeg_huff_core.h"
 #include "jpeg_orient.h"
@@ -335,7 +334,7 @@ int decode(const uint8_t *data, size_t size, int32_t h, int32_t w, uint8_t *out,
     return rc;
 }
 
-// ---- coefficients for the device reconstruction (jpeg_recon.hip)
+// ---- coefficients for the device reconstruction (jpeg_images.hip)
 constexpr int64_t kQuantBytes = 3 * 128;  // three 64 x u16 tables lead the slot
 
 inline int64_t div_up(int64_t a, int64_t b) { return (a + b - 1) / b; }
@@ -806,29 +805,12 @@ extern "C" int llfe_jpeg_read_coefs_batch(const uint8_t *const *data, const uint
     if (n < 0 || (n && (!data || !sizes || !slots || !descs || !status)) || height <= 0 || width <= 0 ||
         height > 65535 || width > 65535 || slot_stride < 0)
         return LLFE_ERR_INVALID;
-    const int nt = std::max(1, std::min<int>(threads > 0 ? threads : 1, n));
-    std::atomic<int> next{0};
-    auto work = [&]() {
-        for (int i; (i = next.fetch_add(1)) < n;) {
-            int rc;
-            memset(&descs[i], 0, sizeof descs[i]);  // n_comp 0: nothing staged for this image
-            try {
-                rc = data[i] ? llfe_jpeg::read_coefs(data[i], (size_t)sizes[i], height, width,
-                                                     slots + (size_t)i * (size_t)slot_stride, slot_stride, &descs[i])
-                             : LLFE_ERR_INVALID;
-            } catch (const std::bad_alloc &) {
-                rc = LLFE_ERR_OOM;
-            }
-            status[i] = rc;
-        }
-    };
-    std::vector<std::thread> th;
-    for (int t = 1; t < nt; t++) th.emplace_back(work);
-    work();
-    for (auto &t : th) t.join();
-    for (int i = 0; i < n; i++)
-        if (status[i]) return status[i];
-    return LLFE_OK;
+    return llfe::fan_out(n, threads, status, [&](int i) {
+        memset(&descs[i], 0, sizeof descs[i]);  // n_comp 0: nothing staged for this image
+        return data[i] ? llfe_jpeg::read_coefs(data[i], (size_t)sizes[i], height, width,
+                                               slots + (size_t)i * (size_t)slot_stride, slot_stride, &descs[i])
+                       : LLFE_ERR_INVALID;
+    });
 }
 
 // used by png_decode.cpp's llfe_jpeg_images_layout (which owns the format dispatch and the pixel limit)
@@ -874,33 +856,16 @@ extern "C" int llfe_jpeg_read_coefs_images_flags(const uint8_t *const *data, con
             m.slot_offset > slots_bytes || m.slot_bytes > slots_bytes - m.slot_offset)
             return LLFE_ERR_INVALID;
     }
-    const int nt = std::max(1, std::min<int>(threads > 0 ? threads : 1, n));
-    std::atomic<int> next{0};
-    auto work = [&]() {
-        for (int i; (i = next.fetch_add(1)) < n;) {
-            const llfe_jpeg_image &m = images[i];
-            int rc;
-            memset(&descs[i], 0, sizeof descs[i]);  // n_comp 0: nothing staged for this image
-            try {
-                rc = m.slot_bytes == 0 ? LLFE_ERR_UNSUPPORTED
-                     : !data[i]        ? LLFE_ERR_INVALID
-                     : m.height <= 0 || m.width <= 0 || m.height > 65535 || m.width > 65535
-                         ? LLFE_ERR_CAPACITY  // (no JPEG has that size)
-                         : llfe_jpeg::read_coefs(data[i], (size_t)sizes[i], m.height, m.width, slots + m.slot_offset,
-                                                 m.slot_bytes, &descs[i], (flags & LLFE_JPEG_ORIENT) != 0);
-            } catch (const std::bad_alloc &) {
-                rc = LLFE_ERR_OOM;
-            }
-            status[i] = rc;
-        }
-    };
-    std::vector<std::thread> th;
-    for (int t = 1; t < nt; t++) th.emplace_back(work);
-    work();
-    for (auto &t : th) t.join();
-    for (int i = 0; i < n; i++)
-        if (status[i]) return status[i];
-    return LLFE_OK;
+    return llfe::fan_out(n, threads, status, [&](int i) {
+        const llfe_jpeg_image &m = images[i];
+        memset(&descs[i], 0, sizeof descs[i]);  // n_comp 0: nothing staged for this image
+        return m.slot_bytes == 0 ? LLFE_ERR_UNSUPPORTED
+               : !data[i]        ? LLFE_ERR_INVALID
+               : m.height <= 0 || m.width <= 0 || m.height > 65535 || m.width > 65535
+                   ? LLFE_ERR_CAPACITY  // (no JPEG has that size)
+                   : llfe_jpeg::read_coefs(data[i], (size_t)sizes[i], m.height, m.width, slots + m.slot_offset,
+                                           m.slot_bytes, &descs[i], (flags & LLFE_JPEG_ORIENT) != 0);
+    });
 }
 
 extern "C" int llfe_jpeg_parse_batch_flags(const uint8_t *const *data, const uint64_t *sizes, int32_t n, int32_t height,
@@ -911,32 +876,15 @@ extern "C" int llfe_jpeg_parse_batch_flags(const uint8_t *const *data, const uin
         height > 65535 || width > 65535 || slot_stride < 0 || record_stride < LLFE_JPEG_RECORD_HEADER ||
         (record_stride & 15))
         return LLFE_ERR_INVALID;
-    const int nt = std::max(1, std::min<int>(threads > 0 ? threads : 1, n));
-    std::atomic<int> next{0};
-    auto work = [&]() {
-        for (int i; (i = next.fetch_add(1)) < n;) {
-            int rc;
-            memset(&descs[i], 0, sizeof descs[i]);  // n_comp 0, blocks_in_mcu 0: nothing staged for this image
-            memset(&scans[i], 0, sizeof scans[i]);
-            try {
-                const int64_t off = (int64_t)i * record_stride;
-                rc = data[i] ? llfe_jpeg::parse_one(data[i], (size_t)sizes[i], height, width, staging + off, off,
-                                                    record_stride, slot_stride, &descs[i], &scans[i],
-                                                    (flags & LLFE_JPEG_PARSE_RESTARTS) != 0)
-                             : LLFE_ERR_INVALID;
-            } catch (const std::bad_alloc &) {
-                rc = LLFE_ERR_OOM;
-            }
-            status[i] = rc;
-        }
-    };
-    std::vector<std::thread> th;
-    for (int t = 1; t < nt; t++) th.emplace_back(work);
-    work();
-    for (auto &t : th) t.join();
-    for (int i = 0; i < n; i++)
-        if (status[i]) return status[i];
-    return LLFE_OK;
+    return llfe::fan_out(n, threads, status, [&](int i) {
+        memset(&descs[i], 0, sizeof descs[i]);  // n_comp 0, blocks_in_mcu 0: nothing staged for this image
+        memset(&scans[i], 0, sizeof scans[i]);
+        const int64_t off = (int64_t)i * record_stride;
+        return data[i] ? llfe_jpeg::parse_one(data[i], (size_t)sizes[i], height, width, staging + off, off,
+                                              record_stride, slot_stride, &descs[i], &scans[i],
+                                              (flags & LLFE_JPEG_PARSE_RESTARTS) != 0)
+                       : LLFE_ERR_INVALID;
+    });
 }
 
 extern "C" int llfe_jpeg_parse_batch(const uint8_t *const *data, const uint64_t *sizes, int32_t n, int32_t height,
@@ -970,9 +918,8 @@ extern "C" int llfe_jpeg_entropy_reference(const uint8_t *staging, int64_t stagi
     if (n < 0 || (n && (!staging || !scans || !descs || !slots || !status)) || h <= 0 || w <= 0 || h > 65535 ||
         w > 65535 || slot_stride <= 0 || staging_bytes < 0 || ((uintptr_t)staging & 15))
         return LLFE_ERR_INVALID;
-    int64_t plane_stride = 0;
-    int mb = 0, max_sub = 0, max_blocks = 0;
-    if (!llfe::check_jpeg_descs(descs, n, h, w, slot_stride, &plane_stride, &mb) ||
+    int max_sub = 0, max_blocks = 0;
+    if (!llfe::check_jpeg_descs(descs, n, h, w, slot_stride) ||
         !llfe_huff::validate_scans(scans, descs, n, staging_bytes, &max_sub, &max_blocks))
         return LLFE_ERR_INVALID;
     return llfe_jpeg::reference_all(staging, scans, descs, n, status, one_piece != 0,
@@ -1022,34 +969,17 @@ extern "C" int llfe_jpeg_parse_images(const uint8_t *const *data, const uint64_t
             llfe_jpeg::record_bytes(sizes[i]) > staging_bytes - off)
             return LLFE_ERR_INVALID;
     }
-    const int nt = std::max(1, std::min<int>(threads > 0 ? threads : 1, n));
-    std::atomic<int> next{0};
-    auto work = [&]() {
-        for (int i; (i = next.fetch_add(1)) < n;) {
-            const llfe_jpeg_image &m = images[i];
-            int rc;
-            memset(&descs[i], 0, sizeof descs[i]);  // n_comp 0, blocks_in_mcu 0: nothing staged for this image
-            memset(&scans[i], 0, sizeof scans[i]);
-            try {
-                rc = m.slot_bytes == 0 ? LLFE_ERR_UNSUPPORTED
-                     : !data[i]        ? LLFE_ERR_INVALID
-                     : m.height <= 0 || m.width <= 0 || m.height > 65535 || m.width > 65535
-                         ? LLFE_ERR_CAPACITY  // (no JPEG has that size)
-                         : llfe_jpeg::parse_one(data[i], (size_t)sizes[i], m.height, m.width, staging + record_offsets[i],
-                                                record_offsets[i], llfe_jpeg::record_bytes(sizes[i]), m.slot_bytes,
-                                                &descs[i], &scans[i], (flags & LLFE_JPEG_PARSE_RESTARTS) != 0,
-                                                (flags & LLFE_JPEG_ORIENT) != 0);
-            } catch (const std::bad_alloc &) {
-                rc = LLFE_ERR_OOM;
-            }
-            status[i] = rc;
-        }
-    };
-    std::vector<std::thread> th;
-    for (int t = 1; t < nt; t++) th.emplace_back(work);
-    work();
-    for (auto &t : th) t.join();
-    for (int i = 0; i < n; i++)
-        if (status[i]) return status[i];
-    return LLFE_OK;
+    return llfe::fan_out(n, threads, status, [&](int i) {
+        const llfe_jpeg_image &m = images[i];
+        memset(&descs[i], 0, sizeof descs[i]);  // n_comp 0, blocks_in_mcu 0: nothing staged for this image
+        memset(&scans[i], 0, sizeof scans[i]);
+        return m.slot_bytes == 0 ? LLFE_ERR_UNSUPPORTED
+               : !data[i]        ? LLFE_ERR_INVALID
+               : m.height <= 0 || m.width <= 0 || m.height > 65535 || m.width > 65535
+                   ? LLFE_ERR_CAPACITY  // (no JPEG has that size)
+                   : llfe_jpeg::parse_one(data[i], (size_t)sizes[i], m.height, m.width, staging + record_offsets[i],
+                                          record_offsets[i], llfe_jpeg::record_bytes(sizes[i]), m.slot_bytes, &descs[i],
+                                          &scans[i], (flags & LLFE_JPEG_PARSE_RESTARTS) != 0,
+                                          (flags & LLFE_JPEG_ORIENT) != 0);
+    });
 }

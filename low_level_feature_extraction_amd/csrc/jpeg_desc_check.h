@@ -1,7 +1,7 @@
 // The host check of llfe_jpeg_desc records, in front of every kernel that indexes a coefficient
-// slot through them: llfe_jpeg_reconstruct (jpeg_recon.hip), llfe_jpeg_reconstruct_images
-// (jpeg_images.hip), llfe_jpeg_entropy_decode (jpeg_huff.hip) and the latter's host twin (jpeg_decode.cpp, which is also built on its own
-// without the device code).  Plain C++, no HIP types.
+// slot through them: llfe_jpeg_reconstruct and llfe_jpeg_reconstruct_images (jpeg_images.hip),
+// llfe_jpeg_entropy_decode (jpeg_huff.hip) and the latter's host twin (jpeg_decode.cpp, which is
+// also built on its own without the device code).  Plain C++, no HIP types.
 #ifndef LLFE_JPEG_DESC_CHECK_H
 #define LLFE_JPEG_DESC_CHECK_H
 #include <algorithm>
@@ -17,16 +17,6 @@
 #endif
 
 namespace llfe {
-
-// the planes of one image in the workspace: component c is blocks_h * 8 rows of blocks_w * 8 bytes
-LLFE_DESC_HD int64_t plane_bytes(const llfe_jpeg_desc &d, int c) {
-    return (int64_t)d.comp[c].blocks_w * d.comp[c].blocks_h * 64;
-}
-LLFE_DESC_HD int64_t plane_offset(const llfe_jpeg_desc &d, int c) {
-    int64_t o = 0;
-    for (int k = 0; k < c; k++) o += plane_bytes(d, k);
-    return o;
-}
 
 // one staged descriptor (n_comp != 0) against (h, w) and the bytes of its slot: false for any
 // offset or extent outside the slot, a block grid that does not cover the image or an unknown
@@ -63,21 +53,12 @@ inline bool check_jpeg_desc(const llfe_jpeg_desc &d, int h, int w, int64_t slot_
 }
 
 // n descriptors against (h, w) and the slot stride: false when check_jpeg_desc refuses one of
-// the staged ones; on success the bytes of plane workspace per image and the largest block
-// count of a component
-inline bool check_jpeg_descs(const llfe_jpeg_desc *descs, int n, int h, int w, int64_t slot_stride,
-                             int64_t *plane_stride, int *max_blocks) {
-    int64_t ps = 0, mb = 0;
+// the staged ones
+inline bool check_jpeg_descs(const llfe_jpeg_desc *descs, int n, int h, int w, int64_t slot_stride) {
     for (int i = 0; i < n; i++) {
-        const llfe_jpeg_desc &d = descs[i];
-        if (d.n_comp == 0) continue;
         int64_t blocks = 0;
-        if (!check_jpeg_desc(d, h, w, slot_stride, &blocks)) return false;
-        mb = std::max(mb, blocks);
-        ps = std::max(ps, plane_offset(d, d.n_comp));
+        if (descs[i].n_comp != 0 && !check_jpeg_desc(descs[i], h, w, slot_stride, &blocks)) return false;
     }
-    *plane_stride = (ps + 15) & ~(int64_t)15;
-    *max_blocks = (int)mb;
     return true;
 }
 

@@ -1,6 +1,6 @@
 // The entropy half of a baseline JPEG decode on the device: the scan's bytes (staged by
 // llfe_jpeg_parse_batch, jpeg_decode.cpp) -> exactly the coefficient slots that
-// llfe_jpeg_read_coefs_batch writes on the host, for llfe_jpeg_reconstruct (jpeg_recon.hip).
+// llfe_jpeg_read_coefs_batch writes on the host, for llfe_jpeg_reconstruct (jpeg_images.hip).
 // The decoding itself -- bit reader, tables, one subsequence -- is jpeg_huff_core.h, shared
 // with the host twin llfe_jpeg_entropy_reference.
 //

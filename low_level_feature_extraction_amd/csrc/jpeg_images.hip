@@ -1,7 +1,8 @@
 // JPEG reconstruction of a batch whose images each have their own size and sampling class
-// (llfe_jpeg_reconstruct_images): quantised coefficients in tight slots (staged by
-// llfe_jpeg_read_coefs_images, jpeg_decode.cpp) -> each image's packed H x W x 3 BGR result,
-// bit for bit what jpeg_recon.hip and the host decoder write.
+// (llfe_jpeg_reconstruct_images, and llfe_jpeg_reconstruct with every image of one size):
+// quantised coefficients in slots (staged by llfe_jpeg_read_coefs_images or
+// llfe_jpeg_read_coefs_batch, jpeg_decode.cpp) -> each image's packed H x W x 3 BGR result,
+// bit for bit what the host decoder writes.
 //
 // One launch over a host-built work table of (image, tile) entries; images that were not
 // staged have no entries.  A workgroup reconstructs one tile (jpeg_images.h JpegTiling) of
@@ -32,9 +33,9 @@
 //          a 128-pixel row two banks apart and consecutive tile rows one bank apart, and step 3's
 //          reads of four consecutive staging rows fall in four different bank classes mod 4.
 //
-// Every index derives from a record that llfe_jpeg_reconstruct_images validated on the host:
-// the descriptor against the image's own size and slot, the slot inside the coefficient
-// buffer, the result inside the output and apart from every other image's.
+// Every index derives from a record that the entry point validated on the host
+// (llfe_decode.cpp): the descriptor against the image's own size and slot, the slot inside the
+// coefficient buffer, the result inside the output and apart from every other image's.
 #include "jpeg_images.h"
 #include "jpeg_orient.h"
 #include "jpeg_recon_core.h"

@@ -375,12 +375,10 @@ struct llfe_ctx {
     // the hysteresis kernels (HostSlot::mask_ready, Lane::mask_reader)
     hipStream_t copy_stream = nullptr;
     llfe_host::HostBuf<llfe::KmeansImageOut> h_kout;
-    // llfe_jpeg_reconstruct: the validated descriptors (pinned, then on the device) and the
-    // u8 component planes of one chunk of images between its two kernels
+    // llfe_jpeg_entropy_decode: the validated descriptors (pinned, then on the device)
     llfe_host::HostBuf<llfe_jpeg_desc> h_jpeg_desc;
     llfe_host::DevBuf<llfe_jpeg_desc> d_jpeg_desc;
-    llfe_host::DevBuf<uint8_t> d_jpeg_planes;
-    // llfe_jpeg_reconstruct_images: the call's image records, then its (image, tile) work table
+    // llfe_jpeg_reconstruct[_images]: the call's image records, then its (image, tile) work table
     llfe_host::HostBuf<uint8_t> h_jpeg_img_tab;
     llfe_host::DevBuf<uint8_t> d_jpeg_img_tab;
     // llfe_jpeg_entropy_decode: the validated scan records and the kernels' workspace

@@ -41,11 +41,6 @@ int download_status(llfe_ctx *ctx, int32_t *status_out, int n, hipStream_t s) {
     return LLFE_OK;
 }
 
-// The plane workspace is bounded: images go through it in chunks on the one stream (a chunk's
-// colour kernel is ordered before the next chunk's IDCT).  256 MiB is 86 1080p 4:2:0 images
-// (1.5 plane bytes per pixel), 4 M blocks of IDCT per launch.
-constexpr int64_t kJpegPlaneBudget = (int64_t)256 << 20;
-
 // What both entropy entry points do behind their host checks.  For the images with
 // blocks_in_mcu != 0: the HuffImage records (those without a restart interval first; slot i at
 // images[i].slot_offset, or at i x slot_stride when images is null) and per kind the work table
@@ -144,6 +139,71 @@ int run_jpeg_huff(llfe_ctx *ctx, const char *who, const uint8_t *staging, int64_
     return download_status(ctx, status_out, n, s);
 }
 
+// What both reconstruction entry points do behind their host checks, on records the caller built
+// from what it validated: per orientation group the tile count and the bytes moved, the records
+// and then the work table (one part per group: a launch is uniform) up through one pinned buffer
+// in one copy, a launch per group present.  More than 2^31 tiles are LLFE_ERR_CAPACITY, before
+// any launch.
+int run_jpeg_images(llfe_ctx *ctx, const char *who, const uint8_t *coefs, const std::vector<llfe::JpegImageRec> &recs,
+                    uint8_t *out, hipStream_t s) {
+    using llfe::JpegImageRec;
+    using llfe::JpegWork;
+    int64_t group_work[llfe::kJpegOrientGroups] = {0, 0, 0};  // tiles per orientation group
+    double group_bytes[llfe::kJpegOrientGroups] = {0, 0, 0};
+    auto tiles_of = [](const JpegImageRec &r) {
+        llfe::JpegTiling t;
+        llfe::jpeg_tiling(r.d.sampling, &t);
+        return (int64_t)r.tiles_x * ((r.h + t.th - 1) / t.th);
+    };
+    for (const JpegImageRec &r : recs) {
+        const int g = llfe::jpeg_orient_group(r.orient);
+        group_work[g] += tiles_of(r);
+        for (int c = 0; c < r.d.n_comp; c++)
+            group_bytes[g] += (double)r.d.comp[c].blocks_w * r.d.comp[c].blocks_h * 128 + 128;
+        group_bytes[g] += (double)r.h * r.w * 3;  // (the same for both shapes)
+    }
+    const int64_t n_work = group_work[0] + group_work[1] + group_work[2];
+    if (n_work > 0x7fffffff) return ctx->fail(LLFE_ERR_CAPACITY, "%s: %lld tiles in one call", who, (long long)n_work);
+    if (recs.empty()) return LLFE_OK;
+    try {
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        const size_t rec_bytes = (recs.size() * sizeof(JpegImageRec) + 15) & ~(size_t)15;
+        const size_t tab_bytes = rec_bytes + (size_t)n_work * sizeof(JpegWork);
+        HIPCHK(ctx, ctx->h_jpeg_img_tab.ensure(tab_bytes));
+        HIPCHK(ctx, ctx->d_jpeg_img_tab.ensure(tab_bytes));
+        std::memcpy(ctx->h_jpeg_img_tab.p, recs.data(), recs.size() * sizeof(JpegImageRec));
+        JpegWork *wk = (JpegWork *)(ctx->h_jpeg_img_tab.p + rec_bytes);
+        for (int g = 0; g < llfe::kJpegOrientGroups; g++) {
+            if (group_work[g] == 0) continue;
+            for (size_t k = 0; k < recs.size(); k++) {
+                if (llfe::jpeg_orient_group(recs[k].orient) != g) continue;
+                const int tiles = (int)tiles_of(recs[k]);
+                for (int q = 0; q < tiles; q++) *wk++ = JpegWork{(int32_t)k, q};
+            }
+        }
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_jpeg_img_tab.p, ctx->h_jpeg_img_tab.p, tab_bytes, hipMemcpyHostToDevice, s));
+        {
+            StageSlotScope tag(ctx->prof);
+            // coefficients and tables in, BGR out: no plane goes through memory
+            static const char *const names[llfe::kJpegOrientGroups] = {"k_jpeg_images", "k_jpeg_images_mirrored",
+                                                                       "k_jpeg_images_transposed"};
+            const JpegWork *d_work = (const JpegWork *)(ctx->d_jpeg_img_tab.p + rec_bytes);
+            for (int g = 0; g < llfe::kJpegOrientGroups; g++) {
+                if (group_work[g] == 0) continue;
+                TIMED(ctx, s, names[g], group_bytes[g],
+                      llfe::launch_jpeg_images(coefs, (const JpegImageRec *)ctx->d_jpeg_img_tab.p, d_work,
+                                               (int)group_work[g], out, g, s));
+                d_work += group_work[g];
+            }
+        }
+        HIPCHK(ctx, hipStreamSynchronize(s));  // (the pinned table is free again)
+        ctx->prof.collect(Profiler::kStageSlot);
+    } catch (const std::bad_alloc &) {
+        return ctx->fail(LLFE_ERR_OOM, "%s: out of host memory", who);
+    }
+    return LLFE_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -155,38 +215,34 @@ int llfe_jpeg_reconstruct(llfe_ctx *ctx, const uint8_t *coefs, int64_t slot_stri
         (slot_stride & 15) || ((uintptr_t)coefs & 15))
         return ctx->fail(LLFE_ERR_INVALID, "llfe_jpeg_reconstruct: bad arguments (n=%d h=%d w=%d slot_stride=%lld)", n, h,
                          w, (long long)slot_stride);
-    int64_t plane_stride = 0;
-    int max_blocks = 0;
     // nothing is launched on a descriptor the host check has not passed
-    if (!validate_jpeg_descs(descs, n, h, w, slot_stride, &plane_stride, &max_blocks))
+    if (!llfe::check_jpeg_descs(descs, n, h, w, slot_stride))
         return ctx->fail(LLFE_ERR_INVALID, "llfe_jpeg_reconstruct: a descriptor points outside its slot or does not "
                                            "cover %dx%d", w, h);
-    if (n == 0 || max_blocks == 0) return LLFE_OK;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = (hipStream_t)stream;
-    int64_t budget = kJpegPlaneBudget;
-    if (const char *e = getenv("LLFE_JPEG_PLANE_BYTES"); e && atoll(e) > 0) budget = atoll(e);  // (tests: many chunks)
-    const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(n, budget / plane_stride));
-    HIPCHK(ctx, ensure_records(ctx->h_jpeg_desc, ctx->d_jpeg_desc, n));
-    HIPCHK(ctx, ctx->d_jpeg_planes.ensure((size_t)chunk * (size_t)plane_stride));
-    HIPCHK(ctx, upload_records(ctx->h_jpeg_desc, ctx->d_jpeg_desc, descs, n, s));
-    for (int i0 = 0; i0 < n; i0 += chunk) {
-        StageSlotScope tag(ctx->prof);
-        const int m = std::min(chunk, n - i0);
-        const uint8_t *cf = coefs + (size_t)i0 * (size_t)slot_stride;
-        uint8_t *o = out_bgr + (size_t)i0 * (size_t)h * w * 3;
-        const llfe_jpeg_desc *dd = ctx->d_jpeg_desc.p + i0;
-        // coefficients in (2 B each, at most 3 per pixel), planes out; planes in, BGR out
-        TIMED(ctx, s, "k_jpeg_idct", (double)m * plane_stride * 3,
-              launch_jpeg_reconstruct(cf, slot_stride, dd, m, h, w, max_blocks, ctx->d_jpeg_planes.p, plane_stride, o, s,
-                                      0));
-        TIMED(ctx, s, "k_jpeg_color", (double)m * (plane_stride + (double)h * w * 3),
-              launch_jpeg_reconstruct(cf, slot_stride, dd, m, h, w, max_blocks, ctx->d_jpeg_planes.p, plane_stride, o, s,
-                                      1));
+    // one record per staged image; image i's slot and result lie where its index puts them
+    std::vector<llfe::JpegImageRec> recs;
+    try {
+        llfe::JpegTiling t;
+        recs.reserve((size_t)n);
+        for (int i = 0; i < n; i++) {
+            if (descs[i].n_comp == 0) continue;  // staged elsewhere: its place in out stays as it is
+            llfe::jpeg_tiling(descs[i].sampling, &t);
+            llfe::JpegImageRec r;
+            r.d = descs[i];
+            r.slot_offset = (int64_t)i * slot_stride;
+            r.out_offset = (int64_t)i * h * w * 3;
+            r.h = h;
+            r.w = w;
+            r.tiles_x = (w + t.tw - 1) / t.tw;
+            // (the result is tightly packed: an image may start at any byte)
+            r.vec = (w % 4 == 0 && ((uintptr_t)(out_bgr + r.out_offset) & 3) == 0) ? 1 : 0;
+            r.orient = 1;
+            recs.push_back(r);
+        }
+    } catch (const std::bad_alloc &) {
+        return ctx->fail(LLFE_ERR_OOM, "llfe_jpeg_reconstruct: out of host memory");
     }
-    HIPCHK(ctx, hipStreamSynchronize(s));  // (the pinned descriptors and the planes are free again)
-    ctx->prof.collect(Profiler::kStageSlot);
-    return LLFE_OK;
+    return run_jpeg_images(ctx, "llfe_jpeg_reconstruct", coefs, recs, out_bgr, (hipStream_t)stream);
 }
 
 int llfe_jpeg_images_tiling(int32_t sampling, int32_t *tile_w, int32_t *tile_h) {
@@ -209,7 +265,6 @@ int llfe_jpeg_reconstruct_images_oriented(llfe_ctx *ctx, const uint8_t *coefs, i
                                           const uint8_t *orientation, int32_t n, uint8_t *out, int64_t out_capacity,
                                           llfe_stream stream) {
     using llfe::JpegImageRec;
-    using llfe::JpegWork;
     if (!ctx) return LLFE_ERR_INVALID;
     if (n < 0 || (n && (!coefs || !images || !descs || !out)) || coefs_bytes < 0 || out_capacity < 0 ||
         ((uintptr_t)coefs & 15))
@@ -218,9 +273,7 @@ int llfe_jpeg_reconstruct_images_oriented(llfe_ctx *ctx, const uint8_t *coefs, i
     // nothing is launched on a record the host check has not passed
     std::vector<JpegImageRec> recs;
     std::vector<std::pair<int64_t, int64_t>> ranges;  // [begin, end) of every result
-    int64_t n_work = 0, out_end = 0;
-    int64_t group_work[llfe::kJpegOrientGroups] = {0, 0, 0};  // tiles per orientation group
-    double group_bytes[llfe::kJpegOrientGroups] = {0, 0, 0};
+    int64_t out_end = 0;
     try {
         recs.reserve((size_t)n);
         ranges.reserve((size_t)n);
@@ -254,13 +307,6 @@ int llfe_jpeg_reconstruct_images_oriented(llfe_ctx *ctx, const uint8_t *coefs, i
             const int64_t px_bytes = (int64_t)m.height * m.width * 3;  // (the same for both shapes)
             ranges.emplace_back(m.out_offset, m.out_offset + px_bytes);
             out_end = std::max(out_end, m.out_offset + px_bytes);
-            const int64_t tiles = (int64_t)r.tiles_x * ((m.height + t.th - 1) / t.th);
-            n_work += tiles;
-            const int g = llfe::jpeg_orient_group(o);
-            group_work[g] += tiles;
-            for (int c = 0; c < d.n_comp; c++)
-                group_bytes[g] += (double)d.comp[c].blocks_w * d.comp[c].blocks_h * 128 + 128;
-            group_bytes[g] += (double)px_bytes;
         }
         std::sort(ranges.begin(), ranges.end());
         for (size_t k = 1; k < ranges.size(); k++)
@@ -269,51 +315,10 @@ int llfe_jpeg_reconstruct_images_oriented(llfe_ctx *ctx, const uint8_t *coefs, i
         if (out_end > out_capacity)
             return ctx->fail(LLFE_ERR_CAPACITY, "llfe_jpeg_reconstruct_images: out holds %lld bytes, the results end at "
                                                 "%lld", (long long)out_capacity, (long long)out_end);
-        if (n_work > 0x7fffffff)
-            return ctx->fail(LLFE_ERR_CAPACITY, "llfe_jpeg_reconstruct_images: %lld tiles in one call",
-                             (long long)n_work);
-        if (recs.empty()) return LLFE_OK;
-        HIPCHK(ctx, hipSetDevice(ctx->device));
-        hipStream_t s = (hipStream_t)stream;
-        // the records, then the work table (one part per orientation group: a launch is uniform),
-        // through one pinned buffer
-        const size_t rec_bytes = (recs.size() * sizeof(JpegImageRec) + 15) & ~(size_t)15;
-        const size_t tab_bytes = rec_bytes + (size_t)n_work * sizeof(JpegWork);
-        HIPCHK(ctx, ctx->h_jpeg_img_tab.ensure(tab_bytes));
-        HIPCHK(ctx, ctx->d_jpeg_img_tab.ensure(tab_bytes));
-        std::memcpy(ctx->h_jpeg_img_tab.p, recs.data(), recs.size() * sizeof(JpegImageRec));
-        JpegWork *wk = (JpegWork *)(ctx->h_jpeg_img_tab.p + rec_bytes);
-        for (int g = 0; g < llfe::kJpegOrientGroups; g++) {
-            if (group_work[g] == 0) continue;
-            for (size_t k = 0; k < recs.size(); k++) {
-                if (llfe::jpeg_orient_group(recs[k].orient) != g) continue;
-                llfe::JpegTiling t;
-                llfe::jpeg_tiling(recs[k].d.sampling, &t);
-                const int tiles = recs[k].tiles_x * ((recs[k].h + t.th - 1) / t.th);
-                for (int q = 0; q < tiles; q++) *wk++ = JpegWork{(int32_t)k, q};
-            }
-        }
-        HIPCHK(ctx, hipMemcpyAsync(ctx->d_jpeg_img_tab.p, ctx->h_jpeg_img_tab.p, tab_bytes, hipMemcpyHostToDevice, s));
-        {
-            StageSlotScope tag(ctx->prof);
-            // coefficients and tables in, BGR out: no plane goes through memory
-            static const char *const names[llfe::kJpegOrientGroups] = {"k_jpeg_images", "k_jpeg_images_mirrored",
-                                                                       "k_jpeg_images_transposed"};
-            const JpegWork *d_work = (const JpegWork *)(ctx->d_jpeg_img_tab.p + rec_bytes);
-            for (int g = 0; g < llfe::kJpegOrientGroups; g++) {
-                if (group_work[g] == 0) continue;
-                TIMED(ctx, s, names[g], group_bytes[g],
-                      llfe::launch_jpeg_images(coefs, (const JpegImageRec *)ctx->d_jpeg_img_tab.p, d_work,
-                                               (int)group_work[g], out, g, s));
-                d_work += group_work[g];
-            }
-        }
-        HIPCHK(ctx, hipStreamSynchronize(s));  // (the pinned table is free again)
-        ctx->prof.collect(Profiler::kStageSlot);
     } catch (const std::bad_alloc &) {
         return ctx->fail(LLFE_ERR_OOM, "llfe_jpeg_reconstruct_images: out of host memory");
     }
-    return LLFE_OK;
+    return run_jpeg_images(ctx, "llfe_jpeg_reconstruct_images", coefs, recs, out, (hipStream_t)stream);
 }
 
 int llfe_jpeg_entropy_decode(llfe_ctx *ctx, const uint8_t *staging, int64_t staging_bytes, const llfe_jpeg_scan *scans,
@@ -325,10 +330,9 @@ int llfe_jpeg_entropy_decode(llfe_ctx *ctx, const uint8_t *staging, int64_t stag
         ((uintptr_t)slots & 15) || staging_bytes < 0 || ((uintptr_t)staging & 15))
         return ctx->fail(LLFE_ERR_INVALID, "llfe_jpeg_entropy_decode: bad arguments (n=%d h=%d w=%d slot_stride=%lld)", n,
                          h, w, (long long)slot_stride);
-    int64_t plane_stride = 0;
-    int recon_blocks = 0, max_sub = 0, max_blocks = 0;
+    int max_sub = 0, max_blocks = 0;
     // nothing is launched on a descriptor or a record the host check has not passed
-    if (!validate_jpeg_descs(descs, n, h, w, slot_stride, &plane_stride, &recon_blocks))
+    if (!llfe::check_jpeg_descs(descs, n, h, w, slot_stride))
         return ctx->fail(LLFE_ERR_INVALID, "llfe_jpeg_entropy_decode: a descriptor points outside its slot or does not "
                                            "cover %dx%d", w, h);
     if (!llfe_huff::validate_scans(scans, descs, n, staging_bytes, &max_sub, &max_blocks))

@@ -402,19 +402,7 @@ hipError_t launch_text_otsu_binary(const uint8_t *g, long long n, unsigned long 
 // tab (device) = n source addresses, then n row pitches in bytes
 hipError_t launch_gather_images(const uint64_t *tab, int n, int h, int w, uint8_t *dst, hipStream_t s);
 
-// llfe_jpeg_reconstruct (jpeg_recon.hip).  validate: the host check of n descriptors against
-// (h, w) and the slot stride -- false for any offset or extent outside the slot, a block grid
-// that does not cover the image or an unknown sampling class; on success the bytes of plane
-// workspace per image and the largest block count of a component.  launch: stage 0 = inverse
-// DCT of every component into the u8 planes (n x plane_stride), stage 1 = upsampling + colour
-// conversion of the planes into out (n x h x w x 3); d_descs is the validated array on the device.
-bool validate_jpeg_descs(const llfe_jpeg_desc *descs, int n, int h, int w, int64_t slot_stride,
-                         int64_t *plane_stride, int *max_blocks);
-hipError_t launch_jpeg_reconstruct(const uint8_t *coefs, int64_t slot_stride, const llfe_jpeg_desc *d_descs, int n,
-                                   int h, int w, int max_blocks, uint8_t *planes, int64_t plane_stride, uint8_t *out,
-                                   hipStream_t s, int stage);
-
-// llfe_jpeg_reconstruct_images (jpeg_images.hip; records and tiling in jpeg_images.h): one
+// llfe_jpeg_reconstruct and llfe_jpeg_reconstruct_images (jpeg_images.hip; records and tiling in jpeg_images.h): one
 // launch over n_work (image, tile) entries; d_recs holds the validated records of the call's
 // images, coefs / out are the bases their slot / result offsets count from.  group: the
 // orientation group (jpeg_orient.h jpeg_orient_group) of every image the entries name.

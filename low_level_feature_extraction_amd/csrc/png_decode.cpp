@@ -27,12 +27,11 @@
 #include <cstdlib>
 
 #include <algorithm>
-#include <atomic>
 #include <cstdint>
 #include <cstring>
-#include <thread>
 #include <vector>
 
+#include "host_fanout.h"
 #include "llfe.h"
 #include "png_inflate_core.h"
 
@@ -608,44 +607,34 @@ extern "C" int llfe_jpeg_images_layout_flags(const uint8_t *const *data, const u
         return LLFE_ERR_INVALID;
     const bool orient = (flags & LLFE_JPEG_ORIENT) != 0;
     for (int i = 0; orientation && i < n; i++) orientation[i] = 1;
-    const int nt = std::max(1, std::min<int>(threads > 0 ? threads : 1, n));
-    std::atomic<int> next{0};
-    auto work = [&]() {
-        for (int i; (i = next.fetch_add(1)) < n;) {
-            llfe_jpeg_image &m = images[i];  // (out_offset is the caller's)
-            m.slot_offset = m.slot_bytes = 0;
-            m.height = m.width = 0;
-            int rc;
-            if (!data[i]) {
-                rc = LLFE_ERR_INVALID;
-            } else if (is_jpeg(data[i], (size_t)sizes[i])) {
-                rc = orient ? llfe_jpeg_layout_one_oriented(data[i], (size_t)sizes[i], &m.height, &m.width, &m.slot_bytes,
-                                                            &orientation[i])
-                            : llfe_jpeg_layout_one(data[i], (size_t)sizes[i], &m.height, &m.width, &m.slot_bytes);
-                if ((uint64_t)(uint32_t)m.width * (uint32_t)m.height > max_pixels()) rc = LLFE_ERR_CAPACITY;
-                if (rc) m.slot_bytes = 0;
-                if (rc && orient) orientation[i] = 1;
-            } else {  // another format: its size when its header gives one
-                rc = llfe_image_info(data[i], sizes[i], &m.width, &m.height);
-                if (rc == LLFE_OK) rc = LLFE_ERR_UNSUPPORTED;
-                if (rc != LLFE_ERR_UNSUPPORTED && rc != LLFE_ERR_CAPACITY) m.height = m.width = 0;
-            }
-            status[i] = rc;
+    const int first = llfe::fan_out(n, threads, status, [&](int i) {
+        llfe_jpeg_image &m = images[i];  // (out_offset is the caller's)
+        m.slot_offset = m.slot_bytes = 0;
+        m.height = m.width = 0;
+        int rc;
+        if (!data[i]) {
+            rc = LLFE_ERR_INVALID;
+        } else if (is_jpeg(data[i], (size_t)sizes[i])) {
+            rc = orient ? llfe_jpeg_layout_one_oriented(data[i], (size_t)sizes[i], &m.height, &m.width, &m.slot_bytes,
+                                                        &orientation[i])
+                        : llfe_jpeg_layout_one(data[i], (size_t)sizes[i], &m.height, &m.width, &m.slot_bytes);
+            if ((uint64_t)(uint32_t)m.width * (uint32_t)m.height > max_pixels()) rc = LLFE_ERR_CAPACITY;
+            if (rc) m.slot_bytes = 0;
+            if (rc && orient) orientation[i] = 1;
+        } else {  // another format: its size when its header gives one
+            rc = llfe_image_info(data[i], sizes[i], &m.width, &m.height);
+            if (rc == LLFE_OK) rc = LLFE_ERR_UNSUPPORTED;
+            if (rc != LLFE_ERR_UNSUPPORTED && rc != LLFE_ERR_CAPACITY) m.height = m.width = 0;
         }
-    };
-    std::vector<std::thread> th;
-    for (int t = 1; t < nt; t++) th.emplace_back(work);
-    work();
-    for (auto &t : th) t.join();
+        return rc;
+    });
     int64_t off = 0;
     for (int i = 0; i < n; i++) {
         images[i].slot_offset = off;
         off += images[i].slot_bytes;
     }
     *slots_bytes = off;
-    for (int i = 0; i < n; i++)
-        if (status[i]) return status[i];
-    return LLFE_OK;
+    return first;
 }
 
 namespace {
@@ -654,27 +643,10 @@ int decode_fanout(const uint8_t *const *data, const uint64_t *sizes, int32_t n, 
                   uint8_t *out_bgr, int32_t *status, int32_t threads, F one) {
     if (n < 0 || (n && (!data || !sizes || !out_bgr || !status)) || height <= 0 || width <= 0) return LLFE_ERR_INVALID;
     const size_t img_bytes = (size_t)height * width * 3;
-    const int nt = std::max(1, std::min<int>(threads > 0 ? threads : 1, n));
-    std::atomic<int> next{0};
-    auto work = [&]() {
-        for (int i; (i = next.fetch_add(1)) < n;) {
-            int rc;
-            try {
-                rc = data[i] ? one(data[i], (size_t)sizes[i], height, width, out_bgr + (size_t)i * img_bytes)
-                             : LLFE_ERR_INVALID;
-            } catch (const std::bad_alloc &) {
-                rc = LLFE_ERR_OOM;
-            }
-            status[i] = rc;
-        }
-    };
-    std::vector<std::thread> th;
-    for (int t = 1; t < nt; t++) th.emplace_back(work);
-    work();
-    for (auto &t : th) t.join();
-    for (int i = 0; i < n; i++)
-        if (status[i]) return status[i];
-    return LLFE_OK;
+    return llfe::fan_out(n, threads, status, [&](int i) {
+        return data[i] ? one(data[i], (size_t)sizes[i], height, width, out_bgr + (size_t)i * img_bytes)
+                       : LLFE_ERR_INVALID;
+    });
 }
 }  // namespace
 
@@ -776,31 +748,16 @@ extern "C" int llfe_png_parse_batch(const uint8_t *const *data, const uint64_t *
     if (n < 0 || (n && (!data || !sizes || !staging || !descs || !status)) || height <= 0 || width <= 0 ||
         record_stride < 48 || (record_stride & 15))
         return LLFE_ERR_INVALID;
-    const int nt = std::max(1, std::min<int>(threads > 0 ? threads : 1, n));
-    std::atomic<int> next{0};
-    auto work = [&]() {
-        for (int i; (i = next.fetch_add(1)) < n;) {
-            llfe_png_desc d{};
-            d.record_offset = (int64_t)i * record_stride;
-            int rc;
-            try {
-                rc = data[i] ? stage_one(data[i], (size_t)sizes[i], height, width, staging + d.record_offset, record_stride, &d)
-                             : LLFE_ERR_INVALID;
-            } catch (const std::bad_alloc &) {
-                rc = LLFE_ERR_OOM;
-            }
-            if (rc) d = llfe_png_desc{};
-            descs[i] = d;
-            status[i] = rc;
-        }
-    };
-    std::vector<std::thread> th;
-    for (int t = 1; t < nt; t++) th.emplace_back(work);
-    work();
-    for (auto &t : th) t.join();
-    for (int i = 0; i < n; i++)
-        if (status[i]) return status[i];
-    return LLFE_OK;
+    return llfe::fan_out(n, threads, status, [&](int i) {
+        descs[i] = llfe_png_desc{};  // deflate_bytes 0: nothing staged for this image
+        llfe_png_desc d{};
+        d.record_offset = (int64_t)i * record_stride;
+        const int rc = data[i] ? stage_one(data[i], (size_t)sizes[i], height, width, staging + d.record_offset,
+                                           record_stride, &d)
+                               : LLFE_ERR_INVALID;
+        if (rc == LLFE_OK) descs[i] = d;
+        return rc;
+    });
 }
 
 extern "C" int llfe_png_decode_reference(const uint8_t *staging, int64_t staging_bytes, const llfe_png_desc *descs,

@@ -12,7 +12,7 @@ PNG, CMYK JPEG, EXIF-rotated JPEG, other formats) is decoded with Pillow.  Image
 above ``MAX_PIXELS`` (cv2's CV_IO_MAX_IMAGE_PIXELS, 2^30) fail like cv2.imdecode does.
 
 ``decode_batch_device`` (opt-in, at the end of this module) returns the same batch in device
-memory: for JPEG the host stops after the entropy half and csrc/jpeg_recon.hip reconstructs;
+memory: for JPEG the host stops after the entropy half and csrc/jpeg_images.hip reconstructs;
 with ``entropy="device"`` baseline files are entropy-decoded on the device too (csrc/jpeg_huff.hip);
 with ``png="device"`` 8-bit RGB / RGBA PNGs are inflated, unfiltered and converted there
 (csrc/png_inflate.hip).  ``decode_images_device`` (opt-in too) is decode_many's device form for
@@ -278,7 +278,7 @@ def decode_batch(blobs, out=None, workers=None) -> np.ndarray:
 # The same decode split in two (DESIGN.md §3 "JPEG reconstruction on the device"): the host
 # stops after the entropy half (llfe_jpeg_read_coefs_batch: libjpeg-turbo's
 # jpeg_read_coefficients), the quantised coefficients cross PCIe, and llfe_jpeg_reconstruct
-# (csrc/jpeg_recon.hip) writes the BGR batch in device memory, bit for bit what decode_batch
+# (csrc/jpeg_images.hip) writes the BGR batch in device memory, bit for bit what decode_batch
 # writes on the host.  Opt-in: nothing above calls it.
 _STAGE_RING = 3  # staging buffers per (size, count): extraction of batch k + 1 beside batch k's copy
 _RINGS = {}  # family ("coefs" / "bytes" / "png") -> {(n, stride): ring}
@@ -1119,7 +1119,7 @@ def decode_batch_device(blobs, device=0, workers=None, out=None, entropy="host",
     (N, H, W, 3) BGR uint8 tensor on ``device``, the same bytes decode_batch returns.  Eligible
     JPEGs (8-bit greyscale or YCbCr 4:4:4 / 4:2:2 / 4:2:0, EXIF orientation 1, no decoder
     warning) are entropy-decoded on ``workers`` host threads and reconstructed by
-    csrc/jpeg_recon.hip; everything else (PNG, CMYK, EXIF-rotated, other samplings, truncated
+    csrc/jpeg_images.hip; everything else (PNG, CMYK, EXIF-rotated, other samplings, truncated
     files) goes through the host decoders image by image.  Raises DecodeError as decode_batch
     does.  The result feeds Backend.process / submit unchanged.
 

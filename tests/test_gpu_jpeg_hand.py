@@ -3,7 +3,7 @@ csrc/jpeg_huff.hip (batch, ragged and restart instances) gives the status of its
 by image -- zero for every "ok" file, with coefficient slots equal to decode.stage_coefs
 (libjpeg-turbo's jpeg_read_coefficients) over every byte the image occupies -- and hands back what
 the twin hands back; the public doors give the host decoder's pixels or its error for every file,
-in a batch and alone; and csrc/jpeg_recon.hip / csrc/jpeg_images.hip reconstruct coefficients and
+in a batch and alone; and csrc/jpeg_images.hip, behind both of its entries, reconstructs coefficients and
 16-bit quantisation tables that no encoder produces to the library's bytes.  Every stream here,
 malformed ones included, stays inside its staged record and passes the host checks in front of the
 kernels.  tests/test_jpeg_hand_inputs.py checks the same list against the twin on the CPU."""
@@ -133,7 +133,7 @@ def test_all_cases_in_one_shuffled_ragged_call(backend):
 
 
 def test_reconstruction_of_tables_and_coefficients_no_encoder_makes(backend):
-    """The host's coefficients through jpeg_recon.hip and jpeg_images.hip: 16-bit table entries
+    """The host's coefficients through llfe_jpeg_reconstruct and llfe_jpeg_reconstruct_images: 16-bit table entries
     whose products wrap, the whole-block DC shortcut beside the full pass, samples far outside
     0..255, saturated chroma through the triangle upsampling and the colour clamp."""
     by_size = {}

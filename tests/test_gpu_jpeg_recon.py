@@ -1,11 +1,13 @@
-"""JPEG reconstruction on the device (csrc/jpeg_recon.hip behind decode.decode_batch_device):
-the same bytes as the host decoder (decode.decode_batch, i.e. cv2.imdecode(IMREAD_COLOR) at
-utils.py:108-109 / image_processor.py:208-211), for every case of tests/jpeg_restate.py
-(which test_jpeg_coefs.py pins against the installed libjpeg-turbo on the CPU), for mixed
-batches with host fallbacks, and on the kernels' seams: 32 blocks per IDCT workgroup, 256
-columns x 4 rows per colour workgroup, rows that are / are not 4-byte aligned, more than
-one chunk of plane workspace.  A descriptor that points outside its slot is refused by the
-host check before any launch."""
+"""JPEG reconstruction on the device (llfe_jpeg_reconstruct, the tile kernel of
+csrc/jpeg_images.hip, behind decode.decode_batch_device): the same bytes as the host decoder
+(decode.decode_batch, i.e. cv2.imdecode(IMREAD_COLOR) at utils.py:108-109 /
+image_processor.py:208-211), for every case of tests/jpeg_restate.py (which test_jpeg_coefs.py
+pins against the installed libjpeg-turbo on the CPU), for mixed batches with host fallbacks,
+and on the kernel's seams: the tile of each sampling class (64 x 32 for 4:4:4, 128 x 32 for
+4:2:2 and grey, 128 x 64 for 4:2:0) in both directions, rows and images that are / are not
+4-byte aligned, classes mixed in one call, an image in the middle of a call that is not
+staged.  A descriptor that points outside its slot is refused by the host check before any
+launch."""
 import dataclasses
 import io
 
@@ -60,11 +62,14 @@ def test_mixed_batch_with_fallbacks(backend):
     assert np.array_equal(got[10], decode.decode_bgr(blobs[10]))
 
 
-@pytest.mark.parametrize("h,w,sub", [(70, 530, 2), (9, 260, 2), (12, 256, 1), (5, 1028, 0), (130, 136, 2)])
+@pytest.mark.parametrize("h,w,sub", [(70, 530, 2), (9, 260, 2), (12, 256, 1), (5, 1028, 0), (130, 136, 2),
+                                     (40, 72, 0), (40, 136, 1)])
 def test_kernel_seams(backend, h, w, sub):
-    """Widths across the colour kernel's 256-column workgroups with 4-byte aligned rows
-    (dword stores) and without (byte tail), block counts that are no multiple of the IDCT's
-    32 per workgroup; a subsampled batch fills half a slot, so its slots are copied piecewise."""
+    """Sizes across the tile of the class, which one workgroup reconstructs: several tiles in a
+    row with 4-byte aligned rows (dword stores) and without (byte tail), a last tile of a few
+    columns or rows, 2 x 2 tiles of the 4:4:4 tile (40 x 72) and of the 4:2:2 and grey tile
+    (40 x 136), 3 x 2 of the 4:2:0 tile (130 x 136: chroma halo blocks on every side); a
+    subsampled batch fills half a slot, so its slots are copied piecewise."""
     rng = np.random.default_rng(h * w)
     blobs = [R.jpeg(synth.synth_numpy(0, h, w, seed=2)[:, :, ::-1].copy(), quality=85, subsampling=sub),
              R.jpeg(rng.integers(0, 256, (h, w, 3), dtype=np.uint8), quality=40, subsampling=sub),
@@ -81,10 +86,9 @@ def test_hand_made_tables_equal_host_decode(backend):
     _same(blobs)
 
 
-def test_more_than_one_chunk_of_planes(backend, monkeypatch):
-    """The plane workspace is bounded and images go through it chunk by chunk: with the bound
-    at one 40 x 56 image, five images are five chunks."""
-    monkeypatch.setenv("LLFE_JPEG_PLANE_BYTES", "4096")
+def test_three_classes_in_one_call(backend):
+    """Five 40 x 56 images of three sampling classes in one call: every image's tiles find
+    their own record, slot and place in the result."""
     rng = np.random.default_rng(11)
     blobs = [R.jpeg(rng.integers(0, 256, (40, 56, 3), dtype=np.uint8), quality=50 + 10 * i, subsampling=i % 3)
              for i in range(5)]
@@ -108,6 +112,30 @@ def test_out_tensor_and_process_equal_host_path(backend):
         for f in dataclasses.fields(x):
             u, v = getattr(x, f.name), getattr(y, f.name)
             assert np.array_equal(u, v) if isinstance(u, np.ndarray) else u == v, f.name
+
+
+@pytest.mark.parametrize("h,w", [(17, 33), (16, 16)])
+def test_skipped_image_in_the_middle(backend, h, w):
+    """One image per sampling class, the second not staged (n_comp = 0): its place in out
+    stays as it was and the images behind it still land at their own index.  17 x 33 is 1683
+    bytes per image, so every later image starts at an odd address and takes byte stores;
+    16 x 16 is 768 bytes per image, dword stores."""
+    import torch
+
+    rng = np.random.default_rng(h * w)
+    blobs = [R.jpeg(rng.integers(0, 256, (h, w, 3), dtype=np.uint8), quality=80, subsampling=sub) for sub in (2, 1, 0)]
+    blobs.append(R.jpeg(rng.integers(0, 256, (h, w), dtype=np.uint8), quality=80))
+    st = decode.stage_coefs(blobs, workers=2)
+    assert st.status == [0, 0, 0, 0]
+    descs = (_lib.LlfeJpegDesc * 4).from_buffer_copy(st.descs)
+    descs[1].n_comp = 0
+    out = torch.full((4, h, w, 3), 77, dtype=torch.uint8, device="cuda:0")
+    backend.jpeg_reconstruct(torch.from_numpy(st.slots).cuda(), descs, h, w, out=out)
+    got = out.cpu().numpy()
+    want = decode.decode_batch(blobs, workers=2)
+    assert (got[1] == 77).all()
+    for i in (0, 2, 3):
+        assert np.array_equal(got[i], want[i]), f"image {i} differs at {np.argwhere(got[i] != want[i])[:4].tolist()}"
 
 
 def test_descriptor_outside_the_slot_is_refused_on_the_host(backend):

@@ -6,7 +6,7 @@ reconstruction -- dequantise, ISLOW inverse DCT, fancy upsampling, YCbCr -> BGR 
 the extracted coefficients must equal the native host decoder's bytes
 (cv2.imdecode(IMREAD_COLOR), utils.py:108-109, image_processor.py:208-211).  That pins the
 hand-declared jpeg_component_info / JQUANT_TBL / jpeg_memory_mgr layouts and the arithmetic
-that csrc/jpeg_recon.hip restates against the installed library without a GPU.
+that csrc/jpeg_recon_core.h restates against the installed library without a GPU.
 """
 import ctypes as C
 import io
@@ -69,7 +69,7 @@ def test_inputs_leave_the_sample_range_before_limiting():
 def test_samples_far_outside_the_range_saturate_as_the_library_does(k):
     """Quality-100 noise with its all-ones tables scaled by 5: samples land more than 384
     outside 0..255, where libjpeg-turbo's C code (a 1024-entry table under a 10-bit mask)
-    wraps and its SIMD code saturates.  The installed library decides; jpeg_recon.hip and
+    wraps and its SIMD code saturates.  The installed library decides; jpeg_images.hip and
     the restatement saturate."""
     b = R.scaled_tables(R.blob(16, 16, k), 5)
     rc, want = R.host_decode(b)
@@ -86,7 +86,7 @@ def test_samples_far_outside_the_range_saturate_as_the_library_does(k):
 def test_hand_made_tables_decode_as_the_library_decodes_them(h, w, k, factor):
     """Tables scaled until the dequantised values leave what any encoder emits: the library's
     SIMD code then wraps its 16-bit products and sums and saturates its 16-bit workspace.  The
-    restatement (and jpeg_recon.hip, test_gpu_jpeg_recon.py) follows it bit for bit, so such
+    restatement (and jpeg_images.hip, test_gpu_jpeg_recon.py) follows it bit for bit, so such
     files too decode to the host path's bytes."""
     b = R.scaled_tables(R.blob(h, w, k), factor)
     rc, want = R.host_decode(b)

@@ -112,6 +112,20 @@ def test_refused_files_leave_nothing_written():
     assert status == [H.UNSUPPORTED] and (rec == 0xA5).all()
     assert _parse([ok], h, w, stride=_lib.JPEG_RECORD_HEADER - 16)[0] == H.INVALID
     assert _parse([ok], 0, w, slot_bytes=4096)[0] == H.INVALID
+    # the thread fan-out: any thread count, more threads than images included, gives every image
+    # its own status and record and returns the first non-zero status in index order
+    ok2 = R.jpeg(arr[::-1].copy(), quality=60, subsampling=0)
+    garbage = bytes(rng.integers(0, 256, 300, dtype=np.uint8))
+    blobs = [ok, ok2, garbage, b"", ok]
+    _, _, rec1, descs1, scans1 = _parse(blobs, h, w, threads=1)
+    for threads in (0, 1, 3, 64):
+        rc, status, rec, descs, scans = _parse(blobs, h, w, threads=threads)
+        assert [s != 0 for s in status] == [False, False, True, True, False]
+        assert rc == status[2]
+        for i in (0, 1, 4):
+            assert np.array_equal(rec[i], rec1[i]) and not (rec[i] == 0xA5).all()
+            assert bytes(descs[i]) == bytes(descs1[i]) and bytes(scans[i]) == bytes(scans1[i])
+        assert _parse([], h, w, threads=threads, stride=_lib.JPEG_RECORD_HEADER + 64)[0] == 0
 
 
 @pytest.mark.parametrize("sub", [2, 1, 0])

@@ -18,7 +18,8 @@ JPEG leg are not touched: this tool measures the opt-in path beside them.
                decode.decode_staged_bytes (H2D of the records, llfe_jpeg_entropy_decode,
                llfe_jpeg_reconstruct) and the device batch submitted.
            A, B and C alternate in one process, --legs each; then the producers alone, the
-           isolated kernel times (llfe_kernel_stats) and the H2D times of one batch of
+           isolated kernel times (llfe_kernel_stats; llfe_jpeg_reconstruct reports its one
+           launch as k_jpeg_images) and the H2D times of one batch of
            coefficients and of one batch of records.  The bar B had to clear over A is applied
            to C over B: every C leg above every B leg, medians further apart than three times
            B's min-max range.

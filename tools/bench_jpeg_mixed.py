@@ -5,7 +5,8 @@ profiles/jpeg_images/).  bench.py is not touched: this tool measures the new ent
 
   A  decode.decode_many (decode_bgr per image on the decode pool) and one upload per image:
      what ImageProcessor.auto_process_images(device=True) does by default
-  B  group the feed by size, decode.decode_batch_device per group (csrc/jpeg_recon.hip)
+  B  group the feed by size, decode.decode_batch_device per group (llfe_jpeg_reconstruct: the
+     kernel of C, one launch per group)
   C  decode.decode_images_device: one staging buffer, one launch (csrc/jpeg_images.hip)
   D  decode.decode_images_device(entropy="device"): C with the entropy decode on the device too
      (csrc/jpeg_huff.hip; DESIGN.md §3 "JPEG entropy decode of a mixed-size batch"; figures in
@@ -23,9 +24,9 @@ A seeded feed of --images quality-85 4:2:0 JPEGs, one process, one rank, a warm-
                   behaviour before the option) against Co and Do, the same two with
                   orient="device"; A and B are not run.  The profiled passes give k_jpeg_images per
                   orientation group (k_jpeg_images, _mirrored, _transposed).
-After the timed legs one profiled pass of B, of C and of D gives the kernel ms (llfe_kernel_stats):
-k_jpeg_idct + k_jpeg_color against k_jpeg_images on the same coefficients, and D's k_huff_*
-kernels (k_huff_sync: one launch per pass and kind).  One JSON line on stdout.
+After the timed legs one profiled pass of C and of D gives the kernel ms (llfe_kernel_stats):
+k_jpeg_images, and D's k_huff_* kernels (k_huff_sync: one launch per pass and kind).  One JSON
+line on stdout.
 """
 from __future__ import annotations
 
@@ -200,7 +201,7 @@ def main():
     del ra, rb, rc, rd
 
     legs = run_legs(args, routes, len(blobs))
-    kb, kc, kd = profiled(be, route_b), profiled(be, route_c), profiled(be, route_d)
+    kc, kd = profiled(be, route_c), profiled(be, route_d)
     summary = {k: {"median": statistics.median(v), "min": min(v), "max": max(v)} for k, v in legs.items()}
     spread = max(summary[k]["max"] - summary[k]["min"] for k in ("A", "B"))
     out = {
@@ -212,7 +213,7 @@ def main():
         "C_minus_best_base_median": round(summary["C"]["median"] - max(summary["A"]["median"], summary["B"]["median"]), 1),
         "D_minus_C_median": round(summary["D"]["median"] - summary["C"]["median"], 1),
         "three_times_base_spread": round(3 * spread, 1),
-        "kernels_ms_per_pass": {"B": kb, "C": kc, "D": kd},
+        "kernels_ms_per_pass": {"C": kc, "D": kd},
         "device": torch.cuda.get_device_name(0),
     }
     print(json.dumps(out))
