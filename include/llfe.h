@@ -228,6 +228,56 @@ int llfe_process_images(llfe_ctx *ctx, const llfe_image_desc *images, int32_t n,
                         llfe_image_result *results, llfe_shape *shapes, int64_t shape_capacity,
                         int64_t *shapes_needed, llfe_stream stream);
 
+/* llfe_process_images with flags; flags 0 is llfe_process_images itself, an unknown bit is
+ * LLFE_ERR_UNSUPPORTED (checked before every other argument).
+ * LLFE_IMAGES_COLORS_ONE_PASS: with LLFE_FEATURE_COLORS, the colours of all images of the call
+ * come from one device pass whatever their sizes -- one k_uq_scatter, one k_uq_part, one
+ * k_uq_gather and one k-means launch -- instead of one pass per size group.  A packed device
+ * image is read where it lies (any alignment); a host, strided or resized image is staged
+ * packed at a 16-byte aligned offset of one staging buffer.  The per-image arrays of the
+ * pass keep the strides of its largest image (llfe_colors_images_layout); a call that does not
+ * fit one workspace (LLFE_WORKSPACE_GB, at most 4096 images) is cut into consecutive passes.
+ * The other features of the call still run by size group, and every field of every result is
+ * bit for bit what flags 0 gives. */
+#define LLFE_IMAGES_COLORS_ONE_PASS 1u
+int llfe_process_images_flags(llfe_ctx *ctx, const llfe_image_desc *images, int32_t n, uint32_t features,
+                              int32_t preprocessing, int32_t n_colors, uint64_t seed, int64_t index_base,
+                              llfe_image_result *results, llfe_shape *shapes, int64_t shape_capacity,
+                              int64_t *shapes_needed, llfe_stream stream, uint32_t flags);
+
+/* The plan of the colour passes LLFE_IMAGES_COLORS_ONE_PASS runs (host only, no ctx). */
+typedef struct {
+    int64_t pixels;        /* P = height * width after preprocessing */
+    int64_t field_pixels;  /* the image's own noise-field length, P rounded up to 16 */
+    int64_t stage_offset;  /* byte offset in its pass's staging buffer (a multiple of 16); -1: read in place */
+    int32_t height, width; /* after preprocessing */
+    int32_t steps;         /* scatter steps of 4096 pixels */
+    int32_t pass;          /* the pass it belongs to */
+    int32_t resized;       /* the preprocessing rule resizes it */
+    int32_t pad_;
+} llfe_color_image;        /* 48 bytes */
+typedef struct {
+    int32_t image;              /* index in the call */
+    int32_t first_step, steps;  /* the scatter steps one workgroup takes (steps >= 1) */
+} llfe_color_work;              /* 12 bytes */
+typedef struct {
+    int32_t first, count;            /* images [first, first + count) of the call */
+    int32_t work_first, work_count;  /* its entries of the work table */
+    int32_t tab_steps;               /* steps of its largest image: the run-table row */
+    int32_t pad_;
+    int64_t max_pixels;              /* its largest image */
+    int64_t key_stride, cube_stride, cell_stride; /* the common per-image strides, from max_pixels */
+    int64_t stage_bytes;             /* its staging buffer */
+} llfe_color_pass;                   /* 64 bytes */
+/* images / work / passes may each be NULL (counts only: *n_work, *n_passes).  LLFE_ERR_INVALID
+ * for what llfe_process_images rejects (a bad descriptor, a bad preprocessing mode);
+ * LLFE_ERR_CAPACITY when work_capacity or pass_capacity is short (the counts are still set).
+ * Passes are consecutive runs of the input order: a pass grows while its image count stays
+ * within llfe_batch_capacity of its largest image. */
+int llfe_colors_images_layout(const llfe_image_desc *descs, int32_t n, int32_t preprocessing,
+                              llfe_color_image *images, llfe_color_work *work, int64_t work_capacity,
+                              int64_t *n_work, llfe_color_pass *passes, int32_t pass_capacity, int32_t *n_passes);
+
 /* Asynchronous form (serving loops): llfe_submit_batch enqueues the device work of one
  * batch (n <= one device pass) and returns a ticket; llfe_collect_batch (tickets in
  * submission order) waits for it, traces contours and fills results / shapes exactly as
@@ -357,6 +407,14 @@ int llfe_shadow_stats(llfe_ctx *ctx, const uint8_t *bgr, uint64_t *sums, uint64_
  * n x (h*w) u32 (R<<16|G<<8|B ascending, first n_unique[i] valid); n_unique host. */
 int llfe_color_unique(llfe_ctx *ctx, const llfe_batch *batch, uint64_t seed, uint32_t *keys, int64_t *n_unique,
                       llfe_stream stream);
+/* llfe_color_unique for n images that each have their own size, row stride and memory
+ * (descriptors as llfe_process_images, no preprocessing), through the colour passes of
+ * LLFE_IMAGES_COLORS_ONE_PASS.  Image i carries global index index_base + i.  keys: device
+ * n x key_stride u32, key_stride >= the largest pixel count; image i's keys start at
+ * keys + i * key_stride (first n_unique[i] valid); n_unique host. */
+int llfe_color_unique_images(llfe_ctx *ctx, const llfe_image_desc *images, int32_t n, uint64_t seed,
+                             int64_t index_base, uint32_t *keys, int64_t key_stride, int64_t *n_unique,
+                             llfe_stream stream);
 /* cv2.kmeans(float32(keys->RGB), K=min(n_colors,U), None, (EPS+MAX_ITER,200,0.2), 10,
  * KMEANS_PP_CENTERS) per image (color_extractor.py:189-197).  keys device
  * (n x key_stride), n_points host; results host (colour fields only). */

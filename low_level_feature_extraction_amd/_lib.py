@@ -97,6 +97,47 @@ class LlfeThumbOut(C.Structure):
     ]
 
 
+class LlfeColorImage(C.Structure):
+    _fields_ = [
+        ("pixels", C.c_int64),
+        ("field_pixels", C.c_int64),
+        ("stage_offset", C.c_int64),
+        ("height", C.c_int32),
+        ("width", C.c_int32),
+        ("steps", C.c_int32),
+        ("pass_", C.c_int32),  # `pass` in the header
+        ("resized", C.c_int32),
+        ("pad_", C.c_int32),
+    ]
+
+
+class LlfeColorWork(C.Structure):
+    _fields_ = [
+        ("image", C.c_int32),
+        ("first_step", C.c_int32),
+        ("steps", C.c_int32),
+    ]
+
+
+class LlfeColorPass(C.Structure):
+    _fields_ = [
+        ("first", C.c_int32),
+        ("count", C.c_int32),
+        ("work_first", C.c_int32),
+        ("work_count", C.c_int32),
+        ("tab_steps", C.c_int32),
+        ("pad_", C.c_int32),
+        ("max_pixels", C.c_int64),
+        ("key_stride", C.c_int64),
+        ("cube_stride", C.c_int64),
+        ("cell_stride", C.c_int64),
+        ("stage_bytes", C.c_int64),
+    ]
+
+
+IMAGES_COLORS_ONE_PASS = 1  # LLFE_IMAGES_COLORS_ONE_PASS
+
+
 class LlfeShape(C.Structure):
     _fields_ = [
         ("type", C.c_int32),
@@ -233,6 +274,11 @@ SIGNATURES = {
     "llfe_process_batch": (C.c_int, [_vp, C.POINTER(LlfeBatch), _u32, _u64, _vp, _vp, _i64, C.POINTER(C.c_int64), _vp]),
     "llfe_process_images": (C.c_int, [_vp, _vp, _i32, _u32, _i32, _i32, _u64, _i64, _vp, _vp, _i64,
                                       C.POINTER(C.c_int64), _vp]),
+    "llfe_process_images_flags": (C.c_int, [_vp, _vp, _i32, _u32, _i32, _i32, _u64, _i64, _vp, _vp, _i64,
+                                            C.POINTER(C.c_int64), _vp, _u32]),
+    "llfe_colors_images_layout": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _i64, C.POINTER(C.c_int64), _vp, _i32,
+                                            C.POINTER(C.c_int32)]),
+    "llfe_color_unique_images": (C.c_int, [_vp, _vp, _i32, _u64, _i64, _vp, _i64, _vp, _vp]),
     "llfe_gray_blur5": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "llfe_shape_mask": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "llfe_edge_classes": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp]),

@@ -176,6 +176,43 @@ def jpeg_images_tiling(sampling: int):
     return tw.value, th.value
 
 
+COLOR_ROUTES = {"grouped": 0, "one_pass": L.IMAGES_COLORS_ONE_PASS}
+
+
+def colors_flags(colors: str) -> int:
+    """The llfe_process_images_flags bits of process_images' ``colors`` option."""
+    try:
+        return COLOR_ROUTES[colors]
+    except (KeyError, TypeError):
+        raise ValueError(f"colors must be one of {sorted(COLOR_ROUTES)}, got {colors!r}") from None
+
+
+def colors_images_layout(images, preprocessing: str = "none", device: int = 0):
+    """The colour passes process_images(..., colors="one_pass") runs (llfe_colors_images_layout,
+    host only): -> (per-image records, work table, passes) as lists of dicts."""
+    descs, keep, _, _, _ = _image_descs(images, device)
+    n = len(keep)
+    mode = PRE_MODES.get(preprocessing, 0)
+    nw, npass = C.c_int64(0), C.c_int32(0)
+    lib = L.lib()
+    rc = lib.llfe_colors_images_layout(descs.ctypes.data, n, mode, None, None, 0, C.byref(nw), None, 0, C.byref(npass))
+    if rc < 0:
+        raise L.LlfeError(rc, "invalid image list")
+    recs = (L.LlfeColorImage * max(n, 1))()
+    work = (L.LlfeColorWork * max(nw.value, 1))()
+    passes = (L.LlfeColorPass * max(npass.value, 1))()
+    rc = lib.llfe_colors_images_layout(descs.ctypes.data, n, mode, recs, work, nw.value, C.byref(nw), passes,
+                                       npass.value, C.byref(npass))
+    if rc < 0:  # pragma: no cover
+        raise L.LlfeError(rc, "invalid image list")
+
+    def dicts(arr, m):
+        return [{f.rstrip("_") if f == "pass_" else f: int(getattr(r, f)) for f, _ in r._fields_ if f != "pad_"}
+                for r in arr[:m]]
+
+    return dicts(recs, n), dicts(work, nw.value), dicts(passes, npass.value)
+
+
 def thumbnail_images_layout(images, max_w=1920, max_h=1080, device: int = 0):
     """Where llfe_thumbnail_pil_images puts each result: -> (list of (offset, height, width,
     resized), bytes the packed destination must hold).  Host only."""
@@ -380,14 +417,19 @@ class Backend:
         return out
 
     def process_images(self, images, features=("colors", "shapes", "shadows"), seed: int = 0, noise=None,
-                       index_base: int = 0, n_colors: int = 5, preprocessing: str = "none") -> list:
+                       index_base: int = 0, n_colors: int = 5, preprocessing: str = "none",
+                       colors: str = "grouped") -> list:
         """Ragged batch through llfe_process_images: ``images`` is a list of H x W x 3 BGR
         uint8 images of any sizes -- numpy arrays (host) or torch tensors (host or GPU;
         rows may be strided, pixels must be packed) -- with validate_and_preprocess_image's
         resize rule (``preprocessing``: none / auto / high_quality / performance; other
         names do not resize, as in utils.py:116-143) applied on the GPU first.  Image i
         keeps global index index_base + i.  ``noise``: one parity-noise array per image of
-        its preprocessed size, or None.  Returns ImageFeatures in input order."""
+        its preprocessed size, or None.  ``colors``: "grouped" runs the colours with the size
+        groups; "one_pass" runs the colours of all images in one device pass whatever their
+        sizes (LLFE_IMAGES_COLORS_ONE_PASS), with the same results.  Returns ImageFeatures in
+        input order."""
+        flags = colors_flags(colors)
         n = len(images)
         mode = PRE_MODES.get(preprocessing, 0)
         descs, keep, hs, ws, first = _image_descs(images, self.device)
@@ -402,8 +444,9 @@ class Backend:
         mask = feature_mask(features)
         stream = self._stream(first)
         results, shapes, fonts = self._with_shapes(n, mask, L.LAST_CALL, lambda res, sh, cap, need: (
-            self._lib.llfe_process_images(self.ctx, descs.ctypes.data, n, mask, mode, int(n_colors),
-                                          C.c_uint64(seed & (2**64 - 1)), index_base, res, sh, cap, need, stream)))
+            self._lib.llfe_process_images_flags(self.ctx, descs.ctypes.data, n, mask, mode, int(n_colors),
+                                                C.c_uint64(seed & (2**64 - 1)), index_base, res, sh, cap, need, stream,
+                                                flags)))
         out = self._convert(results, shapes, n, mask, ws, hs, fonts)
         del keep
         return out
@@ -853,6 +896,28 @@ class Backend:
         self._call("llfe_color_unique", C.byref(b), C.c_uint64(seed), keys.data_ptr(),
                                               nu.ctypes.data, self._stream(x))
         return keys, nu
+
+    def color_unique_images(self, images, seed=0, noise=None, index_base=0) -> list:
+        """llfe_color_unique for a list of images of any sizes (as process_images takes them,
+        no preprocessing) in one colour pass: -> [(sorted unique keys np.uint32[n_unique],
+        n_unique)] in input order.  ``noise``: one parity-noise array per image, or None."""
+        torch = _torch()
+        n = len(images)
+        if n == 0:
+            return []
+        descs, keep, hs, ws, first = _image_descs(images, self.device)
+        if noise is not None:
+            nz = [self._noise_view(noise[i], 1, hs[i], ws[i]) for i in range(n)]
+            descs["noise"], descs["noise_on_device"] = [v[0] or 0 for v in nz], [v[1] for v in nz]
+            keep.append(nz)
+        stride = (max(h * w for h, w in zip(hs, ws)) + 3) & ~3
+        keys = torch.empty((n, stride), dtype=torch.int32, device=f"cuda:{self.device}")
+        nu = np.zeros(n, np.int64)
+        self._call("llfe_color_unique_images", descs.ctypes.data, n, C.c_uint64(seed & (2**64 - 1)), index_base,
+                   keys.data_ptr(), stride, nu.ctypes.data, self._stream(first))
+        host = keys.cpu().numpy().view(np.uint32)
+        del keep
+        return [(host[i, :nu[i]].copy(), int(nu[i])) for i in range(n)]
 
     def kmeans(self, keys, n_points, n_colors=5, seed=0, index_base=0):
         """keys: device int32 tensor (n, stride) of packed RGB keys; n_points np.int64[n]."""

@@ -5,6 +5,7 @@
 //   llfe_stages.cpp    the stage drop-ins
 //   llfe_resize.cpp    PIL / cv2 resize and the text binary
 //   llfe_decode.cpp    JPEG / PNG decode on the device
+//   llfe_colors_images.cpp  llfe_process_images and the colours of a mixed-size batch in one pass
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -353,6 +354,13 @@ struct llfe_ctx {
     llfe_host::DevBuf<uint8_t> d_rsz_tmp, d_rsz_src;
     llfe_host::DevBuf<uint8_t> d_ragged;       // llfe_process_images: one size group's packed images
     llfe_host::DevBuf<int8_t> d_ragged_noise;
+    // the one-pass colours of llfe_process_images_flags: the staged images and host noise of a
+    // pass (its own buffers: the size groups of the other features run beside it), then its
+    // records and its work table
+    llfe_host::DevBuf<uint8_t> d_color_stage;
+    llfe_host::DevBuf<int8_t> d_color_noise;
+    llfe_host::HostBuf<uint8_t> h_uq_tab;
+    llfe_host::DevBuf<uint8_t> d_uq_tab;
     llfe_host::DevBuf<int32_t> d_coef;
     // llfe_thumbnail_pil_images: the call's tables (pinned, then on the device) and the staging
     // workspace of one chunk of images
@@ -458,10 +466,16 @@ int run_contours(llfe_ctx *ctx, Work &W, int n, int h, int w, const uint64_t *bi
 int copy_contours(llfe_ctx *ctx, Work &W, int n, HostSlot &H, hipStream_t cs);
 void grow_contour_caps(Work &W, int n, int h, int w, const CtCounters &ct);
 int color_stage(llfe_ctx *ctx, Work &W, const uint8_t *img, const uint64_t *img_tab, const int8_t *noise, int n, int h,
-                int w, uint64_t seed, ImgIndex index, bool contiguous_keys, hipStream_t s);
+                int w, uint64_t seed, ImgIndex index, bool contiguous_keys, hipStream_t s,
+                const UqImages *ragged = nullptr);
 int kmeans_stage(llfe_ctx *ctx, Work &W, const uint32_t *keys, int64_t key_stride, const int64_t *d_nuniq, int n,
                  int n_colors, uint64_t seed, ImgIndex index, const KmeansCubes &cubes, hipStream_t s);
 void fill_palette(llfe_image_result &r);
 void fill_color_result(const KmeansImageOut &k, llfe_image_result &r);
+// llfe_process_images by size groups (llfe_colors_images.cpp holds the entry points)
+int process_images_grouped(llfe_ctx *ctx, const llfe_image_desc *images, int32_t n, uint32_t features,
+                           int32_t preprocessing, int32_t n_colors, uint64_t seed, int64_t index_base,
+                           llfe_image_result *results, llfe_shape *shapes, int64_t shape_capacity,
+                           int64_t *shapes_needed, llfe_stream stream);
 
 }  // namespace llfe_host

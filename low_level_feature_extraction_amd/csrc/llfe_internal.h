@@ -298,14 +298,37 @@ hipError_t launch_uq_noise(const int8_t *noise, int8_t *field, int64_t P, uint64
 // steps of 4096 pixels per image (k_uq_scatter's segments; its run table is n x steps x 64 u32)
 int64_t uq_steps(int64_t P);
 int64_t uq_tab_words(int64_t P);  // k_uq_scatter's run table, u32 words per image
+// The images of one colour pass when each has its own size (llfe_process_images_flags with
+// LLFE_IMAGES_COLORS_ONE_PASS, llfe_color_unique_images): one record per image and a work
+// table of (image, first step, step count) entries, both on the device.  Every per-image
+// array keeps the common strides of the pass's largest image; an image's run table row is
+// tab_steps steps long.
+struct UqImgRec {
+    const uint8_t *src;   // P packed BGR pixels (any alignment)
+    const int8_t *noise;  // the image's parity noise (P x 3, RGB order) or null
+    long long P, L;       // pixels; L = noise_field_pixels(P), the image's own field length
+    int32_t nsteps, pad_;  // uq_steps(P)
+};
+struct UqWork {
+    int32_t image, step0, nsteps;
+};
+struct UqImages {
+    const UqImgRec *recs;
+    const UqWork *work;
+    int n_work, tab_steps;  // tab_steps = uq_steps(the largest P)
+    int64_t pixels;         // sum of P (the profiler's bytes)
+};
 // img_tab (may be null): image i at img_tab[i] instead of bgr + i * h * w * 3
+// ragged (may be null): the images are ragged's records, h x w the largest of them (the noise
+// field was written for it), and `noise` only says whether the records carry parity noise
 hipError_t launch_uq_scatter(const uint8_t *bgr, const uint64_t *img_tab, const int8_t *noise, const int8_t *field,
                              int n, int h, int w,
                              uint64_t seed, ImgIndex index, int64_t key_stride, uint32_t *hist, uint32_t *tab,
-                             uint32_t *seg, hipStream_t s);
+                             uint32_t *seg, hipStream_t s, const UqImages *ragged = nullptr);
 hipError_t launch_uq_part(const uint32_t *seg, int n, int64_t key_stride, int64_t P, const uint32_t *hist,
                           const uint32_t *tab, uint32_t *skeys, CubeEnt *seg_cubes, CellEnt *seg_cells,
-                          uint32_t *uq, uint32_t *cc, uint32_t *cl, uint32_t *cs, hipStream_t s);
+                          uint32_t *uq, uint32_t *cc, uint32_t *cl, uint32_t *cs, hipStream_t s,
+                          const UqImages *ragged = nullptr);
 hipError_t launch_uq_gather(const uint32_t *skeys, int n, int64_t key_stride, const uint32_t *hist, const uint32_t *uq,
                             const uint32_t *cc, const uint32_t *cl, const uint32_t *cs, const CubeEnt *seg_cubes,
                             const CellEnt *seg_cells, uint32_t *keys, CubeEnt *cubes,

@@ -170,8 +170,11 @@ void grow_contour_caps(Work &W, int n, int h, int w, const CtCounters &ct) {
 // (llfe_color_unique's output, the general-K k-means); otherwise they stay where k_uq_part
 // wrote them (W.d_raw, partition R at the prefix of the partition pixel counts) and the cube
 // k-means reads them there (KmeansCubes::part_hist)
+// ragged (a pass of images of any sizes): h x w is its largest image, which sizes every
+// stride, the run table rows and the noise field; `noise` non-null says that the records
+// carry parity noise
 int color_stage(llfe_ctx *ctx, Work &W, const uint8_t *img, const uint64_t *img_tab, const int8_t *noise, int n, int h,
-                int w, uint64_t seed, ImgIndex index, bool contiguous_keys, hipStream_t s) {
+                int w, uint64_t seed, ImgIndex index, bool contiguous_keys, hipStream_t s, const UqImages *ragged) {
     // unique colours -> W.d_keys (sorted, key_stride) + cube table for k-means
     const int64_t P = (int64_t)h * w;
     const int64_t key_stride = (std::max<int64_t>(P, 1) + 3) & ~int64_t(3);
@@ -205,13 +208,13 @@ int color_stage(llfe_ctx *ctx, Work &W, const uint8_t *img, const uint64_t *img_
     // k_uq_gather the key read (4U); the step segments written and read back between the
     // scatter and k_uq_part (4P each way) are the implementation's, not counted.
     // keys -> per-step segments sorted by partition + run table + partition totals
-    TIMED(ctx, s, "k_uq_scatter", (double)n * P * (noise ? 6 : 3),
+    TIMED(ctx, s, "k_uq_scatter", (double)(ragged ? ragged->pixels : n * P) * (noise ? 6 : 3),
           launch_uq_scatter(img, img_tab, noise, W.d_nfield.p, n, h, w, seed, index, key_stride, hist, W.d_segtab.p,
-                            W.d_keys.p, s));
+                            W.d_keys.p, s, ragged));
     // the partitions' sorted unique keys go to the (free) d_raw
     TIMED(ctx, s, "k_uq_part", (double)n * 4194304.0,
           launch_uq_part(W.d_keys.p, n, key_stride, P, hist, W.d_segtab.p, W.d_raw.p, W.d_segcubes.p,
-                         W.d_segcells.p, uq, cc, cl, cs, s));
+                         W.d_segcells.p, uq, cc, cl, cs, s, ragged));
     TIMED(ctx, s, "k_uq_gather", 0,
           launch_uq_gather(W.d_raw.p, n, key_stride, hist, uq, cc, cl, cs, W.d_segcubes.p, W.d_segcells.p,
                            W.d_keys.p, W.d_cubes.p, W.d_cells.p, W.d_sups.p, cube_stride, cell_stride,
@@ -825,14 +828,17 @@ int llfe_process_batch(llfe_ctx *ctx, const llfe_batch *b, uint32_t features, ui
     return LLFE_OK;
 }
 
+}  // extern "C"
+
+// llfe_process_images (its entry points are in llfe_colors_images.cpp).
 // Ragged batch: images grouped by (preprocessed) size in input order; each group is
 // packed into a device buffer (2-D copies absorb row strides and host / device sources;
 // images the preprocessing rule resizes go through cv2.resize on the GPU) and runs as
 // ordinary batches that carry every image's own global index.
-int llfe_process_images(llfe_ctx *ctx, const llfe_image_desc *images, int32_t n, uint32_t features,
-                        int32_t preprocessing, int32_t n_colors, uint64_t seed, int64_t index_base,
-                        llfe_image_result *results, llfe_shape *shapes, int64_t shape_capacity,
-                        int64_t *shapes_needed, llfe_stream stream) {
+int llfe_host::process_images_grouped(llfe_ctx *ctx, const llfe_image_desc *images, int32_t n, uint32_t features,
+                                      int32_t preprocessing, int32_t n_colors, uint64_t seed, int64_t index_base,
+                                      llfe_image_result *results, llfe_shape *shapes, int64_t shape_capacity,
+                                      int64_t *shapes_needed, llfe_stream stream) {
     if (!ctx || n < 0 || (n > 0 && (!images || !results))) return LLFE_ERR_INVALID;
     if (preprocessing < LLFE_PRE_NONE || preprocessing > LLFE_PRE_PERFORMANCE)
         return ctx->fail(LLFE_ERR_INVALID, "preprocessing mode %d", preprocessing);
@@ -956,6 +962,8 @@ int llfe_process_images(llfe_ctx *ctx, const llfe_image_desc *images, int32_t n,
                          (long long)total_shapes);
     return LLFE_OK;
 }
+
+extern "C" {
 
 // Asynchronous form of llfe_process_batch: up to two batches in flight, each on its own
 // lane and host slot, so batch k + 1's unique-colour and stencil kernels start in

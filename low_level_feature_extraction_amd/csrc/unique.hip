@@ -17,6 +17,8 @@
 //                 mask + exact sums, CubeEnt)
 //   k_uq_gather   per image: prefix over the partitions, contiguous sorted keys + cube
 //                 table, and each partition's moments (count, colour sums, sum |p|^2)
+// k_uq_scatter and k_uq_part also have a ragged instantiation for a pass whose images each
+// have their own size (UqImages: per-image records and a work table, llfe_internal.h).
 #include <algorithm>
 
 #include "llfe_internal.h"
@@ -207,20 +209,42 @@ constexpr int SK = KB * PPT;  // keys per scatter block step
 // step's own 4096-key segment (coalesced, no global cursors), with the step's 64 (offset,
 // count) run entries in `tab` and the per-image partition totals in `hist`; k_uq_part reads
 // a partition as its runs over the steps.  (No separate histogram pass over the pixels.)
-template <bool kField>
+//
+// kRagged (the images of a pass each have their own size, UqImages): grid (n_work); a
+// workgroup takes one (image, first step, step count) entry of the work table and reads that
+// image's record -- its source, pixel count P_i, field length L_i (the rotation and the wrap
+// are the image's own, so its noise is what a launch of that image alone draws: the field of
+// the pass's largest image holds every shorter field as a prefix) or parity noise.  The
+// image's run table row is `tab_steps` (the pass's largest step count) steps long.
+template <bool kField, bool kRagged>
 __global__ __launch_bounds__(KB) void k_uq_scatter(const uint8_t *__restrict__ bgr, const uint64_t *__restrict__ img_tab,
                                                    NoiseSrc ns, long long P,
                                                    long long key_stride, ImgIndex index, uint32_t *__restrict__ hist,
-                                                   uint32_t *__restrict__ tab, uint32_t *__restrict__ seg) {
+                                                   uint32_t *__restrict__ tab, uint32_t *__restrict__ seg,
+                                                   const UqImgRec *__restrict__ recs,
+                                                   const UqWork *__restrict__ work, int tab_steps) {
     __shared__ uint32_t cnt[NPART], lbase[NPART], nlut[128];
     __shared__ __attribute__((aligned(16))) uint32_t stage[SK];
-    const int img = blockIdx.y, t = threadIdx.x;
+    const int img = kRagged ? work[blockIdx.x].image : blockIdx.y, t = threadIdx.x;
     if (kField && t < 128) nlut[t] = noise_lut_entry((uint32_t)t);  // (visible after the first barrier below)
     const uint8_t *src = img_tab ? (const uint8_t *)img_tab[img] : bgr + (size_t)img * P * 3;
+    int nimg = img;  // the image's place in the noise source
+    if (kRagged) {   // (block-uniform loads)
+        const UqImgRec rec = recs[img];
+        src = rec.src;
+        P = rec.P;
+        if (kField) ns.L = rec.L;
+        else ns.p = rec.noise;
+        nimg = 0;
+    }
     const long long off = field_offset(ns, index.at(img));
     uint32_t *out = seg + (size_t)img * key_stride;
     const long long nsteps = (P + SK - 1) / SK;
-    for (long long st = blockIdx.x; st < nsteps; st += gridDim.x) {
+    // the steps this workgroup takes, and the steps in a row of the run table
+    const long long st0 = kRagged ? work[blockIdx.x].step0 : blockIdx.x,
+                    st1 = kRagged ? st0 + work[blockIdx.x].nsteps : nsteps, stinc = kRagged ? 1 : gridDim.x,
+                    tabw = kRagged ? tab_steps : nsteps;
+    for (long long st = st0; st < st1; st += stinc) {
         const long long p0 = st * SK + (long long)t * PPT;
         const int n = (int)max(0LL, min((long long)PPT, P - p0));
         if (t < NPART) cnt[t] = 0;
@@ -229,7 +253,7 @@ __global__ __launch_bounds__(KB) void k_uq_scatter(const uint8_t *__restrict__ b
         // (the staging uses this wave's 3 KB of `stage`, free until the keys are sorted into it)
         const bool span = wave_span(src + p0 * 3, p0, P);
         if (n > 0)
-            chunk_keys<kField>(src + p0 * 3, noise_at<kField>(ns, img, P, off, p0), n, span,
+            chunk_keys<kField>(src + p0 * 3, noise_at<kField>(ns, nimg, P, off, p0), n, span,
                                (uint4 *)stage + 192 * (t >> 6), nlut, kv);
         // rank within the block's bin: one LDS atomic per run of equal bins.  Static
         // register indexing only: the atomic sits on each run's last key and returns the
@@ -266,7 +290,7 @@ __global__ __launch_bounds__(KB) void k_uq_scatter(const uint8_t *__restrict__ b
                 if (t >= off) x += y;
             }
             lbase[t] = x - c;
-            tab[((size_t)img * nsteps + st) * NPART + t] = (x - c) | (c << 16);
+            tab[((size_t)img * tabw + st) * NPART + t] = (x - c) | (c << 16);
             if (c) atomicAdd(hist + (size_t)img * NPART + t, c);
         }
         __syncthreads();
@@ -321,12 +345,16 @@ __device__ __forceinline__ unsigned long long scan_u64_wg(unsigned long long v, 
 // Reads the partition's keys as its runs in the step segments (`tab`), writes
 // the sorted unique keys to `skeys` at the partition's place in key order (capacity: its
 // hist count), and up to 4096 cube entries to `seg_cubes`.
+// kRagged: the image's step count comes from its record (one block-uniform load) and its run
+// table row is `tab_steps` steps long; P is unused.
+template <bool kRagged>
 __global__ __launch_bounds__(UT) __attribute__((amdgpu_waves_per_eu(8))) void k_uq_part(const uint32_t *__restrict__ seg, long long key_stride, long long P,
                                                 const uint32_t *__restrict__ hist, const uint32_t *__restrict__ tab,
                                                 uint32_t *__restrict__ skeys,
                                                 CubeEnt *__restrict__ seg_cubes, CellEnt *__restrict__ seg_cells,
                                                 uint32_t *__restrict__ uq, uint32_t *__restrict__ cc,
-                                                uint32_t *__restrict__ cl, uint32_t *__restrict__ cs) {
+                                                uint32_t *__restrict__ cl, uint32_t *__restrict__ cs,
+                                                const UqImgRec *__restrict__ recs, int tab_steps) {
     __shared__ __attribute__((aligned(16))) uint32_t W[4 * 2048];  // rows r = 4R + i, word g << 3 | b >> 5
     __shared__ unsigned long long tmp[UT / 64];
     __shared__ uint32_t sbase, scount;
@@ -358,8 +386,8 @@ __global__ __launch_bounds__(UT) __attribute__((amdgpu_waves_per_eu(8))) void k_
     // (flat "ui" partitions: ~4096 keys per run) with RG loads in flight.  (The first keys through
     // an LDS double buffer by direct-to-LDS loads cost occupancy and measured slower: DESIGN.md §3.)
     const uint32_t *sg = seg + (size_t)img * key_stride;
-    const long long nsteps = (P + SK - 1) / SK;
-    const uint32_t *tb = tab + (size_t)img * nsteps * NPART + R;
+    const long long nsteps = kRagged ? (long long)recs[img].nsteps : (P + SK - 1) / SK;
+    const uint32_t *tb = tab + (size_t)img * (kRagged ? (long long)tab_steps : nsteps) * NPART + R;
     const int lane = t & 63, wid = t >> 6;
     constexpr int RG = 8;  // runs (and tail loads) in flight per lane (16: 97 VGPRs, one workgroup per CU)
     auto mark = [&](uint32_t k) {
@@ -700,25 +728,42 @@ int64_t uq_steps(int64_t P) { return (P + SK - 1) / SK; }
 hipError_t launch_uq_scatter(const uint8_t *bgr, const uint64_t *img_tab, const int8_t *noise, const int8_t *field,
                              int n, int h, int w,
                              uint64_t seed, ImgIndex index, int64_t key_stride, uint32_t *hist, uint32_t *tab,
-                             uint32_t *seg, hipStream_t s) {
+                             uint32_t *seg, hipStream_t s, const UqImages *ragged) {
     const int64_t P = (int64_t)h * w;
     int bx = (int)std::min((P + SK * 2 - 1) / (SK * 2), (int64_t)2048);
     if (bx < 1) bx = 1;
     const NoiseSrc ns = noise_src(noise, (int8_t *)field, P, seed);
+    if (ragged) {  // (h x w: the pass's largest image; `noise` only says that the records carry parity noise)
+        if (ragged->n_work < 1) return hipSuccess;
+        if (ns.L)
+            hipLaunchKernelGGL((k_uq_scatter<true, true>), dim3(ragged->n_work), dim3(KB), 0, s, bgr, img_tab, ns,
+                               (long long)P, (long long)key_stride, index, hist, tab, seg, ragged->recs, ragged->work,
+                               ragged->tab_steps);
+        else
+            hipLaunchKernelGGL((k_uq_scatter<false, true>), dim3(ragged->n_work), dim3(KB), 0, s, bgr, img_tab, ns,
+                               (long long)P, (long long)key_stride, index, hist, tab, seg, ragged->recs, ragged->work,
+                               ragged->tab_steps);
+        return hipGetLastError();
+    }
     if (ns.L)
-        hipLaunchKernelGGL(k_uq_scatter<true>, dim3(bx, n), dim3(KB), 0, s, bgr, img_tab, ns, (long long)P, (long long)key_stride,
-                           index, hist, tab, seg);
+        hipLaunchKernelGGL((k_uq_scatter<true, false>), dim3(bx, n), dim3(KB), 0, s, bgr, img_tab, ns, (long long)P, (long long)key_stride,
+                           index, hist, tab, seg, nullptr, nullptr, 0);
     else
-        hipLaunchKernelGGL(k_uq_scatter<false>, dim3(bx, n), dim3(KB), 0, s, bgr, img_tab, ns, (long long)P,
-                           (long long)key_stride, index, hist, tab, seg);
+        hipLaunchKernelGGL((k_uq_scatter<false, false>), dim3(bx, n), dim3(KB), 0, s, bgr, img_tab, ns, (long long)P,
+                           (long long)key_stride, index, hist, tab, seg, nullptr, nullptr, 0);
     return hipGetLastError();
 }
 
 hipError_t launch_uq_part(const uint32_t *seg, int n, int64_t key_stride, int64_t P, const uint32_t *hist,
                           const uint32_t *tab, uint32_t *skeys, CubeEnt *seg_cubes, CellEnt *seg_cells,
-                          uint32_t *uq, uint32_t *cc, uint32_t *cl, uint32_t *cs, hipStream_t s) {
-    hipLaunchKernelGGL(k_uq_part, dim3(NPART, n), dim3(UT), 0, s, seg, (long long)key_stride, (long long)P, hist, tab,
-                       skeys, seg_cubes, seg_cells, uq, cc, cl, cs);
+                          uint32_t *uq, uint32_t *cc, uint32_t *cl, uint32_t *cs, hipStream_t s,
+                          const UqImages *ragged) {
+    if (ragged)
+        hipLaunchKernelGGL(k_uq_part<true>, dim3(NPART, n), dim3(UT), 0, s, seg, (long long)key_stride, (long long)P,
+                           hist, tab, skeys, seg_cubes, seg_cells, uq, cc, cl, cs, ragged->recs, ragged->tab_steps);
+    else
+        hipLaunchKernelGGL(k_uq_part<false>, dim3(NPART, n), dim3(UT), 0, s, seg, (long long)key_stride, (long long)P,
+                           hist, tab, skeys, seg_cubes, seg_cells, uq, cc, cl, cs, nullptr, 0);
     return hipGetLastError();
 }
 
