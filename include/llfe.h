@@ -278,6 +278,68 @@ int llfe_colors_images_layout(const llfe_image_desc *descs, int32_t n, int32_t p
                               llfe_color_image *images, llfe_color_work *work, int64_t work_capacity,
                               int64_t *n_work, llfe_color_pass *passes, int32_t pass_capacity, int32_t *n_passes);
 
+/* llfe_process_images_flags with a second flag word for the shapes / shadows route; an unknown
+ * bit in either word is LLFE_ERR_UNSUPPORTED (checked before every other argument).
+ * colors_flags: the flags of llfe_process_images_flags.
+ * LLFE_IMAGES_SHAPES_ONE_PASS (shapes_flags): with LLFE_FEATURE_SHAPES and / or
+ * LLFE_FEATURE_SHADOWS, the shapes and shadows of all images of the call come from one device
+ * pass whatever their sizes -- one stencil launch, one hysteresis + dilate sequence, one D2H of
+ * the packed masks and the shadow sums, one fan-out over the host contour pool -- instead of one
+ * of each per size group.  Images are read in place or staged as for the colour pass (an image
+ * both one-pass routes stage is staged twice).  A call that does not fit one workspace
+ * (llfe_shapes_images_layout) is cut into consecutive passes.  Fonts still run by size group.
+ * While the context traces contours on the GPU (llfe_set_contour_mode), a call that asks for
+ * shapes takes the size-grouped route for shapes and shadows.  Every field of every result is
+ * bit for bit what shapes_flags 0 gives. */
+#define LLFE_IMAGES_SHAPES_ONE_PASS 1u
+int llfe_process_images_routes(llfe_ctx *ctx, const llfe_image_desc *images, int32_t n, uint32_t features,
+                               int32_t preprocessing, int32_t n_colors, uint64_t seed, int64_t index_base,
+                               llfe_image_result *results, llfe_shape *shapes, int64_t shape_capacity,
+                               int64_t *shapes_needed, llfe_stream stream, uint32_t colors_flags,
+                               uint32_t shapes_flags);
+
+/* The plan of the passes LLFE_IMAGES_SHAPES_ONE_PASS runs (host only, no ctx). */
+typedef struct {
+    int64_t pixels;         /* height * width after preprocessing */
+    int64_t class_offset;   /* of its class map (one byte a pixel) in its pass's, a multiple of 16 */
+    int64_t word_offset;    /* of its height * ceil(width / 64) mask words in its pass's */
+    int64_t stage_offset;   /* byte offset in its pass's staging buffer (a multiple of 16); -1: read in place */
+    int32_t height, width;  /* after preprocessing */
+    int32_t strips, segs, seg_rows; /* the stencil's 240-column strips and row segments of seg_rows rows */
+    int32_t tiles_x, tiles_y;       /* 64 x 64 hysteresis tiles */
+    int32_t first_tile;     /* id of its tile (0, 0) among its pass's tiles */
+    int32_t first_part;     /* its first shadow partial = its first work entry within its pass */
+    int32_t pass;           /* the pass it belongs to */
+    int32_t resized;        /* the preprocessing rule resizes it */
+    int32_t pad_;
+} llfe_shape_image;         /* 80 bytes */
+typedef struct {
+    int32_t image;          /* index in the call */
+    int32_t strip, seg;     /* one stencil wave: columns [240 strip, +240), rows [seg_rows seg, +seg_rows) */
+} llfe_shape_work;          /* 12 bytes */
+typedef struct {
+    int32_t first, count;            /* images [first, first + count) of the call */
+    int32_t work_first, work_count;  /* its entries of the work table */
+    int32_t tiles;                   /* its hysteresis tiles (< 524288: the ids tile * 4096 + node are int) */
+    int32_t pad_;
+    int64_t class_bytes;             /* its class map (every image's rounded up to 16) */
+    int64_t words;                   /* its mask words */
+    int64_t first_word;              /* the words of the passes before it (llfe_shape_bits_images) */
+    int64_t stage_bytes;             /* its staging buffer */
+    int64_t workspace_bytes;         /* what the budget counts (below) */
+} llfe_shape_pass;                   /* 64 bytes */
+/* Same calling convention as llfe_colors_images_layout.  Passes are consecutive runs of the input
+ * order.  A pass grows while (a) workspace_bytes = 3 class_bytes (class map, u16 labels) + 29204
+ * tiles (per tile: 4096 x 7 bytes of union-find parents, root flags and root lists, 512 of promoted
+ * bits, 20 of counts, lists and flags) + 16 words (edge and mask words) + stage_bytes + 8
+ * work_count (shadow partials) stays within LLFE_WORKSPACE_GB (default 24) x 10^9 bytes -- the
+ * budget of llfe_batch_capacity -- and (b) it has fewer than 524288 tiles (every image has at
+ * least as many tiles as stencil waves, so the work table is bounded with them).  An image that
+ * alone exceeds (a) is a pass of its own. */
+int llfe_shapes_images_layout(const llfe_image_desc *descs, int32_t n, int32_t preprocessing,
+                              llfe_shape_image *images, llfe_shape_work *work, int64_t work_capacity,
+                              int64_t *n_work, llfe_shape_pass *passes, int32_t pass_capacity, int32_t *n_passes);
+
 /* Asynchronous form (serving loops): llfe_submit_batch enqueues the device work of one
  * batch (n <= one device pass) and returns a ticket; llfe_collect_batch (tickets in
  * submission order) waits for it, traces contours and fills results / shapes exactly as
@@ -307,7 +369,8 @@ int llfe_batch_capacity(int32_t h, int32_t w);
 
 /* ---- stage entry points (parity tests; device in/out unless noted) ------
  * The ones that use the context's workspace (llfe_shape_mask, llfe_canny,
- * llfe_hysteresis, llfe_shadow_stats, llfe_color_unique, llfe_kmeans, llfe_find_contours_gpu,
+ * llfe_hysteresis, llfe_shadow_stats, llfe_shape_bits_images, llfe_shadow_stats_images,
+ * llfe_hysteresis_images, llfe_color_unique, llfe_kmeans, llfe_find_contours_gpu,
  * llfe_shapes_from_masks_gpu, llfe_font_detect, llfe_font_bits) and llfe_process_images return LLFE_ERR_INVALID while a
  * batch submitted with llfe_submit_batch is not yet collected. */
 /* gray = cvtColor(BGR2GRAY); out = GaussianBlur(gray, (5,5), 0)
@@ -403,6 +466,26 @@ int llfe_text_size(int32_t h, int32_t w, int32_t *out_h, int32_t *out_w);
 /* sums[n], counts[n] host: adaptive-threshold shadow statistics (shadow pyc @L15-21) */
 int llfe_shadow_stats(llfe_ctx *ctx, const uint8_t *bgr, uint64_t *sums, uint64_t *counts, int32_t n, int32_t h,
                       int32_t w, llfe_stream stream);
+/* llfe_shape_mask for n images that each have their own size, row stride and memory (descriptors
+ * as llfe_process_images, no preprocessing), through the passes of LLFE_IMAGES_SHAPES_ONE_PASS.
+ * bits: HOST u64 words, bit x & 63 of word x >> 6 of a row is pixel x (set = 255 in
+ * llfe_shape_mask's mask); image i's height * ceil(width / 64) words begin at its pass's
+ * first_word + its word_offset (llfe_shapes_images_layout).  bits_capacity_words below the
+ * layout's total is LLFE_ERR_CAPACITY. */
+int llfe_shape_bits_images(llfe_ctx *ctx, const llfe_image_desc *descs, int32_t n, uint64_t *bits,
+                           int64_t bits_capacity_words, llfe_stream stream);
+/* llfe_shadow_stats for such a list: sums[n], counts[n] host */
+int llfe_shadow_stats_images(llfe_ctx *ctx, const llfe_image_desc *descs, int32_t n, uint64_t *sums,
+                             uint64_t *counts, llfe_stream stream);
+/* llfe_hysteresis for n class maps of any sizes in one ragged pass: class_maps[i] is a HOST
+ * heights[i] x widths[i] map of bytes 0 / 1 / 2 (any other byte is LLFE_ERR_INVALID, found before
+ * any launch).  bits_edges / bits_mask (either may be null, not both): HOST words as
+ * llfe_shape_bits_images lays them out for images of these sizes (the edges, and the edges
+ * dilated 3 x 3); bits_capacity_words as there.  tile_flags as llfe_hysteresis.  A list that does
+ * not fit one pass is LLFE_ERR_UNSUPPORTED. */
+int llfe_hysteresis_images(llfe_ctx *ctx, const uint8_t *const *class_maps, const int32_t *heights,
+                           const int32_t *widths, int32_t n, int32_t tile_flags, uint64_t *bits_edges,
+                           uint64_t *bits_mask, int64_t bits_capacity_words);
 /* noise + np.unique(axis=0) (color_extractor.py:220-225,177).  keys: device
  * n x (h*w) u32 (R<<16|G<<8|B ascending, first n_unique[i] valid); n_unique host. */
 int llfe_color_unique(llfe_ctx *ctx, const llfe_batch *batch, uint64_t seed, uint32_t *keys, int64_t *n_unique,

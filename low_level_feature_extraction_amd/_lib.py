@@ -138,6 +138,54 @@ class LlfeColorPass(C.Structure):
 IMAGES_COLORS_ONE_PASS = 1  # LLFE_IMAGES_COLORS_ONE_PASS
 
 
+class LlfeShapeImage(C.Structure):
+    _fields_ = [
+        ("pixels", C.c_int64),
+        ("class_offset", C.c_int64),
+        ("word_offset", C.c_int64),
+        ("stage_offset", C.c_int64),
+        ("height", C.c_int32),
+        ("width", C.c_int32),
+        ("strips", C.c_int32),
+        ("segs", C.c_int32),
+        ("seg_rows", C.c_int32),
+        ("tiles_x", C.c_int32),
+        ("tiles_y", C.c_int32),
+        ("first_tile", C.c_int32),
+        ("first_part", C.c_int32),
+        ("pass_", C.c_int32),  # `pass` in the header
+        ("resized", C.c_int32),
+        ("pad_", C.c_int32),
+    ]
+
+
+class LlfeShapeWork(C.Structure):
+    _fields_ = [
+        ("image", C.c_int32),
+        ("strip", C.c_int32),
+        ("seg", C.c_int32),
+    ]
+
+
+class LlfeShapePass(C.Structure):
+    _fields_ = [
+        ("first", C.c_int32),
+        ("count", C.c_int32),
+        ("work_first", C.c_int32),
+        ("work_count", C.c_int32),
+        ("tiles", C.c_int32),
+        ("pad_", C.c_int32),
+        ("class_bytes", C.c_int64),
+        ("words", C.c_int64),
+        ("first_word", C.c_int64),
+        ("stage_bytes", C.c_int64),
+        ("workspace_bytes", C.c_int64),
+    ]
+
+
+IMAGES_SHAPES_ONE_PASS = 1  # LLFE_IMAGES_SHAPES_ONE_PASS
+
+
 class LlfeShape(C.Structure):
     _fields_ = [
         ("type", C.c_int32),
@@ -278,6 +326,13 @@ SIGNATURES = {
                                             C.POINTER(C.c_int64), _vp, _u32]),
     "llfe_colors_images_layout": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _i64, C.POINTER(C.c_int64), _vp, _i32,
                                             C.POINTER(C.c_int32)]),
+    "llfe_process_images_routes": (C.c_int, [_vp, _vp, _i32, _u32, _i32, _i32, _u64, _i64, _vp, _vp, _i64,
+                                             C.POINTER(C.c_int64), _vp, _u32, _u32]),
+    "llfe_shapes_images_layout": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _i64, C.POINTER(C.c_int64), _vp, _i32,
+                                            C.POINTER(C.c_int32)]),
+    "llfe_shape_bits_images": (C.c_int, [_vp, _vp, _i32, _vp, _i64, _vp]),
+    "llfe_shadow_stats_images": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp]),
+    "llfe_hysteresis_images": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i64]),
     "llfe_color_unique_images": (C.c_int, [_vp, _vp, _i32, _u64, _i64, _vp, _i64, _vp, _vp]),
     "llfe_gray_blur5": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "llfe_shape_mask": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp]),

@@ -187,22 +187,31 @@ def colors_flags(colors: str) -> int:
         raise ValueError(f"colors must be one of {sorted(COLOR_ROUTES)}, got {colors!r}") from None
 
 
-def colors_images_layout(images, preprocessing: str = "none", device: int = 0):
-    """The colour passes process_images(..., colors="one_pass") runs (llfe_colors_images_layout,
-    host only): -> (per-image records, work table, passes) as lists of dicts."""
+SHAPE_ROUTES = {"grouped": 0, "one_pass": L.IMAGES_SHAPES_ONE_PASS}
+
+
+def shapes_flags(shapes: str) -> int:
+    """The shapes_flags word of llfe_process_images_routes for process_images' ``shapes`` option."""
+    try:
+        return SHAPE_ROUTES[shapes]
+    except (KeyError, TypeError):
+        raise ValueError(f"shapes must be one of {sorted(SHAPE_ROUTES)}, got {shapes!r}") from None
+
+
+def _images_layout(fn: str, types, images, preprocessing: str, device: int):
+    """(per-image records, work table, passes) of a host-only pass planner as lists of dicts."""
     descs, keep, _, _, _ = _image_descs(images, device)
     n = len(keep)
     mode = PRE_MODES.get(preprocessing, 0)
     nw, npass = C.c_int64(0), C.c_int32(0)
-    lib = L.lib()
-    rc = lib.llfe_colors_images_layout(descs.ctypes.data, n, mode, None, None, 0, C.byref(nw), None, 0, C.byref(npass))
+    plan = getattr(L.lib(), fn)
+    rc = plan(descs.ctypes.data, n, mode, None, None, 0, C.byref(nw), None, 0, C.byref(npass))
     if rc < 0:
         raise L.LlfeError(rc, "invalid image list")
-    recs = (L.LlfeColorImage * max(n, 1))()
-    work = (L.LlfeColorWork * max(nw.value, 1))()
-    passes = (L.LlfeColorPass * max(npass.value, 1))()
-    rc = lib.llfe_colors_images_layout(descs.ctypes.data, n, mode, recs, work, nw.value, C.byref(nw), passes,
-                                       npass.value, C.byref(npass))
+    recs = (types[0] * max(n, 1))()
+    work = (types[1] * max(nw.value, 1))()
+    passes = (types[2] * max(npass.value, 1))()
+    rc = plan(descs.ctypes.data, n, mode, recs, work, nw.value, C.byref(nw), passes, npass.value, C.byref(npass))
     if rc < 0:  # pragma: no cover
         raise L.LlfeError(rc, "invalid image list")
 
@@ -211,6 +220,20 @@ def colors_images_layout(images, preprocessing: str = "none", device: int = 0):
                 for r in arr[:m]]
 
     return dicts(recs, n), dicts(work, nw.value), dicts(passes, npass.value)
+
+
+def colors_images_layout(images, preprocessing: str = "none", device: int = 0):
+    """The colour passes process_images(..., colors="one_pass") runs (llfe_colors_images_layout,
+    host only): -> (per-image records, work table, passes) as lists of dicts."""
+    return _images_layout("llfe_colors_images_layout", (L.LlfeColorImage, L.LlfeColorWork, L.LlfeColorPass), images,
+                          preprocessing, device)
+
+
+def shapes_images_layout(images, preprocessing: str = "none", device: int = 0):
+    """The passes process_images(..., shapes="one_pass") runs (llfe_shapes_images_layout, host
+    only): -> (per-image records, work table, passes) as lists of dicts."""
+    return _images_layout("llfe_shapes_images_layout", (L.LlfeShapeImage, L.LlfeShapeWork, L.LlfeShapePass), images,
+                          preprocessing, device)
 
 
 def thumbnail_images_layout(images, max_w=1920, max_h=1080, device: int = 0):
@@ -418,7 +441,7 @@ class Backend:
 
     def process_images(self, images, features=("colors", "shapes", "shadows"), seed: int = 0, noise=None,
                        index_base: int = 0, n_colors: int = 5, preprocessing: str = "none",
-                       colors: str = "grouped") -> list:
+                       colors: str = "grouped", shapes: str = "grouped") -> list:
         """Ragged batch through llfe_process_images: ``images`` is a list of H x W x 3 BGR
         uint8 images of any sizes -- numpy arrays (host) or torch tensors (host or GPU;
         rows may be strided, pixels must be packed) -- with validate_and_preprocess_image's
@@ -427,9 +450,12 @@ class Backend:
         keeps global index index_base + i.  ``noise``: one parity-noise array per image of
         its preprocessed size, or None.  ``colors``: "grouped" runs the colours with the size
         groups; "one_pass" runs the colours of all images in one device pass whatever their
-        sizes (LLFE_IMAGES_COLORS_ONE_PASS), with the same results.  Returns ImageFeatures in
-        input order."""
-        flags = colors_flags(colors)
+        sizes (LLFE_IMAGES_COLORS_ONE_PASS), with the same results.  ``shapes``: the same choice
+        for shapes and shadows (LLFE_IMAGES_SHAPES_ONE_PASS: one stencil launch, one hysteresis,
+        one mask copy and one fan-out over the host contour pool for the whole list; fonts stay
+        grouped, and so do shapes and shadows while contours run on the GPU).  Returns
+        ImageFeatures in input order."""
+        flags, sflags = colors_flags(colors), shapes_flags(shapes)
         n = len(images)
         mode = PRE_MODES.get(preprocessing, 0)
         descs, keep, hs, ws, first = _image_descs(images, self.device)
@@ -444,9 +470,9 @@ class Backend:
         mask = feature_mask(features)
         stream = self._stream(first)
         results, shapes, fonts = self._with_shapes(n, mask, L.LAST_CALL, lambda res, sh, cap, need: (
-            self._lib.llfe_process_images_flags(self.ctx, descs.ctypes.data, n, mask, mode, int(n_colors),
-                                                C.c_uint64(seed & (2**64 - 1)), index_base, res, sh, cap, need, stream,
-                                                flags)))
+            self._lib.llfe_process_images_routes(self.ctx, descs.ctypes.data, n, mask, mode, int(n_colors),
+                                                 C.c_uint64(seed & (2**64 - 1)), index_base, res, sh, cap, need, stream,
+                                                 flags, sflags)))
         out = self._convert(results, shapes, n, mask, ws, hs, fonts)
         del keep
         return out
@@ -819,6 +845,66 @@ class Backend:
         self._call("llfe_hysteresis", c.ctypes.data, n, h, w, 1 if tile_flags else 0, edges.ctypes.data,
                    mask.ctypes.data)
         return edges, mask
+
+    @staticmethod
+    def _unpack_words(words, layout):
+        """Packed mask words at a shapes layout's offsets -> list of h x w u8 0 / 255 arrays."""
+        recs, _, passes = layout
+        out = []
+        for r in recs:
+            h, w = r["height"], r["width"]
+            wpr = (w + 63) // 64
+            first = passes[r["pass"]]["first_word"] + r["word_offset"]
+            rows = words[first:first + h * wpr].reshape(h, wpr)
+            bits = np.unpackbits(rows.view(np.uint8), axis=1, bitorder="little")[:, :w]
+            out.append(bits * np.uint8(255))
+        return out
+
+    def shape_masks_images(self, images) -> list:
+        """shape_mask for a list of images of any sizes (as process_images takes them, no
+        preprocessing) through the one-pass shapes route (llfe_shape_bits_images): -> list of
+        h x w u8 0 / 255 numpy arrays in input order."""
+        n = len(images)
+        if n == 0:
+            return []
+        descs, keep, _, _, first = _image_descs(images, self.device)
+        layout = shapes_images_layout(keep, device=self.device)
+        total = layout[2][-1]["first_word"] + layout[2][-1]["words"]
+        words = np.zeros(total, np.uint64)
+        self._call("llfe_shape_bits_images", descs.ctypes.data, n, words.ctypes.data, total, self._stream(first))
+        del keep
+        return self._unpack_words(words, layout)
+
+    def shadow_stats_images(self, images):
+        """shadow_stats for a list of images of any sizes through the one-pass route
+        (llfe_shadow_stats_images): -> (sums, counts) np.uint64[n]."""
+        n = len(images)
+        sums, cnts = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+        if n:
+            descs, keep, _, _, first = _image_descs(images, self.device)
+            self._call("llfe_shadow_stats_images", descs.ctypes.data, n, sums.ctypes.data, cnts.ctypes.data,
+                       self._stream(first))
+            del keep
+        return sums, cnts
+
+    def hysteresis_images(self, class_maps, tile_flags=True) -> list:
+        """hysteresis for a list of h x w host class maps of any sizes in one ragged pass
+        (llfe_hysteresis_images): -> list of (edges, mask) h x w 0 / 255 numpy arrays."""
+        maps = [np.ascontiguousarray(c, np.uint8) for c in class_maps]
+        n = len(maps)
+        if n == 0:
+            return []
+        if any(c.ndim != 2 for c in maps):
+            raise ValueError("class maps must be h x w")
+        layout = shapes_images_layout([np.zeros(c.shape + (3,), np.uint8) for c in maps], device=self.device)
+        total = layout[2][-1]["first_word"] + layout[2][-1]["words"]
+        ptrs = (C.c_void_p * n)(*[c.ctypes.data for c in maps])
+        hs = np.array([c.shape[0] for c in maps], np.int32)
+        ws = np.array([c.shape[1] for c in maps], np.int32)
+        edges, mask = np.zeros(total, np.uint64), np.zeros(total, np.uint64)
+        self._call("llfe_hysteresis_images", ptrs, hs.ctypes.data, ws.ctypes.data, n, 1 if tile_flags else 0,
+                   edges.ctypes.data, mask.ctypes.data, total)
+        return list(zip(self._unpack_words(edges, layout), self._unpack_words(mask, layout)))
 
     def dilate3(self, masks):
         """dilate(masks, ones(3, 3)) of an n x h x w (or h x w) u8 batch on the GPU."""

@@ -284,7 +284,7 @@ class ColorExtractor:
     @staticmethod
     def extract_colors_batch(images: List[np.ndarray], n_colors: int = 5, seed: Optional[int] = None,
                              noise=None, index_base: Optional[int] = None,
-                             colors: str = "grouped") -> List[ColorFeatures]:
+                             colors: str = "grouped", shapes: str = "grouped") -> List[ColorFeatures]:
         """Batched extract_colors for same-size BGR uint8 images (N x H x W x 3 array or a
         list).  Mixed sizes are grouped, or with ``colors="one_pass"`` share one device pass;
         ``noise`` (parity mode) is the per-image
@@ -292,5 +292,5 @@ class ColorExtractor:
         from .pipeline import run_batch
 
         res = run_batch(images, ("colors",), seed=seed, noise=noise, n_colors=n_colors, index_base=index_base,
-                        colors=colors)
+                        colors=colors, shapes=shapes)
         return [r["colors"] for r in res]

@@ -22,6 +22,14 @@
 //   k_ccl_edge    per listed tile (one wave): the runs with a promoted root OR-ed into the
 //                 edge words
 //   k_bits_dilate 3x3 dilate on the packed words (shifts and ORs)
+//
+// Two forms.  A uniform batch: n images of H x W one behind the other, tile tt = image *
+// tiles per image + tile.  A ragged pass (<true> instantiations, k_bits_dilate_images): every
+// image its own size; a global tile id maps to its image through a per-tile table, and the
+// image's record (ShapeImgRec) gives H, W, tiles per row, first tile and where its class map /
+// labels (pixels) and its mask words begin.  Everything indexed by tile id alone (parent,
+// sroot, roots, nroots, tstrong, the tile list) is the same in both, so k_tile_list,
+// k_ccl_flatten and k_ccl_strong serve both.
 #include <algorithm>
 
 #include "llfe_internal.h"
@@ -138,12 +146,47 @@ __device__ __forceinline__ int run_len(unsigned long long m, int a) {
     return z ? __builtin_ctzll(z) : 64 - a;
 }
 
+// The image of global tile tt.  RG = false: image tt / ntiles of a batch of H x W images; RG =
+// true: the pass's record of image timg[tt].  row / wd: where row y begins in the class map and
+// the labels, and where its word k lies in the mask words; tile: the global id of its tile t.
+// (the ragged kernels' one more argument, a trailing pack that is empty in the uniform
+// instantiations: those keep the argument list, and so the code, they always had)
+struct RaggedTab {
+    const ShapeImgRec *recs;
+    const int32_t *timg;
+};
+template <bool RG>
+struct ImgAt {
+    int H, W, ntx, ntiles, wpr, img, tile0;  // wpr: mask words per row
+    size_t pix, word;
+    __device__ __forceinline__ ImgAt(int tt, int H_, int W_, int ntx_, int ntiles_, int wpr_)
+        : H(H_), W(W_), ntx(ntx_), ntiles(ntiles_), wpr(wpr_), img(tt / ntiles_), tile0(0), pix(0), word(0) {
+        static_assert(!RG, "the ragged form takes the pass's tables");
+    }
+    __device__ __forceinline__ ImgAt(int tt, int, int, int, int, int, const RaggedTab &tab) {
+        static_assert(RG, "the uniform form takes no tables");
+        const ShapeImgRec &r = tab.recs[tab.timg[tt]];
+        H = r.H, W = r.W, ntx = r.ntx, tile0 = r.tile0, pix = (size_t)r.cls_off, word = (size_t)r.word_off;
+        wpr = (W + 63) >> 6, img = ntiles = 0;
+    }
+    __device__ __forceinline__ int local(int tt) const { return RG ? tt - tile0 : tt % ntiles; }
+    __device__ __forceinline__ size_t tile(int t) const { return RG ? (size_t)tile0 + t : (size_t)img * ntiles + t; }
+    __device__ __forceinline__ size_t row(int y) const {
+        return RG ? pix + (size_t)y * W : ((size_t)img * H + y) * W;
+    }
+    __device__ __forceinline__ size_t wd(int y, int k) const {
+        return RG ? word + (size_t)y * wpr + k : ((size_t)img * H + y) * wpr + k;
+    }
+};
+
 // the row's candidate (class != 1) and strong (class 2) masks; zero outside the image
-__device__ __forceinline__ void row_masks(const uint8_t *__restrict__ cls, int img, int H, int W, int tx0, int y,
+template <bool RG>
+__device__ __forceinline__ void row_masks(const uint8_t *__restrict__ cls, const ImgAt<RG> &g, int tx0, int y,
                                           unsigned long long &C, unsigned long long &S) {
+    const int H = g.H, W = g.W;
     C = S = 0;
     if (y >= H) return;
-    const uint8_t *row = cls + ((size_t)img * H + y) * W + tx0;
+    const uint8_t *row = cls + g.row(y) + tx0;
     const int nx = min(64, W - tx0);
     if (nx == 64 && (((uintptr_t)row) & 15) == 0) {
         uint32_t d[16];
@@ -178,17 +221,18 @@ __device__ __forceinline__ void row_masks(const uint8_t *__restrict__ cls, int i
 // reads.  Plus the edge words the tile decides alone (runs whose local root holds a strong
 // pixel).
 constexpr int kNodes = 64 * 32;
-__device__ __forceinline__ void ccl_runs_tile(const uint8_t *__restrict__ cls, int H, int W, int ntx, int ntiles,
-                                              int wpr, int tt, int lane, int nb, int *P, uint32_t *sflag, int *cnt,
+template <bool RG>
+__device__ __forceinline__ void ccl_runs_tile(const uint8_t *__restrict__ cls, const ImgAt<RG> &g, int tt, int lane,
+                                              int nb, int *P, uint32_t *sflag, int *cnt,
                                               uint16_t *__restrict__ lab, int *__restrict__ parent,
                                               uint8_t *__restrict__ sroot, uint16_t *__restrict__ roots,
                                               int *__restrict__ nroots, uint64_t *__restrict__ ebits) {
-    const int img = tt / ntiles, t = tt % ntiles;
+    const int t = g.local(tt), ntx = g.ntx;
     const int tx0 = (t % ntx) * TW, ty0 = (t / ntx) * TH, y = ty0 + lane;
     unsigned long long C, S;
-    row_masks(cls, img, H, W, tx0, y, C, S);
+    row_masks(cls, g, tx0, y, C, S);
     if (__ballot(C != 0) == 0) {  // (the tile list without the stencil's flags)
-        if (lane == 0) nroots[(size_t)img * ntiles + t] = 0;
+        if (lane == 0) nroots[g.tile(t)] = 0;
         return;
     }
     const unsigned long long starts = C & ~(C << 1);
@@ -228,8 +272,8 @@ __device__ __forceinline__ void ccl_runs_tile(const uint8_t *__restrict__ cls, i
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    const size_t gbase = ((size_t)img * ntiles + t) * TP;
-    uint16_t *const lrow = lab + ((size_t)img * H + y) * W + tx0;
+    const size_t gbase = g.tile(t) * TP;
+    uint16_t *const lrow = lab + g.row(y) + tx0;
     unsigned long long E = 0;
     j = 0;
     for (unsigned long long m = starts; m; m &= m - 1, j++) {
@@ -247,17 +291,19 @@ __device__ __forceinline__ void ccl_runs_tile(const uint8_t *__restrict__ cls, i
             roots[gbase + atomicAdd(cnt, 1)] = (uint16_t)id;
         }
     }
-    if (E) ebits[((size_t)img * H + y) * wpr + (tx0 >> 6)] = E;
+    if (E) ebits[g.wd(y, tx0 >> 6)] = E;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    if (lane == 0) nroots[(size_t)img * ntiles + t] = *cnt;
+    if (lane == 0) nroots[g.tile(t)] = *cnt;
 }
 
+template <bool RG, class... Tab>
 __global__ __launch_bounds__(64 * RW) void k_ccl_runs(const uint8_t *__restrict__ cls, int H, int W, int ntx, int nty,
                                                     uint16_t *__restrict__ lab, int *__restrict__ parent,
                                                     uint8_t *__restrict__ sroot, uint16_t *__restrict__ roots,
                                                     int *__restrict__ nroots, const int *__restrict__ ftlist,
-                                                    int *__restrict__ ftcount, uint64_t *__restrict__ ebits) {
+                                                    int *__restrict__ ftcount, uint64_t *__restrict__ ebits,
+                                                    Tab... tab) {
     __shared__ int Pall[RW][kNodes];
     __shared__ uint32_t sfl[RW][kNodes / 32];
     __shared__ int cntw[RW];
@@ -285,8 +331,11 @@ __global__ __launch_bounds__(64 * RW) void k_ccl_runs(const uint8_t *__restrict_
 #pragma unroll 1
         for (int q = wv; q < kGrab; q += RW) {
             const int it = base + q;
-            if (it < nft) ccl_runs_tile(cls, H, W, ntx, ntiles, wpr, ftlist[it], lane, nb, P, sflag, &cntw[wv], lab,
-                                        parent, sroot, roots, nroots, ebits);
+            if (it < nft) {
+                const int tt = ftlist[it];
+                ccl_runs_tile(cls, ImgAt<RG>(tt, H, W, ntx, ntiles, wpr, tab...), tt, lane, nb, P, sflag, &cntw[wv],
+                              lab, parent, sroot, roots, nroots, ebits);
+            }
         }
     }
 }
@@ -320,9 +369,10 @@ __global__ __launch_bounds__(LT) void k_tile_list(const uint8_t *__restrict__ tf
     if (f) ftlist[wbase[wid] + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = i;
 }
 
-__device__ __forceinline__ int gid_of(const uint16_t *lab, int img, int H, int W, int ntx, int ntiles, int y, int x) {
-    int t = (y / TH) * ntx + x / TW;
-    return (int)(((size_t)img * ntiles + t) * TP) + lab[((size_t)img * H + y) * W + x];
+template <bool RG>
+__device__ __forceinline__ int gid_of(const uint16_t *lab, const ImgAt<RG> &g, int y, int x) {
+    int t = (y / TH) * g.ntx + x / TW;
+    return (int)(g.tile(t) * TP) + lab[g.row(y) + x];
 }
 
 // The passes after k_ccl_runs visit only the listed tiles (those with a candidate; 15 % of
@@ -331,15 +381,22 @@ __device__ __forceinline__ int gid_of(const uint16_t *lab, int img, int H, int W
 // (round 5; 4096 before): border + flatten + edge 210 -> 183 us on the mix, 64k no better.
 constexpr int kListBlocks = 16384;
 
-// threads 0..31 the tile's right column (look east), 32..95 its bottom row (look south)
+// threads 0..31 the tile's right column (look east), 32..95 its bottom row (look south).  A
+// neighbour is a pixel of the same image or nothing: in the ragged form the bounds are the
+// tile's own image's H and W, so no union reaches the next image's bytes, which with the tight
+// layout lie right behind this one's.
+template <bool RG, class... Tab>
 __global__ __launch_bounds__(128) void k_ccl_border(const uint8_t *__restrict__ cls, const uint16_t *__restrict__ lab,
-                                                    int H, int W, int ntx, int nty, const int *__restrict__ tlist,
-                                                    const int *__restrict__ tcount, int *__restrict__ parent) {
-    const int tid = threadIdx.x, ntiles = ntx * nty, ntl = *tcount;
+                                                    int H_, int W_, int ntx_, int nty, const int *__restrict__ tlist,
+                                                    const int *__restrict__ tcount, int *__restrict__ parent,
+                                                    Tab... tab) {
+    const int tid = threadIdx.x, ntiles = ntx_ * nty, ntl = *tcount;
     for (int it = blockIdx.x; it < ntl; it += gridDim.x) {
-        const int tt = tlist[it], img = tt / ntiles, t = tt % ntiles;
+        const int tt = tlist[it];
+        const ImgAt<RG> g(tt, H_, W_, ntx_, ntiles, 0, tab...);
+        const int t = g.local(tt), H = g.H, W = g.W, ntx = g.ntx;
         const int tx0 = (t % ntx) * TW, ty0 = (t / ntx) * TH;
-        const uint8_t *c = cls + (size_t)img * H * W;
+        const uint8_t *c = cls + (RG ? g.pix : (size_t)g.img * H * W);
         int x, y;
         if (tid < TH) {
             x = tx0 + TW - 1;
@@ -351,7 +408,7 @@ __global__ __launch_bounds__(128) void k_ccl_border(const uint8_t *__restrict__ 
             continue;
         }
         if (x >= W || y >= H || c[(size_t)y * W + x] == 1) continue;
-        const int a = gid_of(lab, img, H, W, ntx, ntiles, y, x);
+        const int a = gid_of(lab, g, y, x);
         const int ty = y / TH, txi = x / TW;
         for (int dy = -1; dy <= 1; dy++)
             for (int dx = -1; dx <= 1; dx++) {
@@ -361,7 +418,7 @@ __global__ __launch_bounds__(128) void k_ccl_border(const uint8_t *__restrict__ 
                 if (yy / TH == ty && xx / TW == txi) continue;  // same tile: already merged locally
                 if (tid < TH ? dx != 1 : dy != 1) continue;     // right column looks east, bottom row south
                 if (c[(size_t)yy * W + xx] == 1) continue;
-                g_union(parent, a, gid_of(lab, img, H, W, ntx, ntiles, yy, xx));
+                g_union(parent, a, gid_of(lab, g, yy, xx));
             }
     }
 }
@@ -422,27 +479,72 @@ __global__ __launch_bounds__(64 * RW) void k_ccl_strong(const int *__restrict__ 
 
 // per listed tile with a promoted root (one wave, lane = row): the runs whose local root
 // (lab at the run's first pixel) is promoted OR-ed into the row words k_ccl_runs wrote
+template <bool RG, class... Tab>
 __global__ __launch_bounds__(64 * RW) void k_ccl_edge(const uint8_t *__restrict__ cls, const uint16_t *__restrict__ lab,
-                                                      int H, int W, int ntx, int nty, const int *__restrict__ tlist,
+                                                      int H, int W, int ntx_, int nty, const int *__restrict__ tlist,
                                                       const int *__restrict__ tcount, const int *__restrict__ pflag,
-                                                      const uint32_t *__restrict__ tstrong, uint64_t *__restrict__ ebits) {
+                                                      const uint32_t *__restrict__ tstrong, uint64_t *__restrict__ ebits,
+                                                      Tab... tab) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int ntiles = ntx * nty, ntl = *tcount, wpr = (W + 63) >> 6;
+    const int ntiles = ntx_ * nty, ntl = *tcount, wpr = (W + 63) >> 6;
     for (int it = blockIdx.x * RW + wv; it < ntl; it += gridDim.x * RW) {
         if (!pflag[it]) continue;  // (uniform)
-        const int tt = tlist[it], img = tt / ntiles, t = tt % ntiles;
+        const int tt = tlist[it];
+        const ImgAt<RG> g(tt, H, W, ntx_, ntiles, wpr, tab...);
+        const int t = g.local(tt), ntx = g.ntx;
         const int tx0 = (t % ntx) * TW, ty0 = (t / ntx) * TH, y = ty0 + lane;
         unsigned long long C, S;
-        row_masks(cls, img, H, W, tx0, y, C, S);
+        row_masks(cls, g, tx0, y, C, S);
         const uint32_t *rs = tstrong + (size_t)tt * (TP / 32);
-        const uint16_t *lrow = lab + ((size_t)img * H + y) * W + tx0;
+        const uint16_t *lrow = lab + g.row(y) + tx0;
         unsigned long long E = 0;
         for (unsigned long long m = C & ~(C << 1); m; m &= m - 1) {
             const int a = __builtin_ctzll(m), b = a + run_len(C, a) - 1;
             const uint32_t r = lrow[a] & (TP - 1);
             if ((rs[r >> 5] >> (r & 31)) & 1u) E |= bits_upto(b) & ~bits_upto(a - 1);
         }
-        if (E) ebits[((size_t)img * H + y) * wpr + (tx0 >> 6)] |= E;
+        if (E) ebits[g.wd(y, tx0 >> 6)] |= E;
+    }
+}
+
+// the dilated word k of row y of an H x W image; `row` is that row's index from eb in rows of
+// wpr words (a batch: image * H + y).  Rows outside the image never contribute.
+__device__ __forceinline__ uint64_t dilate_word(const uint64_t *eb, size_t row, int y, int k, int H, int W,
+                                                int wpr) {
+    uint64_t d = 0;
+#pragma unroll
+    for (int dy = -1; dy <= 1; dy++) {
+        if ((unsigned)(y + dy) >= (unsigned)H) continue;
+        const uint64_t *r = eb + (row + dy) * wpr;
+        const uint64_t w = r[k], wl = k > 0 ? r[k - 1] : 0ull, wr = k + 1 < wpr ? r[k + 1] : 0ull;
+        d |= w | (w << 1) | (w >> 1) | (wl >> 63) | (wr << 63);
+    }
+    if (k == wpr - 1 && (W & 63)) d &= (1ull << (W & 63)) - 1ull;
+    return d;
+}
+
+// Ragged form of k_bits_dilate's word pass: one thread per word of the pass.  The word's image is
+// found by a binary search over the records' word offsets rather than through a row table: a
+// table would be one more upload proportional to the pass's rows, while the records are
+// already on the device, stay in L2, and the 64 words of a wave nearly always fall in one or
+// two images, so each step of the search is a same-address load for most of the wave.  The last
+// word of a row is masked with its own image's W & 63, and the rows above and below are taken
+// only within the image: nothing of the next image's words, which follow tightly, gets in.
+__global__ __launch_bounds__(NT) void k_bits_dilate_images(const uint64_t *__restrict__ eb,
+                                                            const ShapeImgRec *__restrict__ recs, int n, size_t total,
+                                                            uint64_t *__restrict__ bits) {
+    for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < total; i += (size_t)gridDim.x * NT) {
+        int lo = 0, hi = n - 1;  // the last image whose words begin at or before i
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if ((size_t)recs[mid].word_off <= i) lo = mid;
+            else hi = mid - 1;
+        }
+        const ShapeImgRec &r = recs[lo];
+        const int wpr = (r.W + 63) >> 6;
+        const size_t j = i - (size_t)r.word_off;
+        const int k = (int)(j % wpr), y = (int)(j / wpr);
+        bits[i] = dilate_word(eb + r.word_off, (size_t)y, y, k, r.H, r.W, wpr);
     }
 }
 
@@ -455,15 +557,7 @@ __global__ __launch_bounds__(NT) void k_bits_dilate(const uint64_t *__restrict__
         const int k = (int)(i % wpr);
         const size_t row = i / wpr;  // img * H + y
         const int y = (int)(row % H);
-        uint64_t d = 0;
-#pragma unroll
-        for (int dy = -1; dy <= 1; dy++) {
-            if ((unsigned)(y + dy) >= (unsigned)H) continue;
-            const uint64_t *r = eb + (row + dy) * wpr;
-            const uint64_t w = r[k], wl = k > 0 ? r[k - 1] : 0ull, wr = k + 1 < wpr ? r[k + 1] : 0ull;
-            d |= w | (w << 1) | (w >> 1) | (wl >> 63) | (wr << 63);
-        }
-        if (k == wpr - 1 && (W & 63)) d &= (1ull << (W & 63)) - 1ull;
+        const uint64_t d = dilate_word(eb, row, y, k, H, W, wpr);
         if (bits) bits[i] = d;
         if (mask_u8) {
             uint8_t *m = mask_u8 + row * W + (size_t)k * 64;
@@ -510,37 +604,55 @@ __global__ __launch_bounds__(NT) void k_dilate3_u8(const uint8_t *__restrict__ s
     }
 }
 
-// the connected-component passes up to the packed edge words wk.ebits
-hipError_t launch_ccl(const uint8_t *cls, int n, int h, int w, const HystWork &wk, hipStream_t s) {
-    const int ntx = tiles_x(w), nty = htiles_y(h), ntiles = ntx * nty;
-    const size_t words = (size_t)n * h * words_per_row(w);
+// the connected-component passes over `total` tiles up to the `words` packed edge words wk.ebits
+// (RG: the ragged pass of the tables `tab`; else a batch of h x w images of ntx x nty tiles)
+template <bool RG, class... Tab>
+hipError_t launch_ccl_tiles(const uint8_t *cls, int h, int w, int ntx, int nty, int total, size_t words,
+                            const HystWork &wk, hipStream_t s, Tab... tab) {
     hipError_t e;
     if ((e = hipMemsetAsync(wk.ebits, 0, sizeof(uint64_t) * words, s)) != hipSuccess) return e;
-    const dim3 lgrid((unsigned)std::min<int64_t>((int64_t)ntiles * n, kListBlocks));
+    const dim3 lgrid((unsigned)std::min<int64_t>((int64_t)total, kListBlocks));
     // the tiles to label: the stencil's flagged ones, or every tile of the batch
     if ((e = hipMemsetAsync(wk.ftcount, 0, 2 * sizeof(int), s)) != hipSuccess) return e;
-    const int total = ntiles * n;
     hipLaunchKernelGGL(k_tile_list, dim3((unsigned)((total + LT - 1) / LT)), dim3(LT), 0, s, wk.tflag, total, wk.ftlist,
                        wk.ftcount);
     // (a work counter hands out the tiles, eight per workgroup; 1024 workgroups cover the
     // 4 x 256 resident ones)
     const dim3 rgrid((unsigned)std::min<int64_t>(((int64_t)total + RW - 1) / RW, 1024));
-    hipLaunchKernelGGL(k_ccl_runs, rgrid, dim3(64 * RW), 0, s, cls, h, w, ntx, nty, wk.lab, wk.parent, wk.sroot,
-                       wk.roots, wk.nroots, (const int *)wk.ftlist, wk.ftcount, wk.ebits);
+    hipLaunchKernelGGL((k_ccl_runs<RG, Tab...>), rgrid, dim3(64 * RW), 0, s, cls, h, w, ntx, nty, wk.lab, wk.parent,
+                       wk.sroot, wk.roots, wk.nroots, (const int *)wk.ftlist, wk.ftcount, wk.ebits, tab...);
     // the later passes visit the same listed tiles (with the stencil's flags exactly those
     // with a candidate; without them every tile, the empty ones with nroots = 0)
     const int *tl = wk.ftlist, *tc = wk.ftcount;
-    hipLaunchKernelGGL(k_ccl_border, lgrid, dim3(128), 0, s, cls, wk.lab, h, w, ntx, nty, tl, tc,
-                       wk.parent);
+    hipLaunchKernelGGL((k_ccl_border<RG, Tab...>), lgrid, dim3(128), 0, s, cls, (const uint16_t *)wk.lab, h, w, ntx, nty,
+                       tl, tc, wk.parent, tab...);
     hipLaunchKernelGGL(k_ccl_flatten, lgrid, dim3(NT), 0, s, tl, tc, wk.roots, wk.nroots, wk.parent,
                        wk.sroot);
     hipLaunchKernelGGL(k_ccl_strong, lgrid, dim3(64 * RW), 0, s, tl, tc, wk.roots, wk.nroots, wk.parent,
                        wk.sroot, wk.tstrong, wk.pflag);
-    hipLaunchKernelGGL(k_ccl_edge, lgrid, dim3(64 * RW), 0, s, cls, wk.lab, h, w, ntx, nty, tl, tc, (const int *)wk.pflag, wk.tstrong, wk.ebits);
+    hipLaunchKernelGGL((k_ccl_edge<RG, Tab...>), lgrid, dim3(64 * RW), 0, s, cls, (const uint16_t *)wk.lab, h, w, ntx, nty,
+                       tl, tc, (const int *)wk.pflag, (const uint32_t *)wk.tstrong, wk.ebits, tab...);
     return hipGetLastError();
 }
 
+hipError_t launch_ccl(const uint8_t *cls, int n, int h, int w, const HystWork &wk, hipStream_t s) {
+    const int ntx = tiles_x(w), nty = htiles_y(h);
+    return launch_ccl_tiles<false>(cls, h, w, ntx, nty, ntx * nty * n, (size_t)n * h * words_per_row(w), wk, s);
+}
+
 }  // namespace
+
+hipError_t launch_hysteresis_dilate_images(const uint8_t *cls, const ShapeImages &rg, const HystWork &wk,
+                                           uint64_t *bits, hipStream_t s) {
+    if (rg.n <= 0) return hipSuccess;
+    hipError_t e = launch_ccl_tiles<true>(cls, 0, 0, 0, 0, rg.tiles, (size_t)rg.words, wk, s,
+                                          RaggedTab{rg.recs, rg.tile_img});
+    if (e != hipSuccess) return e;
+    const int blocks = (int)std::min<size_t>(((size_t)rg.words + NT - 1) / NT, 65536);
+    hipLaunchKernelGGL(k_bits_dilate_images, dim3(blocks), dim3(NT), 0, s, (const uint64_t *)wk.ebits, rg.recs, rg.n,
+                       (size_t)rg.words, bits);
+    return hipGetLastError();
+}
 
 size_t hysteresis_ids(int n, int h, int w) { return (size_t)n * tiles_x(w) * htiles_y(h) * TP; }
 size_t hysteresis_tiles(int n, int h, int w) { return (size_t)n * tiles_x(w) * htiles_y(h); }

@@ -1,4 +1,4 @@
-// llfe_process_images[_flags] and the colours of a batch of images of any sizes in one
+// llfe_process_images[_flags, _routes] and the colours of a batch of images of any sizes in one
 // device pass (LLFE_IMAGES_COLORS_ONE_PASS, llfe_color_unique_images): the host planner, the
 // staging of the images that cannot be read where they lie, and the pass itself -- the ragged
 // k_uq_scatter / k_uq_part over per-image records and a work table (unique.hip), then the
@@ -220,15 +220,25 @@ int llfe_colors_images_layout(const llfe_image_desc *descs, int32_t n, int32_t p
     return LLFE_OK;
 }
 
-int llfe_process_images_flags(llfe_ctx *ctx, const llfe_image_desc *images, int32_t n, uint32_t features,
-                              int32_t preprocessing, int32_t n_colors, uint64_t seed, int64_t index_base,
-                              llfe_image_result *results, llfe_shape *shapes, int64_t shape_capacity,
-                              int64_t *shapes_needed, llfe_stream stream, uint32_t flags) {
-    if (flags & ~LLFE_IMAGES_COLORS_ONE_PASS) return LLFE_ERR_UNSUPPORTED;
-    const bool one_pass = (flags & LLFE_IMAGES_COLORS_ONE_PASS) && (features & LLFE_FEATURE_COLORS) && ctx && n > 0;
+int llfe_process_images_routes(llfe_ctx *ctx, const llfe_image_desc *images, int32_t n, uint32_t features,
+                               int32_t preprocessing, int32_t n_colors, uint64_t seed, int64_t index_base,
+                               llfe_image_result *results, llfe_shape *shapes, int64_t shape_capacity,
+                               int64_t *shapes_needed, llfe_stream stream, uint32_t colors_flags,
+                               uint32_t shapes_flags) {
+    if ((colors_flags & ~LLFE_IMAGES_COLORS_ONE_PASS) || (shapes_flags & ~LLFE_IMAGES_SHAPES_ONE_PASS))
+        return LLFE_ERR_UNSUPPORTED;
+    const bool one_pass =
+        (colors_flags & LLFE_IMAGES_COLORS_ONE_PASS) && (features & LLFE_FEATURE_COLORS) && ctx && n > 0;
+    // shapes and shadows in one pass: not while the context traces contours on the GPU
+    // (contours_gpu.hip takes images of one size) -- a call that asks for shapes then goes by
+    // size group, with the same results
+    const bool shapes_one_pass = (shapes_flags & LLFE_IMAGES_SHAPES_ONE_PASS) &&
+                                 (features & (LLFE_FEATURE_SHAPES | LLFE_FEATURE_SHADOWS)) && ctx && n > 0 &&
+                                 !(ctx->gpu_contours && (features & LLFE_FEATURE_SHAPES));
+    const auto others = shapes_one_pass ? process_images_shapes_one_pass : process_images_grouped;
     if (!one_pass)
-        return process_images_grouped(ctx, images, n, features, preprocessing, n_colors, seed, index_base, results, shapes,
-                                      shape_capacity, shapes_needed, stream);
+        return others(ctx, images, n, features, preprocessing, n_colors, seed, index_base, results, shapes,
+                      shape_capacity, shapes_needed, stream);
     // the grouped route's checks, before any work
     if (!images || !results) return LLFE_ERR_INVALID;
     if (n_colors < 0 || n_colors > kMaxColors)
@@ -245,10 +255,10 @@ int llfe_process_images_flags(llfe_ctx *ctx, const llfe_image_desc *images, int3
         if ((images[i].noise != nullptr) != (images[0].noise != nullptr))
             return ctx->fail(LLFE_ERR_INVALID, "parity noise must be given for every image or for none");
     // The first colour pass goes to the colour stream of lane 0, behind the caller's stream;
-    // shapes, shadows and fonts then run by size group beside it on the lanes' own streams
-    // (they share no buffer with it: the pass stages into buffers of its own) and fill every
-    // other field of the records; the colour fields follow, and the further passes of a call
-    // that does not fit one workspace.
+    // shapes, shadows and fonts then run beside it on the lanes' own streams -- by size group, or
+    // shapes and shadows in one pass of their own (`others`) -- (they share no buffer with it: the
+    // pass stages into buffers of its own) and fill every other field of the records; the colour
+    // fields follow, and the further passes of a call that does not fit one workspace.
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const int K = n_colors ? n_colors : kMaxK;
     llfe_stream cs = (llfe_stream)ctx->lanes[0].col_stream;
@@ -258,8 +268,8 @@ int llfe_process_images_flags(llfe_ctx *ctx, const llfe_image_desc *images, int3
     const uint32_t rest = features & ~(uint32_t)LLFE_FEATURE_COLORS;
     int rc_rest = LLFE_OK;
     if (rest) {
-        rc_rest = process_images_grouped(ctx, images, n, rest, preprocessing, n_colors, seed, index_base, results, shapes,
-                                         shape_capacity, shapes_needed, stream);
+        rc_rest = others(ctx, images, n, rest, preprocessing, n_colors, seed, index_base, results, shapes, shape_capacity,
+                         shapes_needed, stream);
         if (rc_rest && rc_rest != LLFE_ERR_CAPACITY) {  // (short capacity: the results are valid)
             (void)hipStreamSynchronize((hipStream_t)cs);
             return rc_rest;
@@ -282,6 +292,15 @@ int llfe_process_images_flags(llfe_ctx *ctx, const llfe_image_desc *images, int3
     }
     if (rc_rest) ctx->err = err_rest;
     return rc_rest;
+}
+
+int llfe_process_images_flags(llfe_ctx *ctx, const llfe_image_desc *images, int32_t n, uint32_t features,
+                              int32_t preprocessing, int32_t n_colors, uint64_t seed, int64_t index_base,
+                              llfe_image_result *results, llfe_shape *shapes, int64_t shape_capacity,
+                              int64_t *shapes_needed, llfe_stream stream, uint32_t flags) {
+    if (flags & ~LLFE_IMAGES_COLORS_ONE_PASS) return LLFE_ERR_UNSUPPORTED;
+    return llfe_process_images_routes(ctx, images, n, features, preprocessing, n_colors, seed, index_base, results, shapes,
+                                      shape_capacity, shapes_needed, stream, flags, 0);
 }
 
 int llfe_process_images(llfe_ctx *ctx, const llfe_image_desc *images, int32_t n, uint32_t features,

@@ -18,9 +18,14 @@ namespace llfe_host {
 // gathered cube / cell tables (<= 4 MiB + 1 MiB), held
 // within LLFE_WORKSPACE_GB (default 24 GB of the 288 GB of HBM) PER IN-FLIGHT SLOT: every
 // slot of llfe_set_inflight owns one such workspace, so depth 3 takes about 3x the budget.
-int chunk_for(int h, int w) {
+double workspace_gb() {
     double gb = 24.0;
     if (const char *e = getenv("LLFE_WORKSPACE_GB"); e && atof(e) > 0) gb = atof(e);
+    return gb;
+}
+
+int chunk_for(int h, int w) {
+    const double gb = workspace_gb();
     const double P = (double)h * (double)w;
     const double cubes = std::min(P, (double)kMaxCubes), cells = std::min(cubes, (double)kParts * kCellsPerPart);
     const double per_image = 16.0 * P +  // keys, segments, class map, labels, masks

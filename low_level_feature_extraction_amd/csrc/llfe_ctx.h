@@ -6,6 +6,7 @@
 //   llfe_resize.cpp    PIL / cv2 resize and the text binary
 //   llfe_decode.cpp    JPEG / PNG decode on the device
 //   llfe_colors_images.cpp  llfe_process_images and the colours of a mixed-size batch in one pass
+//   llfe_shapes_images.cpp  the shapes and shadows of a mixed-size batch in one pass
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -361,6 +362,11 @@ struct llfe_ctx {
     llfe_host::DevBuf<int8_t> d_color_noise;
     llfe_host::HostBuf<uint8_t> h_uq_tab;
     llfe_host::DevBuf<uint8_t> d_uq_tab;
+    // the one-pass shapes / shadows of llfe_process_images_routes: the staged images of a pass,
+    // then its records, work table and tile table
+    llfe_host::DevBuf<uint8_t> d_shape_stage;
+    llfe_host::HostBuf<uint8_t> h_shape_tab;
+    llfe_host::DevBuf<uint8_t> d_shape_tab;
     llfe_host::DevBuf<int32_t> d_coef;
     // llfe_thumbnail_pil_images: the call's tables (pinned, then on the device) and the staging
     // workspace of one chunk of images
@@ -452,6 +458,7 @@ namespace llfe_host {
 
 // llfe_context.cpp
 int chunk_for(int h, int w);  // images per device pass
+double workspace_gb();        // LLFE_WORKSPACE_GB (default 24): the budget chunk_for divides
 inline bool valid_dims(int n, int h, int w) { return n >= 0 && h > 0 && w > 0 && (int64_t)h * w < (1LL << 31); }
 
 // llfe_pipeline.cpp: the stage helpers, shared by the pipeline and the stage drop-ins
@@ -472,6 +479,21 @@ int kmeans_stage(llfe_ctx *ctx, Work &W, const uint32_t *keys, int64_t key_strid
                  int n_colors, uint64_t seed, ImgIndex index, const KmeansCubes &cubes, hipStream_t s);
 void fill_palette(llfe_image_result &r);
 void fill_color_result(const KmeansImageOut &k, llfe_image_result &r);
+// Shape records of n images from their bit-packed dilated masks (hb, host) on the context's
+// thread pool, into results[i0 ...] and the caller's shape array.  ragged (may be null): image i
+// is ragged[i].height x width with its words at hb + ragged[i].word_offset; else every image is
+// h x w, one behind the other.
+void host_shapes_from_bits(llfe_ctx *ctx, const uint64_t *hb, int n, int h, int w, int i0, llfe_image_result *results,
+                           llfe_shape *shapes, int64_t shape_capacity, int64_t &total_shapes,
+                           const llfe_shape_image *ragged = nullptr);
+int32_t shadow_level(uint64_t sum, uint64_t count);
+// llfe_shapes_images.cpp: shapes and shadows of all images in one pass (LLFE_IMAGES_SHAPES_ONE_PASS),
+// every other feature of `features` by size group afterwards; arguments and statuses as
+// process_images_grouped
+int process_images_shapes_one_pass(llfe_ctx *ctx, const llfe_image_desc *images, int32_t n, uint32_t features,
+                                   int32_t preprocessing, int32_t n_colors, uint64_t seed, int64_t index_base,
+                                   llfe_image_result *results, llfe_shape *shapes, int64_t shape_capacity,
+                                   int64_t *shapes_needed, llfe_stream stream);
 // llfe_process_images by size groups (llfe_colors_images.cpp holds the entry points)
 int process_images_grouped(llfe_ctx *ctx, const llfe_image_desc *images, int32_t n, uint32_t features,
                            int32_t preprocessing, int32_t n_colors, uint64_t seed, int64_t index_base,

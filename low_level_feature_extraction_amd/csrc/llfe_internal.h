@@ -49,6 +49,36 @@ hipError_t launch_stencil_stream(const uint8_t *bgr, int n, int h, int w, uint8_
                                  unsigned long long *shadow_sum, unsigned long long *shadow_cnt, uint2 *wave_part,
                                  const StencilParams &p, hipStream_t s);
 
+// The images of one shapes / shadows pass when each has its own size (llfe_process_images_routes
+// with LLFE_IMAGES_SHAPES_ONE_PASS): one record per image, a work table of one (image, strip,
+// segment) entry per stencil wave and the image of every 64 x 64 hysteresis tile, all on the
+// device.  Class maps (and the labels, at the same offsets) lie one behind the other, each at a
+// 16-byte aligned offset; mask words, tiles and shadow partials are tight.
+struct ShapeImgRec {
+    const uint8_t *src;   // H rows of 3 * W bytes, packed (any alignment)
+    long long cls_off;    // of its class map in the pass's (a multiple of 16)
+    long long word_off;   // of its H * ceil(W / 64) mask words in the pass's
+    int32_t H, W, strips, segs, seg_rows;  // stencil_stream_geometry(H, W)
+    int32_t vec;          // its source, its class map and 3 * W are 4-byte aligned: the dword paths
+    int32_t ntx, tile0;   // hysteresis tiles per tile row; global id of its first tile
+    int32_t part0, pad_;  // its first shadow partial (= its first work entry); strips * segs follow
+};
+static_assert(sizeof(ShapeImgRec) == 64, "ShapeImgRec is 64 bytes");
+struct ShapeWork {
+    int32_t image, strip, seg;
+};
+struct ShapeImages {
+    const ShapeImgRec *recs;
+    const ShapeWork *work;
+    const int32_t *tile_img;  // global tile id -> image
+    int n, n_work, tiles;
+    long long cls_bytes, words;  // the pass's class map and mask words
+};
+void stencil_stream_geometry(int h, int w, int *strips, int *segs, int *seg_rows);
+// tflag (may be null): a byte per global tile id, zeroed by the caller (StencilParams::tflag)
+hipError_t launch_stencil_images(const ShapeImages &rg, uint8_t *cls, unsigned long long *shadow_sum,
+                                 unsigned long long *shadow_cnt, uint2 *wave_part, uint8_t *tflag, hipStream_t s);
+
 // FontDetector.preprocess_image (font_detector.py:17-37): gray -> adaptiveThreshold(
 // GAUSSIAN_C, THRESH_BINARY_INV, 11, 2) -> n x h x w u8 255 / 0 (the stencil kernel
 // with the Gaussian mean taken over the gray image instead of the blurred one)
@@ -76,6 +106,11 @@ size_t hysteresis_tiles(int n, int h, int w);  // hysteresis tiles (<= n * tiles
 size_t hysteresis_tile_words();                // tstrong words per hysteresis tile
 hipError_t launch_hysteresis_dilate(const uint8_t *cls, int n, int h, int w, const HystWork &wk, uint64_t *bits,
                                     uint8_t *mask_u8, hipStream_t s);
+// the same for a ragged pass (wk sized by rg.tiles, rg.cls_bytes and rg.words; wk.tflag by global
+// tile id); bits: rg.words u64 at the records' word offsets (the words before the dilation stay in
+// wk.ebits, at the same offsets)
+hipError_t launch_hysteresis_dilate_images(const uint8_t *cls, const ShapeImages &rg, const HystWork &wk,
+                                           uint64_t *bits, hipStream_t s);
 // the same connected components without the dilation: Canny's 0 / 255 edges (llfe_canny)
 hipError_t launch_canny_edges(const uint8_t *cls, int n, int h, int w, const HystWork &wk, uint8_t *edges_u8,
                               hipStream_t s);

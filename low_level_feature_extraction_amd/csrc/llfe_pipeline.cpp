@@ -329,14 +329,14 @@ int chunk_index(llfe_ctx *ctx, Work &W, const llfe_batch *b, int i0, int n, hipS
 
 }  // namespace llfe_host
 
-namespace {
-
 // ShadowAnalyzer.analyze_shadow_level's decision (shadow pyc @L22-31): 0 Low, 1 Moderate, 2 High
-int32_t shadow_level(uint64_t sum, uint64_t count) {
+int32_t llfe_host::shadow_level(uint64_t sum, uint64_t count) {
     if (count == 0) return 0;
     const double avg_darkness = 255.0 - (double)sum / (double)count;
     return avg_darkness < 30 ? 0 : (avg_darkness < 60 ? 1 : 2);
 }
+
+namespace {
 
 // LLFE_FEATURE_FONTS after k_font_bits, on stream s: the boxes-only contour pass over
 // W.d_fbits, the region filter and largest region, its gray sum, then the D2H of the n
@@ -500,23 +500,33 @@ void emit_shapes(llfe_ctx *ctx, int n, int i0, llfe_image_result *results, llfe_
     }
 }
 
+}  // namespace
+
 // Shape records of n images from their bit-packed dilated masks (hb, host) on the
 // context's thread pool: external contours + the analyze_shapes loop (contours.cpp).
-void host_shapes_from_bits(llfe_ctx *ctx, const uint64_t *hb, int n, int h, int w, int i0,
-                           llfe_image_result *results, llfe_shape *shapes, int64_t shape_capacity,
-                           int64_t &total_shapes) {
+void llfe_host::host_shapes_from_bits(llfe_ctx *ctx, const uint64_t *hb, int n, int h, int w, int i0,
+                                      llfe_image_result *results, llfe_shape *shapes, int64_t shape_capacity,
+                                      int64_t &total_shapes, const llfe_shape_image *ragged) {
     const int wpr = words_per_row(w);
     ctx->img_shapes.resize(n);
     ctx->img_ncont.assign(n, 0);
     const auto t0 = std::chrono::steady_clock::now();
     ctx->pool->parallel_for(n, [&](int i, int wid) {
-        external_contours_bits(hb + (size_t)i * h * wpr, h, w, wpr, ctx->work[wid], ctx->cont[wid]);
+        if (ragged) {
+            const llfe_shape_image &q = ragged[i];
+            external_contours_bits(hb + q.word_offset, q.height, q.width, words_per_row(q.width), ctx->work[wid],
+                                   ctx->cont[wid]);
+        } else {
+            external_contours_bits(hb + (size_t)i * h * wpr, h, w, wpr, ctx->work[wid], ctx->cont[wid]);
+        }
         ctx->img_ncont[i] = shapes_from_contours(ctx->cont[wid], ctx->shs[wid], ctx->img_shapes[i]);
     });
     ctx->host_ct_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     ctx->host_ct_images += n;
     emit_shapes(ctx, n, i0, results, shapes, shape_capacity, total_shapes);
 }
+
+namespace {
 
 // A redo of part of a chunk runs synchronously on lane L (lane 0): the device is idle after
 // the hipDeviceSynchronize, and the input, staged again without its noise, is still the caller's.

@@ -317,20 +317,57 @@ __device__ __forceinline__ void rowpass4(uint32_t B, const float *__restrict__ k
 #ifndef LLFE_ST_STORE_AUX
 #define LLFE_ST_STORE_AUX 2  // the class-map stores' cache policy (2: non-temporal)
 #endif
-// One wave's work item: strip x segment of one image.  `wid` is wave-uniform (an SGPR):
-// every per-wave quantity below -- strip, segment, row bounds, border flags -- then stays
-// scalar and its branches cost no exec masking.
-template <bool CLS, bool SHD>
-__device__ __forceinline__ void stencil_wave(int wid, const uint8_t *__restrict__ bgr, int H, int W, int strips,
-                                             int segs, int seg_rows, int vec, uint8_t *__restrict__ cls,
-                                             uint2 *__restrict__ wave_part, const StencilParams &prm) {
+// What one stencil wave works on: a strip x segment of one H x W image, the image's pixels, class
+// map and tile flags, and the wave's shadow partial.  Every member is wave-uniform (an SGPR).
+// StBatchItem: wave `wid` of a batch of equal images, everything derived from wid as the kernel
+// always did (the accessors hold the expressions where stencil_wave had them, so
+// k_stencil_stream compiles to what it was).
+struct StBatchItem {
+    int wid;
+    const uint8_t *__restrict__ bgr;
+    int H, W, strips, segs, seg_rows, vec;
+    uint8_t *__restrict__ cls;
+    uint2 *__restrict__ wave_part;
+    const StencilParams &prm;
+    __device__ __forceinline__ int strip() const { return wid % strips; }
+    __device__ __forceinline__ int seg() const { return (wid / strips) % segs; }
+    __device__ __forceinline__ int img_i() const { return (wid / strips) / segs; }
+    __device__ __forceinline__ const uint8_t *img() const {
+        return prm.img_tab ? (const uint8_t *)prm.img_tab[img_i()] : bgr + (size_t)img_i() * H * W * 3;
+    }
+    __device__ __forceinline__ uint8_t *cimg() const { return cls + (size_t)img_i() * H * W; }
+    __device__ __forceinline__ uint8_t *tflags(int nty, int ntx) const {  // of the image's tile (0, 0)
+        return prm.tflag ? prm.tflag + (size_t)img_i() * nty * ntx : nullptr;
+    }
+    __device__ __forceinline__ uint2 *part() const { return wave_part + wid; }
+};
+// StRecItem: an entry of a ragged pass's work table, everything read from the entry and the
+// image's record (ShapeImgRec); tile flags by global tile id, the partial at the entry's index.
+struct StRecItem {
+    const uint8_t *__restrict__ src;
+    uint8_t *__restrict__ cmap;
+    uint8_t *tf0;
+    uint2 *__restrict__ wpart;
+    int H, W, seg_rows, vec, strip_, seg_;
+    __device__ __forceinline__ int strip() const { return strip_; }
+    __device__ __forceinline__ int seg() const { return seg_; }
+    __device__ __forceinline__ const uint8_t *img() const { return src; }
+    __device__ __forceinline__ uint8_t *cimg() const { return cmap; }
+    __device__ __forceinline__ uint8_t *tflags(int, int) const { return tf0; }
+    __device__ __forceinline__ uint2 *part() const { return wpart; }
+};
+
+// One wave's work item `it` (above).  Its values are wave-uniform, so every per-wave quantity
+// below -- strip, segment, row bounds, border flags -- stays scalar and its branches cost no exec
+// masking.
+template <bool CLS, bool SHD, class Item>
+__device__ __forceinline__ void stencil_wave(const Item &it) {
+    const int H = it.H, W = it.W, seg_rows = it.seg_rows, vec = it.vec;
     const int lane = threadIdx.x & 63;
-    const int strip = wid % strips;
-    const int rest = wid / strips;
-    const int seg = rest % segs;
-    const int img_i = rest / segs;
-    const uint8_t *img = prm.img_tab ? (const uint8_t *)prm.img_tab[img_i] : bgr + (size_t)img_i * H * W * 3;
-    uint8_t *cimg = CLS ? cls + (size_t)img_i * H * W : nullptr;
+    const int strip = it.strip();
+    const int seg = it.seg();
+    const uint8_t *img = it.img();
+    uint8_t *cimg = CLS ? it.cimg() : nullptr;
     // the image's class map as a buffer (H * W < 2^31 bytes: valid_dims)
     const __amdgpu_buffer_rsrc_t crs = __builtin_amdgcn_make_buffer_rsrc(cimg, (short)0, CLS ? H * W : 0, 0x00020000);
     const int ya = seg * seg_rows, yb = min(H, ya + seg_rows);
@@ -446,7 +483,7 @@ __device__ __forceinline__ void stencil_wave(int wid, const uint8_t *__restrict_
     // storing once per 64-row band: the per-row stores cost the stencil nothing, the band
     // flushes +90 us per 512 x 1080p through their register pressure)
     const int tf_ntx = (W + 63) >> 6;
-    uint8_t *const tf_img = CLS && prm.tflag ? prm.tflag + (size_t)img_i * ((H + 63) >> 6) * tf_ntx : nullptr;
+    uint8_t *const tf_img = CLS ? it.tflags((H + 63) >> 6, tf_ntx) : nullptr;
 
     for (int tb = tb0; tb < t_end; tb += kU) {
 #pragma unroll
@@ -648,7 +685,7 @@ __device__ __forceinline__ void stencil_wave(int wid, const uint8_t *__restrict_
             lsum += __shfl_xor(lsum, off);
             lcnt += __shfl_xor(lcnt, off);
         }
-        if (lane == 0) wave_part[wid] = make_uint2(lsum, lcnt);
+        if (lane == 0) *it.part() = make_uint2(lsum, lcnt);
     }
 }
 
@@ -672,18 +709,40 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, LLFE_ST_MINW) void k_stencil_s
         }
     }
 #endif
-    stencil_wave<CLS, SHD>(wid, bgr, H, W, strips, segs, seg_rows, vec, cls, wave_part, prm);
+    stencil_wave<CLS, SHD>(StBatchItem{wid, bgr, H, W, strips, segs, seg_rows, vec, cls, wave_part, prm});
 }
 
-// per image: sum of its waves' (sum, count)
+// ragged form: wave i of the grid runs entry i of the work table, an (image, strip, segment) of
+// a pass whose images each have their own size; the entry and the image's record are read with
+// block-uniform (scalar) loads.  One launch mixes images on the dword paths (vec) and on the
+// byte paths.  Tile flags go by global tile id (the record's first tile), the wave's shadow
+// partial to wave_part[entry].
+template <bool CLS, bool SHD>
+__global__ __launch_bounds__(64 * kWavesPerBlock, LLFE_ST_MINW) void k_stencil_images(
+    const ShapeImgRec *__restrict__ recs, const ShapeWork *__restrict__ work, int n_work, uint8_t *__restrict__ cls,
+    uint2 *__restrict__ wave_part, uint8_t *__restrict__ tflag) {
+    const int wid = blockIdx.x * kWavesPerBlock + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (wid >= n_work) return;  // (the last workgroup's spare waves)
+    const ShapeWork e = work[wid];
+    const ShapeImgRec &r = recs[__builtin_amdgcn_readfirstlane(e.image)];
+    const int strip = __builtin_amdgcn_readfirstlane(e.strip), seg = __builtin_amdgcn_readfirstlane(e.seg);
+    stencil_wave<CLS, SHD>(StRecItem{r.src, CLS ? cls + r.cls_off : nullptr, CLS && tflag ? tflag + r.tile0 : nullptr,
+                                     wave_part + wid, r.H, r.W, r.seg_rows, r.vec, strip, seg});
+}
+
+// per image: sum of its waves' (sum, count).  RG (the ragged form): image i's own run of partials,
+// first and count from its record (u64 sums: any order gives the same totals).
+template <bool RG>
 __global__ __launch_bounds__(256) void k_stream_shadow_reduce(const uint2 *__restrict__ part, int per_img,
                                                               unsigned long long *__restrict__ shadow_sum,
-                                                              unsigned long long *__restrict__ shadow_cnt) {
+                                                              unsigned long long *__restrict__ shadow_cnt,
+                                                              const ShapeImgRec *__restrict__ recs) {
     __shared__ unsigned long long rs[4], rc[4];
     const int img = blockIdx.x, tid = threadIdx.x;
+    if constexpr (RG) per_img = recs[img].strips * recs[img].segs;
     unsigned long long a = 0, b = 0;
     for (int t = tid; t < per_img; t += 256) {
-        const uint2 v = part[(size_t)img * per_img + t];
+        const uint2 v = part[(RG ? (size_t)recs[img].part0 : (size_t)img * per_img) + t];
         a += v.x;
         b += v.y;
     }
@@ -745,8 +804,32 @@ hipError_t launch_stencil_stream(const uint8_t *bgr, int n, int h, int w, uint8_
         hipLaunchKernelGGL((k_stencil_stream<false, true>), dim3(blocks), dim3(64 * kWavesPerBlock), 0, s, bgr, h,
                            w, strips, segs, seg_rows, (int)waves, vec, cls, wave_part, p);
     if (shd)
-        hipLaunchKernelGGL(k_stream_shadow_reduce, dim3(n), dim3(256), 0, s, wave_part, strips * segs, shadow_sum,
-                           shadow_cnt);
+        hipLaunchKernelGGL(k_stream_shadow_reduce<false>, dim3(n), dim3(256), 0, s, (const uint2 *)wave_part,
+                           strips * segs, shadow_sum, shadow_cnt, (const ShapeImgRec *)nullptr);
+    return hipGetLastError();
+}
+
+void stencil_stream_geometry(int h, int w, int *strips, int *segs, int *seg_rows) {
+    stream_geometry(h, w, *strips, *segs, *seg_rows);
+}
+
+hipError_t launch_stencil_images(const ShapeImages &rg, uint8_t *cls, unsigned long long *shadow_sum,
+                                 unsigned long long *shadow_cnt, uint2 *wave_part, uint8_t *tflag, hipStream_t s) {
+    if (rg.n <= 0 || rg.n_work <= 0) return hipSuccess;
+    const bool shd = shadow_sum != nullptr;
+    const dim3 grid((unsigned)((rg.n_work + kWavesPerBlock - 1) / kWavesPerBlock)), block(64 * kWavesPerBlock);
+    if (cls && shd)
+        hipLaunchKernelGGL((k_stencil_images<true, true>), grid, block, 0, s, rg.recs, rg.work, rg.n_work, cls,
+                           wave_part, tflag);
+    else if (cls)
+        hipLaunchKernelGGL((k_stencil_images<true, false>), grid, block, 0, s, rg.recs, rg.work, rg.n_work, cls,
+                           wave_part, tflag);
+    else if (shd)
+        hipLaunchKernelGGL((k_stencil_images<false, true>), grid, block, 0, s, rg.recs, rg.work, rg.n_work, cls,
+                           wave_part, tflag);
+    if (shd)
+        hipLaunchKernelGGL(k_stream_shadow_reduce<true>, dim3(rg.n), dim3(256), 0, s, (const uint2 *)wave_part, 0,
+                           shadow_sum, shadow_cnt, rg.recs);
     return hipGetLastError();
 }
 

@@ -29,7 +29,8 @@ class ShadowAnalyzer:
         return run_batch([_bgr(image)], ("shadows",))[0]["shadows"]["shadow_level"]
 
     @staticmethod
-    def analyze_shadow_level_batch(images) -> List[str]:
+    def analyze_shadow_level_batch(images, shapes: str = "grouped") -> List[str]:
+        """``shapes="one_pass"``: a list of images of any sizes in one device pass (run_batch)."""
         from .pipeline import run_batch
 
-        return [r["shadows"]["shadow_level"] for r in run_batch(images, ("shadows",))]
+        return [r["shadows"]["shadow_level"] for r in run_batch(images, ("shadows",), shapes=shapes)]

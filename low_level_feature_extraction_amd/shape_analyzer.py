@@ -49,7 +49,8 @@ class ShapeAnalyzer:
         return run_batch([_bgr(image)], ("shapes",))[0]["shapes"]
 
     @staticmethod
-    def analyze_shapes_batch(images) -> List[Dict[str, Any]]:
+    def analyze_shapes_batch(images, shapes: str = "grouped") -> List[Dict[str, Any]]:
+        """``shapes="one_pass"``: a list of images of any sizes in one device pass (run_batch)."""
         from .pipeline import run_batch
 
-        return [r["shapes"] for r in run_batch(images, ("shapes",))]
+        return [r["shapes"] for r in run_batch(images, ("shapes",), shapes=shapes)]
