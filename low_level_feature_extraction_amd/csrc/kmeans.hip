@@ -41,6 +41,8 @@
 #include <mutex>
 #include <type_traits>
 
+#include "kmeans_lattice.h"
+
 namespace llfe {
 namespace {
 
@@ -170,6 +172,14 @@ constexpr int SEL_U = 4;
                              // Both give the same sums
 #endif
 constexpr bool kSplitOn = LLFE_KM_SPLIT_MIN <= 64;
+// The split reads each cube's sign masks from a table per centre pair (kmeans_lattice.h) instead of walking its 64
+// positions.  The four-wave build has the LDS for the ten tables; the eight-wave build (192 B free beside its two
+// workgroups per CU) keeps the walk.  Both are the same integer predicate: identical masks.
+constexpr bool kLattice = !LLFE_KM_WIDE;
+constexpr int kPairs = kMaxK * (kMaxK - 1) / 2;
+static_assert(kMaxK == 5, "llfe_kml::pair_index numbers the pairs of five centres");
+static_assert(!kLattice || 16 * kPairs <= KT, "one thread per position of every pair table");
+static_assert(llfe_kml::kFrac == 10, "kmeans_lattice.h and the band analysis below share the fixed point");
 // per-wave LDS list of two-centre cubes awaiting their walk (a ring, indices masked): drained at 64, so it
 // holds <= 63 pending + the 64 of one cube batch.  Entry: cube index (< 2^18) | owner k << 18 | contender j << 21
 constexpr int kPend = 128;
@@ -263,6 +273,9 @@ struct KmSmem {
     unsigned long long qtot;             // sum of |p|^2 over all colours (exact)
     unsigned long long drift_hist;       // (trace) Lloyd iterations by largest centre move, 8 x u8 bins: thread 0's, kept
                                          // here because as a register of the Lloyd loop it lived in scratch
+#if !LLFE_KM_WIDE
+    llfe_kml::PairTable pair[kPairs];    // (Lloyd, cells path) the split tables of the centre pairs, rebuilt with the centres
+#endif
 };
 
 // 1024 / KT workgroups per CU (160 KB of LDS): two of 512 threads, four of 256
@@ -480,30 +493,39 @@ __device__ __forceinline__ uint4 split_drain(KmSmem &sm, const CubeEnt *__restri
         const CubeEnt e = ctab[ent & ((1u << kPendIdxBits) - 1u)];
         const int k = (int)((ent >> kPendIdxBits) & 7u), jc = (int)(ent >> (kPendIdxBits + 3));
         const int ox = (int)((e.id >> 12) & 63u) * 4, oy = (int)((e.id >> 6) & 63u) * 4, oz = (int)(e.id & 63u) * 4;
-        int p, s1, s2, s3;
+        const float *ck = sm.c[k], *cj = sm.c[jc];
+        const float ax = ck[0] - cj[0], ay = ck[1] - cj[1], az = ck[2] - cj[2];
+        const float bx = (float)(2 * ox) - (cj[0] + ck[0]), by = (float)(2 * oy) - (cj[1] + ck[1]),
+                    bz = (float)(2 * oz) - (cj[2] + ck[2]);
+        const float f0 = __builtin_fmaf(az, bz, __builtin_fmaf(ay, by, ax * bx));
+        constexpr float sc = (float)(1 << kBisFrac);
+        const int f0q = (int)__builtin_rintf(f0 * sc);
+        const uint32_t mlo = (uint32_t)e.mask, mhi = (uint32_t)(e.mask >> 32);
+        // sg: the owner's side, then the contender's; ka, kb: the clusters they go to
+        uint4 sg;
+        int ka = k, kb = jc;
+#if !LLFE_KM_WIDE
         {
-            const float *ck = sm.c[k], *cj = sm.c[jc];
-            const float ax = ck[0] - cj[0], ay = ck[1] - cj[1], az = ck[2] - cj[2];
-            const float bx = (float)(2 * ox) - (cj[0] + ck[0]), by = (float)(2 * oy) - (cj[1] + ck[1]),
-                        bz = (float)(2 * oz) - (cj[2] + ck[2]);
-            const float f0 = __builtin_fmaf(az, bz, __builtin_fmaf(ay, by, ax * bx));
-            constexpr float sc = (float)(1 << kBisFrac);
+            // the pair's table gives the sides of its smaller and its larger index; which of them is the owner's
+            // does not matter to the sums
+            ka = min(k, jc), kb = max(k, jc);
+            const llfe_kml::Sides sd = llfe_kml::lattice_sides(f0q, sm.pair[llfe_kml::pair_index(ka, kb)], k > jc);
+            sg = make_uint4(sd.lo_x, sd.lo_y, sd.hi_x, sd.hi_y);
+        }
+#else
+        {
             const int gx = (int)__builtin_rintf(ax * (2.f * sc)), gy = (int)__builtin_rintf(ay * (2.f * sc)),
                       gz = (int)__builtin_rintf(az * (2.f * sc));
-            p = kBisBand - ((int)__builtin_rintf(f0 * sc) + 3 * (gx + gy + gz));
-            s1 = gz;
-            s2 = gy - 3 * gz;
-            s3 = gx - 3 * (gy + gz);
+            sg = bisector_signs(kBisBand - (f0q + 3 * (gx + gy + gz)), gz, gy - 3 * gz, gx - 3 * (gy + gz));
         }
-        const uint32_t mlo = (uint32_t)e.mask, mhi = (uint32_t)(e.mask >> 32);
-        const uint4 sg = bisector_signs(p, s1, s2, s3);
+#endif
         const MaskMoments a = mask_moments(mlo & sg.x, mhi & sg.y), b = mask_moments(mlo & sg.z, mhi & sg.w);
-        atomicAdd(&sm.accA[k][tid], (unsigned long long)(a.n * (uint32_t)ox + a.sx) |
-                                        ((unsigned long long)(a.n * (uint32_t)oy + a.sy) << 32));
-        atomicAdd(&sm.accB[k][tid], (unsigned long long)(a.n * (uint32_t)oz + a.sz) | ((unsigned long long)a.n << 32));
-        atomicAdd(&sm.accA[jc][tid], (unsigned long long)(b.n * (uint32_t)ox + b.sx) |
+        atomicAdd(&sm.accA[ka][tid], (unsigned long long)(a.n * (uint32_t)ox + a.sx) |
+                                         ((unsigned long long)(a.n * (uint32_t)oy + a.sy) << 32));
+        atomicAdd(&sm.accB[ka][tid], (unsigned long long)(a.n * (uint32_t)oz + a.sz) | ((unsigned long long)a.n << 32));
+        atomicAdd(&sm.accA[kb][tid], (unsigned long long)(b.n * (uint32_t)ox + b.sx) |
                                          ((unsigned long long)(b.n * (uint32_t)oy + b.sy) << 32));
-        atomicAdd(&sm.accB[jc][tid], (unsigned long long)(b.n * (uint32_t)oz + b.sz) | ((unsigned long long)b.n << 32));
+        atomicAdd(&sm.accB[kb][tid], (unsigned long long)(b.n * (uint32_t)oz + b.sz) | ((unsigned long long)b.n << 32));
         r.x = mlo & ~(sg.x | sg.z);
         r.y = mhi & ~(sg.y | sg.w);
         r.z = cube_origin_key(e.id);
@@ -1861,8 +1883,31 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
     // An iteration is three barrier phases: the sweep; the partial sums of the accumulators; then
     // wave 0 finishes the sums, forms the new centres and the next sweep's thresholds while every
     // thread clears its accumulator slots.  The first sweep's tables and zeros are set up here.
+    // The split tables of the centre pairs (kmeans_lattice.h), from the centres in sm.c: thread t < 16 kPairs takes
+    // position q = t % 16 of pair t / 16 -- its value, its rank among the pair's 16 (the row computes all 16 itself:
+    // no exchange), the sorted value and the position's bit at that rank; the masks m[r] are the suffix OR of those
+    // bits along the 16-lane row.  Only a sweep on the cells path splits cubes, so only it gets tables.
+    const bool lattice = kLattice && use_cubes && C >= kCellMinCubes;
+    auto pair_tables = [&](int t) {
+#if !LLFE_KM_WIDE
+        const int p = t >> 4, q = t & 15;
+        const int lo = llfe_kml::pair_lo(p), hi = llfe_kml::pair_hi(p);
+        if (p < kPairs && hi < K) {
+            llfe_kml::PairTable &pt = sm.pair[p];
+            const int gx = llfe_kml::lattice_step(sm.c[lo][0], sm.c[hi][0]), gy = llfe_kml::lattice_step(sm.c[lo][1], sm.c[hi][1]),
+                      gz = llfe_kml::lattice_step(sm.c[lo][2], sm.c[hi][2]);
+            llfe_kml::lattice_place(pt, q, gx, gy, gz);
+            __builtin_amdgcn_wave_barrier();  // (the row's own stores)
+            uint32_t x = pt.mm[q + 1];
+#pragma unroll
+            for (int d = 1; d < 16; d <<= 1) x |= (uint32_t)__shfl_down((int)x, d, 16);  // (past the row's end: its own x)
+            pt.mm[q + 1] = (uint16_t)x;
+        }
+#endif
+    };
     if (tid == 0) sm.next_chunk = 0;
     if (use_cubes && tid < kMaxK * kMaxK) thr_tables(tid);
+    if (lattice) pair_tables(tid);
 #pragma unroll
     for (int k = 0; k < kMaxK; k++) {
         sm.accA[k][tid] = 0;
@@ -2481,6 +2526,10 @@ __global__ __launch_bounds__(KT, LLFE_KM_MINW) void k_kmeans(const uint32_t *__r
         }  // (pass)
         iter++;
         if (sm.flag) break;
+        if (lattice) {  // the next sweep's split tables from the new centres, over the whole workgroup
+            pair_tables(tid);
+            __syncthreads();
+        }
     }
 
     if (tid == 0) {
