@@ -41,28 +41,35 @@ def _stale() -> bool:
     return any(os.path.getmtime(d) > t for d in deps)
 
 
+def compile_flags(src: str, defs=()) -> list:
+    """What build() puts between hipcc and ``-c`` for the source `src` (a name in SOURCES): the
+    common flags, the language and offload arch, the per-source options and `defs`.  The ISA
+    tests compile with these too, so they read the code the library ships."""
+    common = ["-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", f"-I{os.path.join(ROOT, 'include')}",
+              "-Wall", "-Wno-unused-function", "-Wno-unused-variable",
+              *os.environ.get("LLFE_EXTRA_FLAGS", "").split()]  # (experiments only)
+    if src in ("contours.cpp", "png_decode.cpp", "jpeg_decode.cpp"):  # pure host code
+        lang = ["-x", "c++"]
+    else:
+        lang = ["-x", "hip", f"--offload-arch={ARCH}"]
+    extra = ["-fno-slp-vectorize"] if src == "stencil_stream.hip" else []  # keep the scalar fma chains scalar
+    if src in ILP_SCHED:
+        extra += ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]
+    return [*common, *lang, *extra, *defs]
+
+
 def build(force: bool = False, verbose: bool = False) -> str:
     if not force and not _stale():
         return LIB
     objs = []
     hipcc = _hipcc()
-    common = ["-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", f"-I{os.path.join(ROOT, 'include')}",
-              "-Wall", "-Wno-unused-function", "-Wno-unused-variable",
-              *os.environ.get("LLFE_EXTRA_FLAGS", "").split()]  # (experiments only)
     tmpdir = os.path.join(PKG, "build")
     os.makedirs(tmpdir, exist_ok=True)
     procs = []
     for src, stem, defs in [(s, s, []) for s in SOURCES] + RECOMPILE:
         obj = os.path.join(tmpdir, stem + ".o" if stem != src else src + ".o")
         objs.append(obj)
-        if src in ("contours.cpp", "png_decode.cpp", "jpeg_decode.cpp"):  # pure host code
-            lang = ["-x", "c++"]
-        else:
-            lang = ["-x", "hip", f"--offload-arch={ARCH}"]
-        extra = ["-fno-slp-vectorize"] if src == "stencil_stream.hip" else []  # keep the scalar fma chains scalar
-        if src in ILP_SCHED:
-            extra += ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]
-        cmd = [hipcc, *common, *lang, *extra, *defs, "-c", os.path.join(CSRC, src), "-o", obj]
+        cmd = [hipcc, *compile_flags(src, defs), "-c", os.path.join(CSRC, src), "-o", obj]
         if verbose:
             print(" ".join(cmd), file=sys.stderr)
         procs.append((cmd, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))

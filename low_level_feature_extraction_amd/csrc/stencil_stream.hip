@@ -452,6 +452,10 @@ __device__ __forceinline__ void stencil_wave(const Item &it) {
     constexpr int QD = LLFE_ST_QD;
 #endif
     static_assert(kU % QD == 0, "the input ring's length must divide the unroll");
+    // s_waitcnt immediates that wait on the vector-memory counter alone (gfx9 encoding: vmcnt in
+    // bits 3:0 and 15:14, expcnt and lgkmcnt left at their maxima)
+    constexpr int kWaitSteady = ((QD - 2) & 15) | (7 << 4) | (15 << 8) | (((QD - 2) >> 4) << 14);  // vmcnt(QD - 2)
+    constexpr int kWaitDrain = (7 << 4) | (15 << 8);                                                // vmcnt(0)
     const int t0 = ya - 5, t_end = yb + 5, ts = t0 - 6 - (QD - 3), tf = max(t0, 0);
     const int tb0 = ts >= 0 ? ts - ts % kU : -(((-ts) + kU - 1) / kU) * kU;  // floor to a multiple of kU
 #if !LLFE_ST_LDSQ
@@ -498,22 +502,37 @@ __device__ __forceinline__ void stencil_wave(const Item &it) {
                 if (fast) {
                     __builtin_amdgcn_global_load_lds((const void *)(img + (size_t)yl * W * 3 + (uint32_t)(x * 3)),
                                                      (void *)slot, 12, 0, 0);
+                    __builtin_amdgcn_s_waitcnt(kWaitSteady);
                 } else if (vec && small_img) {
                     __builtin_amdgcn_raw_ptr_buffer_load_lds(irs, (__attribute__((address_space(3))) void *)slot, 12,
                                                              yl * W * 3 + x * 3, 0, 0, 0);
+                    __builtin_amdgcn_s_waitcnt(kWaitSteady);
                 } else {  // unaligned rows: byte loads (REFLECT_101 columns), written now
                     const Raw r = load_px(img, yl, W, x, false, coff);
                     slot[4 * lane] = r.a;
                     slot[4 * lane + 1] = r.b;
                     slot[4 * lane + 2] = r.c;
                 }
+            } else if (vec) {
+                __builtin_amdgcn_s_waitcnt(kWaitDrain);
             }
+            // The waits above are this step's wait for the row it reads below.  The compiler does
+            // not track the direct-to-LDS loads; vector-memory operations complete in order, so
+            // the row issued QD - 1 steps ago has landed once no more operations are outstanding
+            // than were issued after it.
+            //   steady state: the step has just issued its own load, the (QD - 1)-th younger than
+            //     that row's, so vmcnt(QD - 2) leaves only younger loads in flight; the wait sits
+            //     in the load's arm, so no path reaches it without the load
+            //   tail (the segment's last QD - 1 steps issue no load): only t_end - 1 - t younger
+            //     loads exist, 4 down to 0, and a class-map store counts only where one happens
+            //     to follow, so the wait drains: vmcnt(0)
+            // Both are immediates behind wave-uniform branches; rows the byte path wrote with
+            // ordinary LDS stores need no wait of ours.  (The tail drains behind vec alone, so a
+            // vec wave on the byte path -- a border wave of an image of 2^31 bytes or more --
+            // drains too: harmless.  The first QD - 1 steps wait without reading: at most QD - 1
+            // loads are in flight then.)
             if (t >= ts + QD - 1) {
                 ST_MARK(gray);
-                // the direct-to-LDS row issued QD - 1 steps ago has landed once at most QD - 2
-                // younger vector-memory operations are outstanding (they complete in order;
-                // the compiler does not track these loads)
-                if (vec) __builtin_amdgcn_s_waitcnt(((QD - 2) & 15) | (7 << 4) | (15 << 8) | (((QD - 2) >> 4) << 14));
                 Raw cur;
                 if (edge && vec && small_img) {
                     // (32-bit LDS addresses: with generic pointers the compiler hoisted a 64-bit

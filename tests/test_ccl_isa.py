@@ -39,8 +39,8 @@ def _function(asm: str, name: str) -> str:
 
 def test_k_ccl_runs_tile_loop_structure(tmp_path):
     out = tmp_path / "hyst.s"
-    cmd = [_hipcc(), "-O3", "-std=c++17", "-ffp-contract=off", f"-I{os.path.join(ROOT, 'include')}",
-           "--offload-arch=gfx950", "--cuda-device-only", "-S", SRC, "-o", str(out)]
+    from low_level_feature_extraction_amd import _build
+    cmd = [_hipcc(), *_build.compile_flags("hysteresis.hip"), "--cuda-device-only", "-S", SRC, "-o", str(out)]  # build()'s flags
     subprocess.run(cmd, check=True, capture_output=True, timeout=300)
     f = _function(out.read_text(), "k_ccl_runs")
     lines = f.splitlines()

@@ -20,9 +20,12 @@ KERNELS = ("k_stencil", "k_hysteresis_dilate")
 # the 240-column strip and its 8-column halo (240, 241, 256, 257, 479, 480, 481), the 216-row
 # segment rule (216, 217, 433), the 64-pixel tile (64, 65, 63 x 65), the W & 3 vector path
 # (widths 8, 12, 16, 200, 240, 256, 480 against the odd ones) and images smaller than the
-# filters' reach (1 x 1 .. 11 x 12)
+# filters' reach (1 x 1 .. 11 x 12); widths from 488 on have `fast` waves, whose interior strip
+# comes by direct-to-LDS loads: 3 x 488 (H < 6: REFLECT_101 bounces more than once), 13 x 728
+# (strips 1 and 2) and 229 x 488 (two segments: the first one's last rows read the ring after
+# the loads have stopped)
 LADDER = [(1, 1), (2, 3), (5, 7), (11, 12), (64, 240), (65, 241), (40, 256), (40, 257), (216, 8), (217, 9), (433, 16),
-          (30, 479), (30, 480), (30, 481), (63, 65), (130, 200)]
+          (30, 479), (30, 480), (30, 481), (63, 65), (130, 200), (3, 488), (13, 728), (229, 488)]
 FEATS = [("shapes",), ("shadows",), ("shapes", "shadows")]
 
 
@@ -164,25 +167,30 @@ def test_strided_host_and_device_views(backend):
 
 
 def test_packed_device_images_at_odd_addresses(backend):
-    """Two packed device images in one buffer from an odd byte on, w % 4 == 0 next to w % 4 != 0,
-    and a third at an aligned address: the dword paths are chosen per image."""
+    """Packed device images in one buffer from an odd byte on, w % 4 == 0 next to w % 4 != 0, and
+    one at an aligned address: the dword paths are chosen per image.  The 25 x 488 image at an
+    odd address would have `fast` waves (direct-to-LDS loads) were it aligned; it takes the byte
+    path whole."""
     import torch
 
-    a, b, c = (synth.synth_numpy(3, 70, 88, seed=12), synth.synth_numpy(4, 64, 65, seed=12),
-               synth.synth_numpy(5, 40, 256, seed=12))
-    flat = torch.zeros(1 + a.size + b.size, dtype=torch.uint8, device="cuda")
+    a, b, c, d = (synth.synth_numpy(3, 70, 88, seed=12), synth.synth_numpy(4, 64, 65, seed=12),
+                  synth.synth_numpy(5, 40, 256, seed=12), synth.synth_numpy(6, 25, 488, seed=12))
+    flat = torch.zeros(1 + a.size + b.size + d.size, dtype=torch.uint8, device="cuda")
     flat[1:1 + a.size] = torch.from_numpy(a).reshape(-1).cuda()
-    flat[1 + a.size:] = torch.from_numpy(b).reshape(-1).cuda()
+    flat[1 + a.size:1 + a.size + b.size] = torch.from_numpy(b).reshape(-1).cuda()
+    flat[1 + a.size + b.size:] = torch.from_numpy(d).reshape(-1).cuda()
     va = flat[1:1 + a.size].view(70, 88, 3)
-    vb = flat[1 + a.size:].view(64, 65, 3)
+    vb = flat[1 + a.size:1 + a.size + b.size].view(64, 65, 3)
     vc = torch.from_numpy(c).cuda()
+    vd = flat[1 + a.size + b.size:].view(25, 488, 3)
     assert va.data_ptr() % 4 == 1 and va.is_contiguous() and vc.data_ptr() % 16 == 0
+    assert vd.data_ptr() % 2 == 1 and vd.is_contiguous()
     feats = ("shapes", "shadows")
-    got = backend.process_images([va, vb, vc], feats, seed=6, index_base=40, shapes="one_pass")
-    for i, im in enumerate((a, b, c)):
+    got = backend.process_images([va, vb, vc, vd], feats, seed=6, index_base=40, shapes="one_pass")
+    for i, im in enumerate((a, b, c, d)):
         _same(got[i], backend.process(im[None], feats, seed=6, index_base=40 + i)[0], f"odd address {i}")
-    masks = backend.shape_masks_images([va, vb, vc])
-    for m, im in zip(masks, (a, b, c)):
+    masks = backend.shape_masks_images([va, vb, vc, vd])
+    for m, im in zip(masks, (a, b, c, d)):
         assert np.array_equal(m, backend.shape_mask(im[None])[0].cpu().numpy())
 
 

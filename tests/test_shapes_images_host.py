@@ -16,7 +16,7 @@ from low_level_feature_extraction_amd import backend as B
 
 # the size ladder of tests/test_gpu_shapes_images.py: (height, width)
 LADDER = [(1, 1), (2, 3), (5, 7), (11, 12), (64, 240), (65, 241), (40, 256), (40, 257), (216, 8), (217, 9), (433, 16),
-          (30, 479), (30, 480), (30, 481), (63, 65), (130, 200)]
+          (30, 479), (30, 480), (30, 481), (63, 65), (130, 200), (3, 488), (13, 728), (229, 488)]
 STRIP, SEG, TILE = 240, 216, 64
 MAX_TILES = 2**31 // 4096  # 524288: the ids tile * 4096 + node are int
 TILE_BYTES = 4096 * 7 + 512 + 20  # llfe.h, llfe_shapes_images_layout
@@ -75,6 +75,22 @@ def test_layout_of_the_size_ladder(sizes):
     assert p["workspace_bytes"] == _workspace(p)
 
 
+def test_the_ladder_has_fast_waves():
+    """What the GPU ladder's comment claims of its widest shapes: each has a strip whose whole
+    window lies inside the image (a `fast` wave, W % 4 == 0), 13 x 728 has two, and 229 x 488 has
+    two segments, so a `fast` wave's segment ends inside the image."""
+    from tests import stencil_cases as SC
+
+    for h, w in ((3, 488), (13, 728), (229, 488)):
+        assert (h, w) in LADDER and w % 4 == 0
+        assert SC.fast_strips(w), (h, w)
+        assert SC.geometry(h, w) == _geometry(h, w)
+    assert SC.fast_strips(488) == [1] and SC.fast_strips(728) == [1, 2]
+    assert SC.geometry(3, 488)[1] == SC.geometry(13, 728)[1] == 1
+    assert SC.geometry(229, 488)[1:] == (2, 115)
+    assert not any(SC.fast_strips(w) for h, w in LADDER if w < 488)  # (no other shape of the ladder has one)
+
+
 def test_every_image_has_at_least_as_many_tiles_as_waves():
     for h in (1, 63, 64, 65, 215, 216, 217, 432, 433, 1080, 5000):
         for w in (1, 64, 239, 240, 241, 1920, 7000):
@@ -83,7 +99,7 @@ def test_every_image_has_at_least_as_many_tiles_as_waves():
 
 
 def test_pass_cutting_under_a_budget(monkeypatch):
-    monkeypatch.setenv("LLFE_WORKSPACE_GB", "0.002")  # 2 MB: the ladder's 78 tiles alone need 2.3 MB
+    monkeypatch.setenv("LLFE_WORKSPACE_GB", "0.002")  # 2 MB: the ladder's 130 tiles alone need 3.8 MB
     budget = 0.002e9
     sizes = LADDER + [(130, 200), (64, 64), (300, 300)]
     recs, work, passes = B.shapes_images_layout(_images(sizes))
@@ -233,8 +249,8 @@ def _tile_loop_structure(asm: str, symbol: str):
 
 def test_ragged_k_ccl_runs_has_the_uniform_tile_loop_structure(tmp_path):
     out = tmp_path / "hyst.s"
-    cmd = [_hipcc(), "-O3", "-std=c++17", "-ffp-contract=off", f"-I{os.path.join(ROOT, 'include')}",
-           "--offload-arch=gfx950", "--cuda-device-only", "-S", SRC, "-o", str(out)]
+    from low_level_feature_extraction_amd import _build
+    cmd = [_hipcc(), *_build.compile_flags("hysteresis.hip"), "--cuda-device-only", "-S", SRC, "-o", str(out)]  # build()'s flags
     subprocess.run(cmd, check=True, capture_output=True, timeout=300)
     asm = out.read_text()
     # k_ccl_runs<false> / <true>: the Itanium mangling of the bool template argument
