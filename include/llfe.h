@@ -591,6 +591,48 @@ int llfe_thumbnail_pil_images(llfe_ctx *ctx, const llfe_image_desc *images, int3
  * host picks a smaller power-of-two height for an image whose tiles would need more than
  * lds_rows source rows) and the widest filter it takes, so that tests can stand on its seams */
 int llfe_thumbnail_images_tiling(int32_t *tile_w, int32_t *tile_h, int32_t *lds_rows, int32_t *max_ksize);
+/* validate_and_preprocess_image's resize (utils.py:118-143) of a batch whose images each have
+ * their own size: where one image's result lies in the packed destination. */
+typedef struct {
+    int64_t offset;          /* byte offset of the result in dst, a multiple of 16 */
+    int32_t height, width;   /* result size */
+    int32_t interpolation;   /* LLFE_CV_INTER_* used; 0 when not resized */
+    int32_t resized;         /* 0: the rule leaves it; it is copied */
+} llfe_resize_out;           /* 24 bytes */
+/* host only, no ctx: the rule (llfe_preprocess_size) per image and the layout a call below will
+ * write (results in input order, each packed height x width x 3, each starting at a multiple of
+ * 16); *dst_bytes = bytes dst must hold.  LLFE_ERR_INVALID: n < 0, a NULL output, a mode outside
+ * LLFE_PRE_*, a descriptor llfe_process_images would reject, or an image whose rule size has a
+ * side of 0 (1 x 2001 under LLFE_PRE_AUTO: cv2.resize raises there). */
+int llfe_preprocess_images_layout(const llfe_image_desc *images, int32_t n, int32_t preprocessing,
+                                  llfe_resize_out *outs, int64_t *dst_bytes);
+/* The resize of `preprocessing` over a batch of n BGR u8 images, each its own size, row stride
+ * and memory (host or device; the noise fields are ignored), into dst (device), packed as `outs`
+ * says (filled as llfe_preprocess_images_layout fills it).  Every result is byte-identical to
+ * llfe_resize_cv of that image at the rule's size and interpolation; an image the rule leaves
+ * is copied.  One plan per distinct (size, result size, interpolation), one upload of all
+ * tables, one launch per plan kind (cvresize_images.hip: k_cv_images_area, _area_fast, _generic,
+ * _copy); device sources are read in place, host sources are staged through a bounded workspace
+ * of the call's own (in chunks when the batch exceeds it; LLFE_RESIZE_STAGE_BYTES overrides the
+ * bound), so the call does not depend on submitted batches.  Everything is checked on the host
+ * before the first launch: dst_capacity below the layout's total is LLFE_ERR_CAPACITY with dst
+ * untouched; a NULL ctx, a bad descriptor, a bad mode or an image whose rule size has a side of
+ * 0 is LLFE_ERR_INVALID (llfe_last_error names the image); n == 0 is LLFE_OK.  Synchronous: one
+ * stream synchronisation, at the end. */
+int llfe_preprocess_images(llfe_ctx *ctx, const llfe_image_desc *images, int32_t n, int32_t preprocessing,
+                           uint8_t *dst, int64_t dst_capacity, llfe_resize_out *outs, llfe_stream stream);
+/* The stage entry: sizes3 holds (out_h, out_w, LLFE_CV_INTER_*) per image; every result is
+ * byte-identical to llfe_resize_cv(..., 3, out_h, out_w, interpolation).  LINEAR at exactly 2 x 2
+ * and AREA upscales run as cv2.resize classifies them; LLFE_CV_INTER_CUBIC is
+ * LLFE_ERR_UNSUPPORTED (the text path keeps llfe_resize_cv), any other code or a size <= 0
+ * LLFE_ERR_INVALID.  Otherwise as above. */
+int llfe_resize_cv_images(llfe_ctx *ctx, const llfe_image_desc *images, int32_t n, const int32_t *sizes3,
+                          uint8_t *dst, int64_t dst_capacity, llfe_resize_out *outs, llfe_stream stream);
+/* host only: the output tile of the kernels (tile_w pixels x at most tile_h rows; the host picks
+ * a smaller power-of-two height for an image whose tiles would need more than lds_rows source
+ * rows, and the global-memory arm of the kernel where no height fits), so that tests can stand
+ * on its seams */
+int llfe_resize_cv_images_tiling(int32_t *tile_w, int32_t *tile_h, int32_t *lds_rows);
 /* host-side external contours (findContours RETR_EXTERNAL/CHAIN_APPROX_SIMPLE,
  * shape pyc @L140) on a host u8 mask; points x,y pairs; offsets[n_contours+1].
  * Returns the number of contours, or LLFE_ERR_CAPACITY with *needed_points set. */

@@ -18,7 +18,7 @@ from .image_processor import ImageProcessor
 from .models import ColorFeatures, FeatureType, FontFeatures
 from .shadow_analyzer import ShadowAnalyzer
 from .shape_analyzer import ShapeAnalyzer
-from .utils import PreprocessingMode, validate_and_preprocess_image
+from .utils import PreprocessingMode, validate_and_preprocess_image, validate_and_preprocess_images
 
 
 def run_batch(images, features=("colors", "shapes", "shadows"), seed=None, noise=None):
@@ -40,4 +40,5 @@ __all__ = [
     "ShapeAnalyzer",
     "run_batch",
     "validate_and_preprocess_image",
+    "validate_and_preprocess_images",
 ]

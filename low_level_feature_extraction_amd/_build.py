@@ -14,8 +14,8 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libllfe.so")
-SOURCES = ["llfe_context.cpp", "llfe_pipeline.cpp", "llfe_stages.cpp", "llfe_resize.cpp", "llfe_decode.cpp", "llfe_colors_images.cpp", "llfe_shapes_images.cpp", "contours.cpp", "png_decode.cpp", "jpeg_decode.cpp", "stencil.hip", "stencil_stream.hip", "hysteresis.hip", "unique.hip", "kmeans.hip", "kmeans_big.hip", "resize.hip", "contours_gpu.hip",
-           "cvresize.hip", "text.hip", "gather.hip", "font.hip", "font_bits.hip", "jpeg_huff.hip", "png_inflate.hip", "thumb_images.hip", "jpeg_images.hip"]
+SOURCES = ["llfe_context.cpp", "llfe_pipeline.cpp", "llfe_stages.cpp", "llfe_resize.cpp", "llfe_decode.cpp", "llfe_colors_images.cpp", "llfe_shapes_images.cpp", "llfe_preprocess_images.cpp", "contours.cpp", "png_decode.cpp", "jpeg_decode.cpp", "stencil.hip", "stencil_stream.hip", "hysteresis.hip", "unique.hip", "kmeans.hip", "kmeans_big.hip", "resize.hip", "contours_gpu.hip",
+           "cvresize.hip", "text.hip", "gather.hip", "font.hip", "font_bits.hip", "jpeg_huff.hip", "png_inflate.hip", "thumb_images.hip", "jpeg_images.hip", "cvresize_images.hip"]
 HEADERS = ["llfe_ctx.h", "llfe_internal.h", "contours.h", "kmeans_common.h", "kmeans_lattice.h", "jpeg_huff_core.h", "jpeg_desc_check.h", "jpeg_recon_core.h", "jpeg_images.h", "jpeg_orient.h", "png_inflate_core.h", "host_fanout.h"]
 # second builds of a source under another object name: (source, object stem, defines)
 RECOMPILE = [("kmeans.hip", "kmeans_wide", ["-DLLFE_KM_WIDE=1", "-DLLFE_KM_THREADS=512", "-DLLFE_KM_UNROLL=4"])]

@@ -97,6 +97,16 @@ class LlfeThumbOut(C.Structure):
     ]
 
 
+class LlfeResizeOut(C.Structure):
+    _fields_ = [
+        ("offset", C.c_int64),
+        ("height", C.c_int32),
+        ("width", C.c_int32),
+        ("interpolation", C.c_int32),
+        ("resized", C.c_int32),
+    ]
+
+
 class LlfeColorImage(C.Structure):
     _fields_ = [
         ("pixels", C.c_int64),
@@ -367,6 +377,10 @@ SIGNATURES = {
     "llfe_thumbnail_images_layout": (C.c_int, [_vp, _i32, _i32, _i32, _vp, C.POINTER(C.c_int64)]),
     "llfe_thumbnail_pil_images": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _i64, _vp, _vp]),
     "llfe_thumbnail_images_tiling": (C.c_int, [C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
+    "llfe_preprocess_images_layout": (C.c_int, [_vp, _i32, _i32, _vp, C.POINTER(C.c_int64)]),
+    "llfe_preprocess_images": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp]),
+    "llfe_resize_cv_images": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i64, _vp, _vp]),
+    "llfe_resize_cv_images_tiling": (C.c_int, [C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
     "llfe_find_contours":(C.c_int, [_vp, _i32, _i32, _vp, _i64, _vp, _i32, C.POINTER(C.c_int64)]),
     "llfe_border_radius": (C.c_double, [_vp, _i32, C.c_double]),
     "llfe_classify_contour": (C.c_int, [_vp, _i32, C.POINTER(LlfeShape)]),

@@ -249,6 +249,49 @@ def thumbnail_images_layout(images, max_w=1920, max_h=1080, device: int = 0):
     return [(int(o.offset), int(o.height), int(o.width), int(o.resized)) for o in outs[:len(keep)]], int(total.value)
 
 
+def resize_cv_images_tiling():
+    """(tile width, largest tile height, LDS rows) of the k_cv_images_* kernels
+    (llfe_resize_cv_images_tiling)."""
+    v = [C.c_int32(0) for _ in range(3)]
+    if L.lib().llfe_resize_cv_images_tiling(*[C.byref(x) for x in v]) < 0:  # pragma: no cover
+        raise ValueError("resize_cv_images_tiling")
+    return tuple(x.value for x in v)
+
+
+def _pre_mode(preprocessing: str) -> int:
+    try:
+        return PRE_MODES[preprocessing]
+    except (KeyError, TypeError):
+        raise ValueError(f"preprocessing must be one of {sorted(PRE_MODES)}, got {preprocessing!r}") from None
+
+
+def _resize_outs(outs, n):
+    return [(int(o.offset), int(o.height), int(o.width), int(o.interpolation), int(o.resized)) for o in outs[:n]]
+
+
+def preprocess_images_layout(images, preprocessing: str = "auto", device: int = 0):
+    """Where llfe_preprocess_images puts each result: -> (list of (offset, height, width,
+    interpolation code, resized), bytes the packed destination must hold).  Host only."""
+    mode = _pre_mode(preprocessing)
+    descs, keep, _, _, _ = _image_descs(images, device)
+    outs = (L.LlfeResizeOut * max(len(keep), 1))()
+    total = C.c_int64(0)
+    rc = L.lib().llfe_preprocess_images_layout(descs.ctypes.data, len(keep), mode, outs, C.byref(total))
+    if rc < 0:
+        raise L.LlfeError(rc, "invalid preprocessing batch")
+    return _resize_outs(outs, len(keep)), int(total.value)
+
+
+PREPROCESS_ROUTES = ("per_image", "one_pass")
+
+
+def preprocess_route(preprocess: str) -> str:
+    """process_images' ``preprocess`` option, checked."""
+    if preprocess not in PREPROCESS_ROUTES:
+        raise ValueError(f"preprocess must be one of {sorted(PREPROCESS_ROUTES)}, got {preprocess!r}")
+    return preprocess
+
+
 def text_size(h: int, w: int):
     """Output (height, width) of TextExtractor.preprocess_image (llfe_text_size)."""
     oh, ow = C.c_int32(0), C.c_int32(0)
@@ -441,7 +484,7 @@ class Backend:
 
     def process_images(self, images, features=("colors", "shapes", "shadows"), seed: int = 0, noise=None,
                        index_base: int = 0, n_colors: int = 5, preprocessing: str = "none",
-                       colors: str = "grouped", shapes: str = "grouped") -> list:
+                       colors: str = "grouped", shapes: str = "grouped", preprocess: str = "per_image") -> list:
         """Ragged batch through llfe_process_images: ``images`` is a list of H x W x 3 BGR
         uint8 images of any sizes -- numpy arrays (host) or torch tensors (host or GPU;
         rows may be strided, pixels must be packed) -- with validate_and_preprocess_image's
@@ -453,12 +496,27 @@ class Backend:
         sizes (LLFE_IMAGES_COLORS_ONE_PASS), with the same results.  ``shapes``: the same choice
         for shapes and shadows (LLFE_IMAGES_SHAPES_ONE_PASS: one stencil launch, one hysteresis,
         one mask copy and one fan-out over the host contour pool for the whole list; fonts stay
-        grouped, and so do shapes and shadows while contours run on the GPU).  Returns
-        ImageFeatures in input order."""
+        grouped, and so do shapes and shadows while contours run on the GPU).  ``preprocess``:
+        "per_image" resizes each image the rule resizes with a launch of its own inside the call;
+        "one_pass" sends those images through one ``preprocess_images`` call first and proceeds
+        with its device tensors in their places and no preprocessing, with the same results
+        (the other images are passed through as they are).  Returns ImageFeatures in input
+        order."""
         flags, sflags = colors_flags(colors), shapes_flags(shapes)
         n = len(images)
         mode = PRE_MODES.get(preprocessing, 0)
         descs, keep, hs, ws, first = _image_descs(images, self.device)
+        if preprocess_route(preprocess) == "one_pass" and mode:
+            idx = [i for i in range(n) if preprocess_size(ws[i], hs[i], preprocessing)]
+            if idx:  # their records go through one call; its results take their places in `descs`
+                res = self._preprocess_descs(np.ascontiguousarray(descs[idx]), first, mode)
+                for i, t in zip(idx, res):
+                    keep[i], hs[i], ws[i] = t, t.shape[0], t.shape[1]
+                descs["data"][idx] = [t.data_ptr() for t in res]
+                descs["height"][idx], descs["width"][idx] = [hs[i] for i in idx], [ws[i] for i in idx]
+                descs["row_stride"][idx], descs["on_device"][idx] = [3 * ws[i] for i in idx], 1
+                first = res[0] if first is None else first
+            preprocessing, mode = "none", 0
         for i in range(n):
             plan = preprocess_size(ws[i], hs[i], preprocessing)
             if plan:
@@ -1137,6 +1195,68 @@ class Backend:
                    packed.numel(), outs, self._stream(first))
         del keep
         return [packed[o.offset: o.offset + o.height * o.width * 3].view(o.height, o.width, 3) for o in outs]
+
+    def _resize_images(self, fn: str, descs, first, arg, out_sizes, host: bool = False):
+        """llfe_preprocess_images / llfe_resize_cv_images over the records ``descs`` (``arg``: the
+        mode / the address of the size triples; the caller keeps the images alive) -> (views into
+        one packed device tensor, the call's llfe_resize_out records)."""
+        torch = _torch()
+        n = len(descs)
+        outs = (L.LlfeResizeOut * max(n, 1))()
+        # the packed size: every result at a multiple of 16 (a bad size is the call's to refuse)
+        cap = sum(16 + 3 * oh * ow for oh, ow in out_sizes) if n else 0
+        packed = torch.empty(max(cap, 1), dtype=torch.uint8, device=f"cuda:{self.device}")
+        self._call(fn, descs.ctypes.data, n, arg, packed.data_ptr(), packed.numel(), outs, self._stream(first))
+        if host:  # one D2H of the packed results
+            packed = packed.cpu().numpy()
+            return [packed[o.offset: o.offset + o.height * o.width * 3].reshape(o.height, o.width, 3)
+                    for o in outs[:n]], outs
+        return [packed[o.offset: o.offset + o.height * o.width * 3].view(o.height, o.width, 3) for o in outs[:n]], outs
+
+    def preprocess_images(self, images, preprocessing: str = "auto", host: bool = False) -> list:
+        """validate_and_preprocess_image's resize (``preprocessing``: none / auto / high_quality /
+        performance) of a list of H x W x 3 BGR uint8 images of any sizes -- numpy arrays and / or
+        torch tensors, host or GPU, rows may be strided -- in one llfe_preprocess_images call.
+        -> one device tensor H' x W' x 3 per image, in input order, each a view into one packed
+        uint8 tensor at a multiple of 16 bytes; an image the rule leaves is copied.  The bytes are
+        those of ``resize_cv`` of each image.  ``host=True``: numpy arrays instead, from one
+        device-to-host copy of the packed tensor."""
+        mode = _pre_mode(preprocessing)
+        if len(images) == 0:
+            return []
+        descs, keep, _, _, first = _image_descs(images, self.device)
+        res = self._preprocess_descs(descs, first, mode, host)
+        del keep
+        return res
+
+    def _preprocess_descs(self, descs, first, mode: int, host: bool = False) -> list:
+        """preprocess_images over prepared records: the layout (host only), then the call."""
+        n = len(descs)
+        lay = (L.LlfeResizeOut * n)()
+        total = C.c_int64(0)
+        rc = self._lib.llfe_preprocess_images_layout(descs.ctypes.data, n, mode, lay, C.byref(total))
+        if rc < 0:  # (the call itself names the image)
+            self._call("llfe_preprocess_images", descs.ctypes.data, n, mode, None, 0, lay, None)
+            raise L.LlfeError(rc, "invalid preprocessing batch")  # pragma: no cover
+        return self._resize_images("llfe_preprocess_images", descs, first, mode, [(o.height, o.width) for o in lay],
+                                   host)[0]
+
+    def resize_cv_images(self, images, sizes) -> list:
+        """cv2.resize of a list of H x W x 3 uint8 images of any sizes in one llfe_resize_cv_images
+        call; ``sizes``: one (out_w, out_h, interpolation) per image, as ``resize_cv`` takes them
+        ("linear" / "area" / "lanczos4" or the OpenCV code).  -> device tensors as
+        ``preprocess_images`` returns them."""
+        if len(sizes) != len(images):
+            raise ValueError("sizes must hold one (out_w, out_h, interpolation) per image")
+        if len(images) == 0:
+            return []
+        s3 = np.ascontiguousarray([(int(oh), int(ow), CV_INTER[it] if isinstance(it, str) else int(it))
+                                   for ow, oh, it in sizes], dtype=np.int32)
+        out_sizes = [(max(int(oh), 0), max(int(ow), 0)) for ow, oh, _ in sizes]
+        descs, keep, _, _, first = _image_descs(images, self.device)
+        res = self._resize_images("llfe_resize_cv_images", descs, first, s3.ctypes.data, out_sizes)[0]
+        del keep
+        return res
 
 
 _FONT_FIELDS = ("n_contours", "n_regions", "x", "y", "width", "height", "gray_sum")

@@ -284,13 +284,15 @@ class ColorExtractor:
     @staticmethod
     def extract_colors_batch(images: List[np.ndarray], n_colors: int = 5, seed: Optional[int] = None,
                              noise=None, index_base: Optional[int] = None,
-                             colors: str = "grouped", shapes: str = "grouped") -> List[ColorFeatures]:
+                             colors: str = "grouped", shapes: str = "grouped", preprocessing: str = "none",
+                             preprocess: str = "per_image") -> List[ColorFeatures]:
         """Batched extract_colors for same-size BGR uint8 images (N x H x W x 3 array or a
         list).  Mixed sizes are grouped, or with ``colors="one_pass"`` share one device pass;
+        ``preprocessing`` / ``preprocess`` (lists): the resize mode first, per image or in one pass;
         ``noise`` (parity mode) is the per-image
         np.random.normal(0, 0.5, (H*W, 3)).astype(np.int8) stream."""
         from .pipeline import run_batch
 
         res = run_batch(images, ("colors",), seed=seed, noise=noise, n_colors=n_colors, index_base=index_base,
-                        colors=colors, shapes=shapes)
+                        colors=colors, shapes=shapes, preprocessing=preprocessing, preprocess=preprocess)
         return [r["colors"] for r in res]

@@ -372,6 +372,9 @@ struct llfe_ctx {
     // workspace of one chunk of images
     llfe_host::HostBuf<uint8_t> h_thumb_tab;
     llfe_host::DevBuf<uint8_t> d_thumb_tab, d_thumb_ws;
+    // llfe_preprocess_images / llfe_resize_cv_images: the same two of its own
+    llfe_host::HostBuf<uint8_t> h_cvimg_tab;
+    llfe_host::DevBuf<uint8_t> d_cvimg_tab, d_cvimg_ws;
     llfe_host::DevBuf<uint8_t> d_text;                  // llfe_text_binary: gray, then its upscale
     llfe_host::DevBuf<unsigned long long> d_text_hist;  // 256 bins + threshold + count of 255s
     // contours on the GPU (contours_gpu.hip) or on the host pool from the D2H'd mask

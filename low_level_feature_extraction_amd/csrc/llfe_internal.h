@@ -450,6 +450,35 @@ int cv_resize_plan_scaled(int h, int w, int cn, int oh, int ow, double inv_x, do
 hipError_t launch_cv_resize(const CvResizePlan &p, const uint8_t *src, uint8_t *dst, const int32_t *d_tab,
                             hipStream_t s);
 
+// cv2.resize of a mixed-size batch of BGR images (cvresize_images.hip): one launch per plan kind
+// covers every image of that kind; a workgroup takes one (image, tile) entry of the kind's work
+// table and reads that image's record.
+constexpr int kCvTileW = 64;             // output pixels per tile row (192 bytes)
+constexpr int kCvTileH = 16;             // output rows per tile at most; the host picks per image
+constexpr int kCvLdsRows = 40;           // AREA: source rows whose horizontal pass one tile keeps in LDS
+constexpr int kCvStageBytes = 8192;      // AREA: one chunk of source rows in LDS
+constexpr int kCvMaxPairs = 1024;        // AREA: (si, alpha) pairs of a tile's slice of the x table
+constexpr int kCvMaxYPairs = 64;         // AREA: (row, beta) pairs of a tile's slice of the y table
+constexpr int kCvFastStageBytes = 16384;  // AREA_FAST: the tile's source rows in LDS
+constexpr int kCvGenericTileH = 4;       // GENERIC and the global-memory arms: a lane per pixel
+enum CvArm : int32_t { kCvArmLds = 0, kCvArmGlobal = 1 };
+struct CvImgRec {
+    const uint8_t *src;  // h x w BGR, rows src_stride bytes apart
+    uint8_t *dst;        // oh x ow packed
+    int64_t src_stride;
+    int32_t h, w, oh, ow;
+    int32_t kind;        // CvResizePlan::Kind
+    int32_t fx, fy;      // AREA_FAST
+    int32_t ks, xmax, x_vec;  // GENERIC (x_vec: where this image's LINEAR vertical forms split)
+    int32_t xt, yt;      // offsets of the plan's x and y tables in the int32 table
+    int32_t tile_h, tiles_x, arm, pad_;
+};
+struct CvImgWork {
+    int32_t image, tile;
+};
+hipError_t launch_cv_images(int kind, const CvImgRec *recs, const CvImgWork *work, int n_work, const int32_t *tab,
+                            hipStream_t s);
+
 // TextExtractor.preprocess_image (text.hip): gray of n pixels (cn 1, 3 or 4); Otsu
 // binary of n gray pixels; hist = 258 u64 of device scratch (threshold in hist[256])
 hipError_t launch_text_gray(const uint8_t *img, long long n, int cn, uint8_t *gray, hipStream_t s);

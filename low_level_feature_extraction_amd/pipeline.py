@@ -16,7 +16,7 @@ from typing import Iterable, List, Optional, Sequence
 
 import numpy as np
 
-from .backend import Backend, colors_flags, feature_mask, shapes_flags  # noqa: F401  (feature_mask validates names)
+from .backend import Backend, colors_flags, feature_mask, preprocess_route, shapes_flags  # noqa: F401  (feature_mask validates names)
 from .color_extractor import ColorExtractor, palette_features
 
 
@@ -78,7 +78,7 @@ def assemble_batch(recs, features: Iterable[str]) -> list:
 def run_batch(images, features: Sequence[str] = ("colors", "shapes", "shadows"), seed: Optional[int] = None,
               noise=None, backend: Optional[Backend] = None, raw: bool = False, n_colors: int = 5,
               index_base: Optional[int] = None, preprocessing: str = "none", colors: str = "grouped",
-              shapes: str = "grouped") -> List[dict]:
+              shapes: str = "grouped", preprocess: str = "per_image") -> List[dict]:
     """images: N x H x W x 3 BGR uint8 array / torch tensor, or a list of H x W x 3
     arrays of any sizes.  Returns one dict per image, in input order.  ``index_base``
     fixes the global index of image 0 (the per-image noise / k-means seeds); by default
@@ -86,11 +86,13 @@ def run_batch(images, features: Sequence[str] = ("colors", "shapes", "shadows"),
     validate_and_preprocess_image's resize mode, applied on the GPU before the features.
     ``colors`` (lists only): "grouped", or "one_pass" for the colours of all images in one
     device pass whatever their sizes (Backend.process_images).  ``shapes`` (lists only): the same
-    choice for shapes and shadows."""
+    choice for shapes and shadows.  ``preprocess`` (lists only): "per_image", or "one_pass" for the
+    resize of every image the mode resizes in one device pass first (Backend.process_images)."""
     from . import color_extractor as ce
 
     colors_flags(colors)
     shapes_flags(shapes)
+    preprocess_route(preprocess)
     be = backend or Backend.get()
     feats = tuple(getattr(f, "value", f) for f in features)
     feature_mask(feats)
@@ -112,6 +114,6 @@ def run_batch(images, features: Sequence[str] = ("colors", "shapes", "shadows"),
     if noise is not None:
         nz = [np.asarray(noise[i], np.int8).reshape(-1, 3) for i in range(len(imgs))]
     res = be.process_images(imgs, feats, seed=seed, noise=nz, index_base=base, n_colors=n_colors,
-                            preprocessing=preprocessing, colors=colors, shapes=shapes)
+                            preprocessing=preprocessing, colors=colors, shapes=shapes, preprocess=preprocess)
     out = res if raw else assemble_batch(res, feats)
     return out  # type: ignore[return-value]

@@ -29,8 +29,11 @@ class ShadowAnalyzer:
         return run_batch([_bgr(image)], ("shadows",))[0]["shadows"]["shadow_level"]
 
     @staticmethod
-    def analyze_shadow_level_batch(images, shapes: str = "grouped") -> List[str]:
-        """``shapes="one_pass"``: a list of images of any sizes in one device pass (run_batch)."""
+    def analyze_shadow_level_batch(images, shapes: str = "grouped", preprocessing: str = "none",
+                                   preprocess: str = "per_image") -> List[str]:
+        """``shapes="one_pass"``: a list of images of any sizes in one device pass (run_batch);
+        ``preprocessing`` / ``preprocess``: the resize mode first, per image or in one pass."""
         from .pipeline import run_batch
 
-        return [r["shadows"]["shadow_level"] for r in run_batch(images, ("shadows",), shapes=shapes)]
+        return [r["shadows"]["shadow_level"] for r in run_batch(images, ("shadows",), shapes=shapes,
+                                                                  preprocessing=preprocessing, preprocess=preprocess)]

@@ -49,8 +49,11 @@ class ShapeAnalyzer:
         return run_batch([_bgr(image)], ("shapes",))[0]["shapes"]
 
     @staticmethod
-    def analyze_shapes_batch(images, shapes: str = "grouped") -> List[Dict[str, Any]]:
-        """``shapes="one_pass"``: a list of images of any sizes in one device pass (run_batch)."""
+    def analyze_shapes_batch(images, shapes: str = "grouped", preprocessing: str = "none",
+                             preprocess: str = "per_image") -> List[Dict[str, Any]]:
+        """``shapes="one_pass"``: a list of images of any sizes in one device pass (run_batch);
+        ``preprocessing`` / ``preprocess``: the resize mode first, per image or in one pass."""
         from .pipeline import run_batch
 
-        return [r["shapes"] for r in run_batch(images, ("shapes",), shapes=shapes)]
+        return [r["shapes"] for r in run_batch(images, ("shapes",), shapes=shapes, preprocessing=preprocessing,
+                                                 preprocess=preprocess)]

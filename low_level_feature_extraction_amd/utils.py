@@ -70,6 +70,63 @@ def _http_exception(status_code: int, detail: str):
         return ValueError(detail)
 
 
+_DECODE_DETAIL = "Failed to decode image. The file may be corrupted or in an unsupported format."
+
+
+def validate_and_preprocess_images(images_bytes, preprocessing: str, device: bool = False, decode: str = "host",
+                                   entropy: str = "host", restarts: bool = False, orient: str = "host") -> list:
+    """Batched validate_and_preprocess_image: decode, then the mode resize of every image the
+    rule resizes, whatever the sizes, in one llfe_preprocess_images call
+    (Backend.preprocess_images).  Returns the images in input order; an input that fails to
+    decode gets the exception validate_and_preprocess_image would raise, in its place.
+
+    ``device=False``: host arrays with the bytes of ``preprocess_decoded`` (the results of the
+    one call come back in one device-to-host copy; an image the rule leaves is the decoded array
+    itself).  ``device=True``: device tensors (views into one packed tensor), which run_batch,
+    Backend.process_images and MicroBatcher.submit take as they are.
+
+    ``decode`` / ``entropy`` / ``restarts`` / ``orient`` are those of
+    ImageProcessor.auto_process_images: ``decode="device"`` (with ``device=True`` only) chains
+    decode.decode_images_device, so a JPEG's pixels never cross PCIe."""
+    from .backend import Backend
+    from .decode import decode_images_device, decode_many
+
+    if decode not in ("host", "device"):
+        raise ValueError('decode must be "host" or "device"')
+    if decode == "device" and not device:
+        raise ValueError('decode="device" needs device=True')
+    if entropy not in ("host", "device"):
+        raise ValueError('entropy must be "host" or "device"')
+    if entropy == "device" and decode != "device":
+        raise ValueError('entropy="device" needs decode="device"')
+    if restarts and entropy != "device":
+        raise ValueError('restarts=True needs entropy="device"')
+    if orient not in ("host", "device"):
+        raise ValueError('orient must be "host" or "device"')
+    if orient == "device" and decode != "device":
+        raise ValueError('orient="device" needs decode="device"')
+    preprocessing = getattr(preprocessing, "value", preprocessing)
+    mode = preprocessing if preprocessing in _LIMITS else "none"  # (other names do not resize)
+    if decode == "device":
+        decoded = decode_images_device(list(images_bytes), Backend.get().device, entropy=entropy, restarts=restarts,
+                                       orient=orient)
+    else:
+        decoded = decode_many(list(images_bytes))
+    out: list = list(decoded)
+    for i, im in enumerate(decoded):
+        if isinstance(im, Exception):
+            inner = _http_exception(400, _DECODE_DETAIL)
+            out[i] = _http_exception(400, f"Image validation or preprocessing failed: {str(inner)}")
+    good = [i for i, im in enumerate(decoded) if not isinstance(im, Exception)]
+    if not device:  # only what the rule resizes goes to the device
+        good = [i for i in good if preprocess_size(decoded[i].shape[1], decoded[i].shape[0], mode)]
+    if good:
+        res = Backend.get().preprocess_images([decoded[i] for i in good], mode, host=not device)
+        for i, t in zip(good, res):
+            out[i] = t
+    return out
+
+
 async def validate_and_preprocess_image(image_bytes: bytes, request_id: str, preprocessing: str) -> np.ndarray:
     try:
         try:
